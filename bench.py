@@ -15,7 +15,11 @@ path over the shard, inputs resident in HBM:
 value = total plain bytes of the batch / max over ranks of the step time   [GiB/s, 2^30]; strong scaling
 (the batch is fixed, N GPUs share it).
 
-Extra JSON fields: per-direction times and rates; the packed-output mode (hhuff_{de,en}code_batch_packed)
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs where --dump-outputs DIR
+says (dump_outputs) and prints the line: the headline, the per-direction times and rates of the timed steps and
+the algorithmic roofline they imply.  Everything else takes runs of its own and waits behind --full:
+
+--full JSON fields: the packed-output mode (hhuff_{de,en}code_batch_packed)
 timed on the same shard; `roofline` for the dominant kernel (algorithmic bytes per launch over its HIP-event
 duration; HBM traffic from rocprofv3 PMC passes run before this process touches the GPU) plus a `secondary`
 ceiling (VALU / LDS issue from the SQ counters); N = 1 only: the other BASELINE configs (c2, c3, c5), the
@@ -48,6 +52,13 @@ def parse():
     ap.add_argument("--config", default="c4")
     ap.add_argument("--strings", "--n", dest="n", type=int, default=None,
                     help="strings in the whole batch (default: the config's N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (PMC traffic passes, the copy peak, the packed-output "
+                         "legs, the other configs, per-string latency, the host-inclusive rate, the CPU baseline); the "
+                         "--no-* options below switch single ones off again.  Without --full only the headline step is "
+                         "set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="strings in the CPU-baseline sample (0: 4M)")
     ap.add_argument("--cpu-threads", type=int, default=None)
@@ -60,7 +71,10 @@ def parse():
     ap.add_argument("--force-pg", action="store_true",
                     help="create the process group (and run the exchange) even in a world of one rank: exercises the "
                          "RCCL branch on a one-GPU box under torch.distributed.run --nproc-per-node 1")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: nothing beside the headline step
+        args.no_cpu_baseline = args.no_traffic = args.no_host = args.no_extra = args.no_packed = True
+    return args
 
 
 def _template_args(name):
@@ -128,7 +142,7 @@ def pmc_passes(args, config=None, groups=None, n=None):
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return {}
-    child = [sys.executable, os.path.abspath(__file__), "--pmc-child", "--steps", "2", "--warmup", "1",
+    child = [sys.executable, os.path.abspath(__file__), "--pmc-child", "--full", "--steps", "2", "--warmup", "1",
              "--no-cpu-baseline", "--no-traffic", "--no-host", "--no-extra", "--config", config or args.config]
     if (n or args.n) and config is None:
         child += ["--strings", str(n or args.n)]
@@ -222,6 +236,71 @@ def timed_events(torch, fns, steps, warmup, pg, dist):
 
 def mean(x):
     return sum(x) / len(x)
+
+
+DUMP_SAMPLE, DUMP_SEED = 65536, 20240607  # strings whose bytes are dumped whole (about 25 MB for c4's two directions)
+DUMP_STRINGS_PER_BLOCK, DUMP_BYTES_PER_BLOCK = 1024, 4096
+
+
+def dump_outputs(torch, directory, name, out, starts, out_len, status):
+    """--dump-outputs: what one direction of the last timed step handed its caller -- `out` in the slot layout
+    (string i at out[starts[i] : starts[i] + out_len[i]]; out_len -1 = FAIL, no bytes), out_len and status -- as
+    DIR/<name>_*.npy.  Only bytes a caller may read are dumped: the gaps between the slots are never written.
+      <name>_sample_index  float64 [m]     the strings of the sample: m = min(n, 65536) indices, seeded, ascending
+      <name>_sample_len    float32 [m]     out_len of those strings (-1 = FAIL)
+      <name>_sample_status float32 [m]     status of those strings
+      <name>_sample_bytes  float32 [sum]   their output bytes, back to back in index order
+      <name>_strings       float64 [ceil(n/1024), 3]   per 1,024 consecutive strings: output bytes, FAILs, sum of status
+      <name>_bytes         float64 [ceil(size/4096), 2]   per 4,096 consecutive positions of `out`: the sum of the valid
+                           bytes and their sum weighted by (position mod 251) + 1 -- every output byte of the batch
+    The inputs are seeded, so two runs with the same arguments write identical files."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+
+    def save(suffix, t, dtype):
+        np.save(os.path.join(directory, "%s_%s.npy" % (name, suffix)), t.cpu().numpy().astype(dtype))
+
+    n = int(out_len.numel())
+    size = int(out.numel())
+    if out.is_cuda:
+        torch.cuda.synchronize()
+    starts = starts.to(torch.int64)
+    lens = torch.clamp(out_len.to(torch.int64), min=0)  # FAIL (-1): no bytes
+    st = status.to(torch.int64)
+    # the sample
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(max(n, 1), size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(pick).to(out.device)
+    sl = lens[idx]
+    first = torch.cumsum(sl, 0) - sl
+    src = torch.repeat_interleave(starts[idx] - first, sl) + torch.arange(int(sl.sum().item()), device=out.device)
+    save("sample_index", idx, np.float64)
+    save("sample_len", out_len[idx], np.float32)
+    save("sample_status", status[idx], np.float32)
+    save("sample_bytes", out[src], np.float32)
+    # every string, in blocks
+    nb = -(-n // DUMP_STRINGS_PER_BLOCK)
+    cols = torch.zeros(nb * DUMP_STRINGS_PER_BLOCK, 3, dtype=torch.int64, device=out.device)
+    cols[:n, 0], cols[:n, 1], cols[:n, 2] = lens, (out_len == -1).to(torch.int64), st
+    save("strings", cols.view(nb, DUMP_STRINGS_PER_BLOCK, 3).sum(1), np.float64)
+    del cols
+    # every valid byte, in blocks of positions: +1 at each string's first byte, -1 one past its last
+    mark = torch.zeros(size + 1, dtype=torch.int32, device=out.device)
+    one = torch.ones(n, dtype=torch.int32, device=out.device)
+    mark.index_add_(0, starts, one)
+    mark.index_add_(0, starts + lens, -one)
+    valid = torch.cumsum(mark[:-1], 0, dtype=torch.int32) > 0
+    del mark, one
+    nb = -(-size // DUMP_BYTES_PER_BLOCK)
+    v = torch.zeros(nb * DUMP_BYTES_PER_BLOCK, dtype=torch.int32, device=out.device)
+    v[:size] = torch.where(valid, out.to(torch.int32), 0)
+    del valid
+    w = (torch.arange(nb * DUMP_BYTES_PER_BLOCK, device=out.device) % 251 + 1).to(torch.int32)
+    sums = torch.stack([v.view(nb, -1).sum(1), (v * w).view(nb, -1).sum(1)], 1)
+    save("bytes", sums, np.float64)
+    del v, w
+    if out.is_cuda:
+        torch.cuda.empty_cache()
 
 
 def launch_plan(gpus, env, backend, device_count):
@@ -400,6 +479,13 @@ def main():
             ([run_exchange] if pg else [])
         slot_enc, slot_dec = 0, (1 if do_enc else 0)
     ms_step, per = timed_events(torch, fns, args.steps, args.warmup, pg, dist)
+    if args.dump_outputs:  # before the packed legs, which write out_len / status again
+        tag = "" if world == 1 else "_rank%d" % rank
+        if do_enc:
+            e_starts = off32[:-1].to(torch.int64) & 0xFFFFFFFF
+            dump_outputs(torch, args.dump_outputs, "encode" + tag, enc_out, e_starts, enc_len, enc_st)
+        if do_dec:
+            dump_outputs(torch, args.dump_outputs, "decode" + tag, dec_out, (h_off[:-1] * 8) // 5, dec_len, dec_st)
     if args.pmc_child and args.config == "c5":  # c5's own operation, flatten_string framing, for its PMC pass
         f_out = torch.empty(P + 11 * n + 16, dtype=torch.uint8, device="cuda")
         f_len = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -458,7 +544,7 @@ def main():
         sec = secondary(pmc.get(dominant, {}))
         if sec:
             roof["secondary"] = sec
-        cp = copy_peak(torch)
+        cp = copy_peak(torch) if args.full else None  # a measurement of its own
         if cp:
             roof["measured_copy_peak"] = cp  # torch copy_ (the runtime's blit / SDMA copy)
         # the guide's measured float4 (16 B a lane) copy, MI355X_MICROARCH.md: what a streaming kernel reaches

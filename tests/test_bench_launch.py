@@ -163,7 +163,7 @@ def test_bench_two_ranks_with_traffic_passes():
     for k in bench.LAUNCHER_ENV:
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--strings", "262144", "--steps", "2",
-           "--warmup", "1", "--no-extra", "--no-host", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-extra", "--no-host", "--no-cpu-baseline"]
     line = _run_traffic_on(cmd, env)
     assert line["n_gpus"] == 2 and line["dist_backend"] == "gloo"
     assert "traffic_note" in line and "131072 strings" in line["traffic_note"]
@@ -187,7 +187,8 @@ def test_bench_rccl_world_of_one_with_traffic_passes():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strings",
-           "262144", "--steps", "2", "--warmup", "1", "--no-extra", "--no-host", "--no-cpu-baseline", "--force-pg"]
+           "262144", "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-host", "--no-cpu-baseline",
+           "--force-pg"]
     line = _run_traffic_on(cmd, env)
     assert line["dist_backend"] == "nccl" and line["n_gpus"] == 1
     assert line["roofline"]["traffic"] is not None and line["roofline"]["traffic"] > 0

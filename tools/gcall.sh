@@ -2,8 +2,8 @@
 # The GPU-box recipe (run through gpurun from the repo root):  T=<tag> bash tools/gcall.sh STEP...
 #   tests       the whole -m gpu suite (K="<pytest -k expr>" narrows it)
 #   smoke       __graft_entry__.smoke()
-#   bench       python3 bench.py (BENCH_ARGS="..." appends arguments)
-#   trace       kernel trace + stats of the c4 bench (rocprofv3 --kernel-trace --stats)
+#   bench       python3 bench.py (BENCH_ARGS="..." appends arguments; "--full" for every secondary key of the line)
+#   trace       kernel trace + stats of the whole bench, bench.py --full (rocprofv3 --kernel-trace --stats), under $OUT
 #   prof_c4 / prof_c3 / prof_c5   tools/profile.sh: trace + PMC passes of one config
 #   ab          tools/ab.py $AB_ARGS (interleaved A/B of two builds, see tools/ab.py)
 #   per_string  tools/per_string_bench 1 4 16 (caller threads)
@@ -11,6 +11,7 @@
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 T=${T:-run}
+OUT=${OUT:-out}  # where the trace step writes
 for step in "$@"; do
   case $step in
     tests)
@@ -21,8 +22,9 @@ for step in "$@"; do
     bench)
       timeout -k 10 600 python3 -u bench.py $BENCH_ARGS > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || exit 5 ;;
     trace)
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${T}/trace -o run -- \
-        python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-traffic --no-host > gpurun_out/${T}_trace.log 2>&1 || exit 6 ;;
+      mkdir -p "$OUT"
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT"/prof_${T}/trace -o run -- \
+        python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-traffic --no-host > "$OUT"/${T}_trace.log 2>&1 || exit 6 ;;
     prof_c4)
       timeout -k 10 900 bash tools/profile.sh ${T}_c4 --no-extra || exit 6 ;;
     prof_c3|prof_c5)
