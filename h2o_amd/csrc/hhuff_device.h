@@ -433,9 +433,6 @@ __device__ __forceinline__ void lds_zero(uint8_t* base, uint32_t a, uint32_t b, 
 // the lane's next symbols or lie past its decoded length inside its slot (5 symbols' room), so the stores need
 // no redirection of untaken bytes to a trash byte (c4 decode -7 % against that; one unaligned ds_write_b16 for
 // both bytes was measured too: 0.66 -> 0.98 ms).
-#ifndef HHUFF_DEC_READ_FIRST  // 1 (default): a bulk step's second LUT read goes to the LDS ahead of the first entry's
-#define HHUFF_DEC_READ_FIRST 1   // byte stores: c4 decode -0.6 %, c3 -0.9 % (profiles/r06m_decode_read_first_ab.jsonl)
-#endif
 __device__ __forceinline__ void bulk_put2(uint32_t o, uint32_t e, uint32_t trash) {
     (void)trash;
     lds_st8(o, e);
@@ -480,7 +477,6 @@ __device__ __forceinline__ DecResult decode_staged_lane_v7(const uint32_t* stage
             const uint32_t e = T.lut[w >> (32 - HHUFF_LUT_BITS)];
             const uint32_t sl = (uint32_t)((int32_t)e >> 31);  // LONG: nothing taken from the window
             uint32_t cons = lut_l12(e);  // LONG entries carry L12 = 0
-#if HHUFF_DEC_READ_FIRST
             {  // the second lookup goes to the LDS ahead of the first entry's byte stores (in-order LDS queue)
                 const uint32_t wb = w << cons;
                 const uint32_t eb = T.lut[wb >> (32 - HHUFF_LUT_BITS)];
@@ -492,19 +488,6 @@ __device__ __forceinline__ DecResult decode_staged_lane_v7(const uint32_t* stage
                 accb |= eb;
                 cons += lut_l12(eb);
             }
-#else
-            bulk_put2(o, e, trash);
-            o += (e >> 28) & 3u;
-            accb |= e;
-            {
-                const uint32_t wb = w << cons;
-                const uint32_t eb = T.lut[wb >> (32 - HHUFF_LUT_BITS)];
-                bulk_put2(o, eb, trash);
-                o += (eb >> 28) & 3u;
-                accb |= eb;
-                cons += lut_l12(eb);
-            }
-#endif
             if (longchk && __builtin_amdgcn_ballot_w64(sl != 0u) != 0) {
                 if (sl) {
                     const uint32_t k = min((uint32_t)__builtin_clz(~w | 1u), 30u);
@@ -774,13 +757,6 @@ __device__ __forceinline__ void place_bits(O obase, uint32_t tb, uint64_t c, uin
     if (sh + n > 64u) or_word(obase, a + 2u, (uint32_t)t << (32u - sh));  // sh > 0 here
 }
 
-#ifndef HHUFF_ENC_HEAD_REUSE  // encode_chunk_v2: the head's stage word seeds the bulk loop (no second read of it)
-#define HHUFF_ENC_HEAD_REUSE 0
-#endif
-#ifndef HHUFF_ENC_OR3  // encode_chunk_v2's bulk step: the third output word ORed on every step (see put4m)
-#define HHUFF_ENC_OR3 0
-#endif
-
 template <class O>
 struct EncV2 {
     const uint2* enc;
@@ -833,19 +809,11 @@ struct EncV2 {
         const uint32_t sh = tb & 31u;
         const uint64_t u = t >> sh;
         const uint32_t a = tb >> 5;
-#if defined(HHUFF_X_ENC_NOOR)  // ablation (output wrong by design): no placement (one OR keeps the values live)
-        if (__builtin_amdgcn_ballot_w64((uint32_t)u == 0x12345u) != 0) or_word(obase, a, (uint32_t)(u >> 32));
-#else
         or_word(obase, a, (uint32_t)(u >> 32));
         or_word(obase, a + 1u, (uint32_t)u);
-#endif
-#if HHUFF_ENC_OR3  // the third word's OR on every step (0 where nothing spills into it): no vote, no branch
-        or_word(obase, a + 2u, sh + nf > 64u ? (uint32_t)t << ((32u - sh) & 31u) : 0u);
-#else
         if (__builtin_amdgcn_ballot_w64(sh + nf > 64u) != 0) {
             if (sh + nf > 64u) or_word(obase, a + 2u, (uint32_t)t << (32u - sh));
         }
-#endif
         tb += nm;
     }
 };
@@ -889,11 +857,7 @@ __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint3
     {
         const uint32_t jlv = E.live ? jl : 0u;  // a lane that failed in its head places nothing more
         const uint32_t jend = wave_max_u32(jlv);  // uniform trip count: no vote per step
-#if HHUFF_ENC_HEAD_REUSE
-        uint32_t wn = w0;
-#else
         uint32_t wn = sw[min(0u, jlast)];
-#endif
         // U == 2: the extra dword past jend has onm == 0 (jlv <= jend) and a clamped read
         if constexpr (U == 2) for (uint32_t j = 0; j < jend; j += 2) {
             const uint32_t w0 = wn, w1 = sw[min(j + 1u, jlast)];
@@ -909,23 +873,7 @@ __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint3
             const uint32_t w = wn;
             wn = sw[min(j + 1u, jlast)];
             const uint32_t onm = ~(uint32_t)((int32_t)((j - jf) | (jlv - 1u - j)) >> 31);  // jf <= j < jlv
-#if defined(HHUFF_X_ENC_TABCF)  // ablation (output wrong by design): conflict-free table reads (entry = lane % 32 + 32)
-            const uint32_t lq = (uint32_t)(__lane_id() & 31) + 32u + (w & 0u);
-            E.put4m(enc[lq], enc[lq ^ 1u], enc[lq ^ 2u], enc[lq ^ 3u], onm);
-#elif defined(HHUFF_X_ENC_TABDEP) || defined(HHUFF_X_ENC_TABBC)
-            // ablations: the same conflict-free (TABDEP) / single-entry broadcast (TABBC) reads, still dependent on the
-            // input word (an opaque zero from it), so the input reads and the chain stay
-            uint32_t z;
-            __asm__ volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"(w));
-#if defined(HHUFF_X_ENC_TABDEP)
-            const uint32_t lq = (uint32_t)(__lane_id() & 31) + 32u + z;
-#else
-            const uint32_t lq = 0x61u + z;
-#endif
-            E.put4m(enc[lq], enc[lq ^ 1u], enc[lq ^ 2u], enc[lq ^ 3u], onm);
-#else
             E.put4m(enc[w & 0xFFu], enc[(w >> 8) & 0xFFu], enc[(w >> 16) & 0xFFu], enc[w >> 24], onm);
-#endif
         }
     }
     E.fail = E.fail || (E.live && E.tb >= E.tlim);

@@ -212,9 +212,6 @@ __device__ __forceinline__ bool lit_eq(const uint8_t* a, const char* lit, uint32
 
 // byte equality without an early exit: 16-byte loads issue back to back, one wait covers them
 __device__ __forceinline__ bool bytes_eq(const uint8_t* a, const uint8_t* b, uint32_t n) {
-#ifdef HHUFF_HPE_NOVERIFY  // ablation only (wrong on a hash collision): what the walk's byte checks cost
-    return true;
-#endif
     uint32_t diff = 0, k = 0;
     for (; k + 16u <= n; k += 16u) {
         uint4 x, y;
@@ -429,9 +426,7 @@ struct EncTable {
         while (num >= kMaxEntries) evict_one();
         if (num == 0 && add > cap) return;
         start = (start + kMaxEntries - 1) & (kMaxEntries - 1);
-#ifndef HHUFF_HPE_NOENTST  // ablation only: what the entries' global stores cost the walk
         ent[start] = e;
-#endif
         meta[start * 64] = make_uint4(e.nl | (e.tok << 31), e.vl, e.nh, e.vh);
         size += add;
         ++num;
@@ -590,9 +585,7 @@ __global__ __launch_bounds__(64) void hpe_table_kernel(HpeArgs A) {
                     code = hpe_field(A, t, cur, kSrcIn | cur.noff, kSrcIn | cur.voff, l);
                 }
                 const uint64_t dst = base + 9u + pos;
-#ifndef HHUFF_HPE_NOOPST  // ablation only: what the per-field op stores cost the walk
                 A.op[h] = make_uint4((uint32_t)dst, (uint32_t)(dst >> 32), code, 0u);
-#endif
                 pos += l;
                 cur = nxt;
             }

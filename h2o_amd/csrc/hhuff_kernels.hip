@@ -27,16 +27,6 @@
 
 namespace hhuff {
 
-// A/B builds only (tools/ab.py build NAME -DHHUFF_AB_VARIANTS=1 ..., include path tools/ab): the variant kernels
-// measured and not adopted live in tools/ab/, out of libhhuff.so.  A flag that selects one implies the switch.
-#if !defined(HHUFF_AB_VARIANTS)
-#if defined(HHUFF_STREAM_RK) || defined(HHUFF_STREAM2) || (defined(HHUFF_ENC_INPLACE) && HHUFF_ENC_INPLACE) || \
-    (defined(HHUFF_DEC_SW) && HHUFF_DEC_SW) || (defined(HHUFF_DEC_RUN) && HHUFF_DEC_RUN)
-#define HHUFF_AB_VARIANTS 1
-#else
-#define HHUFF_AB_VARIANTS 0
-#endif
-#endif
 __device__ const uint32_t g_dec_lut[1u << HHUFF_LUT_BITS] = HHUFF_DEC_LUT_INIT;
 __device__ const uint32_t g_name_invalid[8] = HHUFF_NAME_INVALID_INIT;    // raw-literal validity bitmaps
 __device__ const uint32_t g_value_invalid[8] = HHUFF_VALUE_INVALID_INIT;  // (hpack.c:171-180, 200-209)
@@ -188,9 +178,6 @@ __device__ __forceinline__ Tile finish_tile(uint64_t base, int lane, uint32_t n,
     return t;
 }
 
-#ifndef HHUFF_NT_LOAD  // A/B: tile spans fetched with streaming (non-temporal) loads
-#define HHUFF_NT_LOAD 0
-#endif
 template <int NCH>
 struct SpanPrefetch {  // up to NCH x 1 KiB of a tile's input span, 16 B per lane per KiB
     uint4 v[NCH];
@@ -203,15 +190,7 @@ struct SpanPrefetch {  // up to NCH x 1 KiB of a tile's input span, 16 B per lan
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const uint32_t k = (uint32_t)c * 1024u + (uint32_t)lane * 16u;
-#if HHUFF_NT_LOAD  // A/B: the span as streaming loads (read once)
-            if (k < span && k + 16u <= avail) {
-                typedef unsigned int u32x4l __attribute__((ext_vector_type(4)));
-                const u32x4l x = __builtin_nontemporal_load(reinterpret_cast<const u32x4l*>(src + k));
-                v[c] = make_uint4(x.x, x.y, x.z, x.w);
-            }
-#else
             if (k < span && k + 16u <= avail) v[c] = *reinterpret_cast<const uint4*>(src + k);
-#endif
         }
     }
     template <bool kSwap = false>  // kSwap: store big-endian dwords (the v5 decode window reads them)
@@ -265,29 +244,12 @@ struct EdgeRec {
     uint4 m;  // {address lo, address hi, lo, hi}: bytes [lo, hi) of the chunk are ours (lo >= hi: none)
 };
 
-#ifndef HHUFF_NT_STORE  // output pieces as streaming (non-temporal) 16-B stores: c4 decode -2.1 %, encode -0.9 %,
-                        // c2 -3 %, c3 / c5 level (profiles/r05t_nt_store_ab.jsonl; with the per-string lengths and
-                        // statuses streamed too, HHUFF_NT_RES, c4 decode gains less)
-#define HHUFF_NT_STORE 1
-#endif
-#ifndef HHUFF_STREAM_NT
-#define HHUFF_STREAM_NT 0
-#endif
-#ifndef HHUFF_STATUS_DW  // staged decode: a tile's status bytes stored as dwords
-#define HHUFF_STATUS_DW 0
-#endif
-// result stores the kernel never reads back: streaming (non-temporal) with HHUFF_NT_STORE (HHUFF_NT_RES=1 also for
-// the per-string lengths and statuses)
-#ifndef HHUFF_NT_RES
-#define HHUFF_NT_RES 0
-#endif
+// output pieces the kernel never reads back go out as streaming (non-temporal) 16-B stores (the per-string lengths
+// and statuses, st_res, as plain stores: streamed too, c4 decode gains less; the stream kernel's flush must not
+// stream, its lanes write each line piecewise -- DESIGN.md (e))
 typedef unsigned int hh_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st16_out(uint8_t* p, uint4 v) {
-#if HHUFF_NT_STORE
     __builtin_nontemporal_store(hh_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<hh_u32x4*>(p));
-#else
-    *reinterpret_cast<uint4*>(p) = v;
-#endif
 }
 // bytes [lo, hi) of the 16-B chunk v (in registers) to global g (16-B aligned): whole dwords as dword stores, the
 // partial dword at each end as byte stores -- at most 10 predicated stores
@@ -306,13 +268,10 @@ __device__ __forceinline__ void store_range16r(uint8_t* __restrict__ g, uint4 v,
         if (s1 + j < hi) g[s1 + j] = (uint8_t)byte_at(s1 + j);
     }
 }
+
 template <class T>
-__device__ __forceinline__ void st_res(T* p, T v) {
-#if HHUFF_NT_RES
-    __builtin_nontemporal_store(v, p);
-#else
+__device__ __forceinline__ void st_res(T* p, T v) {  // a per-string length or status
     *p = v;
-#endif
 }
 
 // Write LDS bytes [0, ospan) to global [gbase, gbase + ospan) (gbase 16-aligned), keeping only the
@@ -339,8 +298,7 @@ __device__ __forceinline__ void edge_bytes(uint8_t* __restrict__ out, uint64_t g
     if ((lane < 16 || kl != 0) && part && G >= keep_lo && G < keep_hi) out[G] = lds[k + (SWAP ? b ^ 3u : b)];
 }
 // SWAP: the LDS bytes are MSB-first words (the encode stage), byte-swapped in registers on the way out.
-// G: the LDS reads of G chunks ahead of their stores (one LDS round trip per G chunks; 4 (G - 1) more VGPRs)
-template <int NCH, bool SWAP = false, int G = 1>
+template <int NCH, bool SWAP = false>
 __device__ __forceinline__ void region_copy(uint8_t* __restrict__ out, uint64_t gbase, const uint8_t* lds, uint32_t ospan,
                                             uint64_t keep_lo, uint64_t keep_hi, int lane) {
     auto put = [&](uint32_t k, uint4 v) {
@@ -354,19 +312,7 @@ __device__ __forceinline__ void region_copy(uint8_t* __restrict__ out, uint64_t 
             if (hi > lo) store_range16r(out + g, v, lo, hi);
         }
     };
-    for (uint32_t k = (uint32_t)lane * 16u; k < ospan; k += (uint32_t)G * 64u * 16u) {
-        uint4 v[G];
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-            const uint32_t kj = k + (uint32_t)j * 64u * 16u;
-            v[j] = kj < ospan ? *reinterpret_cast<const uint4*>(lds + kj) : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-            const uint32_t kj = k + (uint32_t)j * 64u * 16u;
-            if (kj < ospan) put(kj, v[j]);
-        }
-    }
+    for (uint32_t k = (uint32_t)lane * 16u; k < ospan; k += 64u * 16u) put(k, *reinterpret_cast<const uint4*>(lds + k));
     if (HHUFF_EDGE_BYTES) edge_bytes<SWAP>(out, gbase, lds, ospan, keep_lo, keep_hi, lane);
 }
 
@@ -549,12 +495,6 @@ __device__ __forceinline__ void decode_direct(const DecArgs& A, uint32_t s, uint
 // never overwrite a source another lane still needs.  The next tile's input then goes into the other
 // half, beside the packed run, before the run's 16-B stores are issued (the pipeline order of the slot
 // layout, whose commit also precedes the stores).
-#ifndef HHUFF_DEC_COPY_G  // decode_staged_kernel's slot-layout copy-out: chunks whose LDS reads go ahead of their stores
-#define HHUFF_DEC_COPY_G 1
-#endif
-#ifndef HHUFF_DEC_TI_TOP  // decode_staged_kernel: the tile-after-next's offsets issued at the loop top, consumed in
-#define HHUFF_DEC_TI_TOP 1   // the same trip (c4 decode -2.2 %, c2 -1.5 %; profiles/r06v_decode_ti_top_ab.jsonl)
-#endif
 template <int WAVES, int IN_STAGE, int OUT_STAGE, bool PACKED>
 __global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
     constexpr uint32_t Z = IN_STAGE + OUT_STAGE + 256u;  // + 16 slack: the run's last 16-B chunk may read past Z
@@ -653,19 +593,14 @@ __global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
         nxt = plan(base + stride, ti, PACKED ? 1u : 0u);
         nxt_name = ti.name_word;
         if (nxt.fits) pf.issue(A.in, A.in_size, nxt.a0(), nxt.span(), lane);
-#if !HHUFF_DEC_TI_TOP
-        ti = issue_tile(base + 2 * stride, lane, A.n, A.in_off, A.in_len, A.is_name_bits, A.out_off);
-#endif
     }
     PROF_DECL
     for (;;) {
         const uint64_t nbase = base + stride;
-#if HHUFF_DEC_TI_TOP
         // the offsets of the tile after next, issued at the top and consumed at this tile's plan step below: no
         // loaded register lives across the loop's back edge, where a PHI copy would wait for it behind this
         // tile's stores (the ISA had s_waitcnt vmcnt(3) / (2) there, in front of two such copies)
         ti = issue_tile(nbase + stride, lane, A.n, A.in_off, A.in_len, A.is_name_bits, A.out_off);
-#endif
         // ---- the current tile: steps and verdicts ----
         const Plan& t = cur;
         const uint32_t ti_i = (uint32_t)base + (uint32_t)lane;
@@ -778,16 +713,9 @@ __global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
         nn = plan(nbase + stride, ti, PACKED ? par : 0u);
         nn_name = ti.name_word;
         if (have_nn && nn.fits) pf.issue(A.in, A.in_size, nn.a0(), nn.span(), lane);
-#if !HHUFF_DEC_TI_TOP
-        ti = issue_tile(nbase + 2 * stride, lane, A.n, A.in_off, A.in_len, A.is_name_bits, A.out_off);
-#endif
         PROF_MARK(3);  // commit + plan
         // ---- the current tile: stores ----
-#if defined(HHUFF_X_NOSTORE) || defined(HHUFF_X_NOSTORE_OUT)  // ablations (output wrong by design): no output stores
-        if (false) {
-#else
         if (cur.fits) {
-#endif
             if (PACKED) {
                 const uint64_t gb = G & ~15ull;
                 const uint32_t ps = (uint32_t)(((G + T_run + 15u) & ~15ull) - gb);
@@ -801,8 +729,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
                     region_copy_deferred(A.out, cur.obase(), obuf, cur.ospan, cur.olo(), cur.ohi(), lane,
                                          A.edges + 2 * (base >> 6));
                 else
-                    region_copy<(OUT_STAGE + 1023) / 1024, false, HHUFF_DEC_COPY_G>(A.out, cur.obase(), obuf, cur.ospan,
-                                                                                           cur.olo(), cur.ohi(), lane);
+                    region_copy<(OUT_STAGE + 1023) / 1024>(A.out, cur.obase(), obuf, cur.ospan, cur.olo(), cur.ohi(), lane);
             } else if (t.valid && ol != kFailLen) {
                 lane_copy(A.out + cur.dst_g, obuf + cur.op0, ol);
             }
@@ -811,23 +738,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
             A.edges[2 * (base >> 6)].m = make_uint4(0u, 0u, 0u, 0u);
             A.edges[2 * (base >> 6) + 1].m = make_uint4(0u, 0u, 0u, 0u);
         }
-#if HHUFF_STATUS_DW
-        // a whole tile's status bytes as 16 dword stores (4 lanes' bytes each) instead of 64 byte stores; a listed
-        // string's byte is 0 here and written by split_decode_kernel, which runs after this kernel
-        const bool st_dw = !PACKED && base + 64u <= A.n && (((uintptr_t)(A.status + base)) & 3u) == 0;  // (uniform)
-        if (st_dw) {
-            uint32_t sv = (t.valid && !listed ? (uint32_t)st : 0u) << (8u * ((uint32_t)lane & 3u));
-            sv |= (uint32_t)__shfl_xor((int)sv, 1);
-            sv |= (uint32_t)__shfl_xor((int)sv, 2);
-            if ((lane & 3) == 0) *reinterpret_cast<uint32_t*>(A.status + base + (uint32_t)lane) = sv;
-            if (t.valid && !listed) A.out_len[ti_i] = ol;
-        } else
-#endif
-#if defined(HHUFF_X_NOSTORE) || defined(HHUFF_X_NOSTORE_LEN)  // (no length / status stores)
-        if (false) {
-#else
         if (t.valid && !listed) {
-#endif
             st_res(A.out_len + ti_i, ol);
             st_res(A.status + ti_i, st);
             if (PACKED) {
@@ -1299,16 +1210,6 @@ __device__ __forceinline__ void store_range16(uint8_t* __restrict__ g, const uin
     }
 }
 
-// 1: the prefetched window lands before the flush stores, removing the loop-top wait that also waits for them.
-// Measured slower (c3 decode 0.293 -> 0.296 ms, c5 0.426 -> 0.449, profiles/r04ak_stream_early_ab.log): the
-// window's loads, not the stores, are what that wait is for, and landing them earlier only shortens their time
-#ifndef HHUFF_STREAM_EARLY
-#define HHUFF_STREAM_EARLY 0
-#endif
-#ifndef HHUFF_STREAM_TAILWHOLE  // 1 (default): a string's last output chunk as one 16-B store when it lies in the
-#define HHUFF_STREAM_TAILWHOLE 1  // string's own slot: c3 decode -1.1 %, c5 -1.5 %, write traffic unchanged
-#endif                            // (profiles/r06i_stream_tail_whole_ab.jsonl, r06i_c3_decode_pmc.txt)
-
 // SEG: flush granularity -- whole SEG-byte aligned output segments leave before a string's end
 template <int WAVES, int NW, int OUT, int SEG = 16>
 __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, unsigned long long* __restrict__ counter) {
@@ -1331,9 +1232,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
     __syncthreads();
     const DecTables T{sm.lut, sm.kinfo, sm.ones};
     const int lane = threadIdx.x & 63;
-#if HHUFF_STREAM_TAILWHOLE
     const bool slots = A.out_off == nullptr && A.in_len == nullptr;  // implicit output slots floor(8 in_off / 5)
-#endif
     uint32_t* win = &sm.win[threadIdx.x][1];
     const lds_u32* st = (const lds_u32*)win;
     uint8_t* obuf = sm.out[threadIdx.x];
@@ -1453,7 +1352,6 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
                 const uint32_t e = T.lut[w >> (32 - HHUFF_LUT_BITS)];
                 const uint32_t sl = (uint32_t)((int32_t)e >> 31);
                 uint32_t cons = lut_l12(e);  // LONG entries carry L12 = 0
-#if HHUFF_DEC_READ_FIRST
                 {  // the second lookup ahead of the first entry's byte stores (decode_staged_lane_v7)
                     const uint32_t wb2 = w << cons;
                     const uint32_t eb = T.lut[wb2 >> (32 - HHUFF_LUT_BITS)];
@@ -1465,19 +1363,6 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
                     accb |= eb;
                     cons += lut_l12(eb);
                 }
-#else
-                bulk_put2(o, e, trash);
-                o += (e >> 28) & 3u;
-                accb |= e;
-                {
-                    const uint32_t wb2 = w << cons;
-                    const uint32_t eb = T.lut[wb2 >> (32 - HHUFF_LUT_BITS)];
-                    bulk_put2(o, eb, trash);
-                    o += (eb >> 28) & 3u;
-                    accb |= eb;
-                    cons += lut_l12(eb);
-                }
-#endif
                 if (longchk && __builtin_amdgcn_ballot_w64(sl != 0u) != 0) {
                     if (sl) {
                         const uint32_t k = min((uint32_t)__builtin_clz(~w | 1u), 30u);
@@ -1570,16 +1455,6 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
         }
 
         PROF_MARK(3);
-#if HHUFF_STREAM_EARLY
-        // land the prefetched window before this round's flush stores: loads and stores share one in-order
-        // counter on gfx950, so a wait for it next round, behind the stores, would wait for them too
-#pragma unroll
-        for (int j = 0; j < NW / 4; ++j) {
-            uint32_t a0 = pfv[j].x, a1 = pfv[j].y, a2 = pfv[j].z, a3 = pfv[j].w;
-            asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) :: "memory");
-            pfv[j] = make_uint4(a0, a1, a2, a3);
-        }
-#endif
         // ---- 4. flush whole chunks, carry the partial one; finish strings ----
         if (busy) {
             flags |= ((accb >> 24) | (accb >> 26) | (acc1 >> 24) | (acc2 >> 26) | (accl >> 14)) & 3u;
@@ -1597,11 +1472,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
             }();
             uint8_t* gchunk = A.out + ((dst + ocnt) & ~(uint64_t)(SEG - 1));
             const uint32_t hs = head ? (uint32_t)(dst & (SEG - 1u)) : 0u;  // head segment: the string starts here
-#ifdef HHUFF_X_NOSTORE
-            if (false) {
-#else
             if (!done || ok) {  // a failed string's output is unspecified: skip its last stores
-#endif
                 // whole 16-B chunks now: all of them at the string's end, else those of whole segments
                 const uint32_t nfull = done ? nb >> 4 : (nb / SEG) * (SEG / 16u);
                 for (uint32_t k = 0; k < nfull; ++k) {
@@ -1610,16 +1481,11 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
                     if (c0 < hs)
                         store_range16(gchunk + c0, obuf + c0, hs - c0, 16u);
                     else
-#if HHUFF_STREAM_NT  // A/B: the flush's whole chunks as streaming stores
-                        st16_out(gchunk + c0, *reinterpret_cast<const uint4*>(obuf + c0));
-#else
                         *reinterpret_cast<uint4*>(gchunk + c0) = *reinterpret_cast<const uint4*>(obuf + c0);
-#endif
                 }
                 const uint32_t c0 = 16u * nfull;
                 if (done) {
                     const uint32_t lo = hs > c0 ? hs - c0 : 0u;
-#if HHUFF_STREAM_TAILWHOLE
                     // implicit slots: the last chunk goes out whole when all of it lies in this string's slot (the
                     // bytes past the output are the slot's unused tail, unspecified) -- one 16-B store, not <= 10
                     const bool whole = slots && lo == 0u && nb > c0 &&
@@ -1627,7 +1493,6 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
                     if (whole)
                         *reinterpret_cast<uint4*>(gchunk + c0) = *reinterpret_cast<const uint4*>(obuf + c0);
                     else
-#endif
                     if (nb - c0 > lo) store_range16(gchunk + c0, obuf + c0, lo, nb - c0);
                 } else if (nfull) {  // carry the partial segment to the buffer's start
                     head = false;
@@ -1638,10 +1503,8 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream_kernel(DecArgs A, un
             ocnt += made;
             P += (uint32_t)(pm - pm0);
             if (done) {
-#ifndef HHUFF_X_NOSTORE
                 A.out_len[i] = ok ? ocnt : kFailLen;
                 A.status[i] = ok ? soft_bits(is_name, ocnt, flags, first, lastb) : kStatusFail;
-#endif
                 busy = false;
             }
         }
@@ -1903,30 +1766,12 @@ __device__ __forceinline__ SortChunk sort_chunk_issue(const EncArgs& A, uint64_t
     return SortChunk{A.in_off[ic], A.in_off[ic + 1], A.in_off[min(cb, (uint64_t)A.n - 1u)],
                      A.in_off[min(cb + ns, (uint64_t)A.n)]};
 }
-#ifndef HHUFF_ENC_COPY_EARLY  // sorted encoder: the batched copy-out's reads issued right after barrier 3
-#define HHUFF_ENC_COPY_EARLY 0
-#endif
-#ifndef HHUFF_ENC_SORTREC  // sorted encoder: one record read (place -> offset | length) before a lane's encode
-#define HHUFF_ENC_SORTREC 0
-#endif
-#ifndef HHUFF_ENC_COPY_BATCH  // sorted encoder's copy-out: all LDS reads of a thread's chunks ahead of the stores
-#define HHUFF_ENC_COPY_BATCH 1   // (c4 encode -2.0 %, c2 -3.8 %; 122 VGPRs, still 4 waves a SIMD: r06aa_encode_copy_batch_ab.jsonl)
-#endif
-#ifndef HHUFF_ENC_EARLY
-// 1: the next chunk's offsets are loaded a chunk ahead and both they and the next span are waited for after
-// barrier 3, before the chunk's stores (c4 encode 0.680 -> 0.655 ms, profiles/r04aa_encode_early_ab.log);
-// 0: the round-3 order, where the compiler's vmcnt waits for those loads also waited for the stores
-#define HHUFF_ENC_EARLY 1
-#endif
 // NS strings per chunk on NS / SPT threads (SPT strings a thread); CH bytes of stage.  SPT = 2 pairs the
 // sorted ranks t and NS - 1 - t on thread t, so every lane encodes a short and a long string one after the
 // other and the lanes' work (about twice the mean length) is even across the workgroup: no wave waits at the
 // chunk's barriers for a longest length group.
 #ifndef HHUFF_ENCO_SPT
 #define HHUFF_ENCO_SPT 1
-#endif
-#ifndef HHUFF_ENCO_PAD  // A/B builds: extra LDS bytes per workgroup (fewer resident workgroups)
-#define HHUFF_ENCO_PAD 0
 #endif
 template <int NS, int CH, int SPT = 1>
 __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
@@ -1936,20 +1781,9 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
     __shared__ __attribute__((aligned(16))) uint2 s_enc[512];  // 256..511: bytes outside a string
     __shared__ __attribute__((aligned(16))) uint32_t s_in[CH / 4 + 8];
     __shared__ __attribute__((aligned(16))) uint32_t s_out[CH / 4 + 8];
-#if HHUFF_ENC_SORTREC
-    // sorted place -> {offset in the span (14 bits) | length << 14}, written by the string's own thread once its
-    // place is known, then overwritten with the encoded length (read back by that thread after barrier 3)
-    static_assert(CH <= 16384, "14-bit span offsets");
-    __shared__ uint32_t s_rec[kSortStr];
-#else
     __shared__ uint2 s_str[kSortStr];  // {offset in the span, length} of chunk string t
     __shared__ uint16_t s_perm[kSortStr];
-#endif
     __shared__ uint32_t s_bin[kSortBins];  // strings per bin, then the bins' first places
-#if HHUFF_ENCO_PAD
-    __shared__ uint32_t s_pad[HHUFF_ENCO_PAD / 4];
-    if (A.n == 0xFFFFFFFFu) s_pad[threadIdx.x % (HHUFF_ENCO_PAD / 4)] = 0u;  // (never: keeps the bytes allocated)
-#endif
     const uint32_t t = threadIdx.x, lane = t & 63u;
     for (uint32_t k = t; k < 512; k += NT) s_enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
     const uint64_t nch = ((uint64_t)A.n + kSortStr - 1) / kSortStr;
@@ -1962,15 +1796,7 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
         for (int j = 0; j < NV; ++j) {
             const uint32_t k = (uint32_t)j * (16u * NT) + t * 16u;
             const uint64_t g = (uint64_t)a0 + k;
-#if HHUFF_NT_LOAD
-            if (k < span && span <= (uint32_t)CH && g + 16 <= A.in_size) {
-                typedef unsigned int u32x4l __attribute__((ext_vector_type(4)));
-                const u32x4l x = __builtin_nontemporal_load(reinterpret_cast<const u32x4l*>(A.in + g));
-                v[j] = make_uint4(x.x, x.y, x.z, x.w);
-            }
-#else
             if (k < span && span <= (uint32_t)CH && g + 16 <= A.in_size) v[j] = *reinterpret_cast<const uint4*>(A.in + g);
-#endif
         }
     };
     auto commit_span = [&](const uint4 (&v)[NV], const SortChunk& q) {
@@ -1987,7 +1813,7 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
 #pragma unroll
         for (int u = 0; u < SPT; ++u) q[u] = sort_chunk_issue(A, qb, t + (uint32_t)u * NT, NS);
     };
-    auto land = [](SortChunk (&q)[SPT]) {  // wait for a chunk's offsets here (see HHUFF_ENC_EARLY)
+    auto land = [](SortChunk (&q)[SPT]) {  // wait for a chunk's offsets here (see below)
 #pragma unroll
         for (int u = 0; u < SPT; ++u) __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e), "+v"(q[u].lo), "+v"(q[u].hi) : : "memory");
     };
@@ -1998,9 +1824,6 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
     // nothing reads those areas any more (three barriers a chunk in all).
     uint4 pv[NV];
     uint32_t bin[SPT], rank[SPT];
-#if HHUFF_ENC_SORTREC
-    uint32_t mypos[SPT];
-#endif
     auto prepare = [&](const SortChunk (&q)[SPT], uint64_t qb, uint32_t z0) {
         const uint32_t sp = span_of(q[0]);
         if (sp > (uint32_t)CH) return;  // workgroup-uniform: the per-thread path needs none of it
@@ -2011,9 +1834,7 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
         for (int u = 0; u < SPT; ++u) {
             const uint32_t tt = t + (uint32_t)u * NT;
             const uint32_t ln = qb + tt < A.n ? q[u].e - q[u].s : 0u;
-#if !HHUFF_ENC_SORTREC
             s_str[tt] = make_uint2(q[u].s - (q[0].lo & ~15u), ln);
-#endif
             // counting sort by the bulk loop's trip count (encode_chunk_v2: dwords from the string's first
             // aligned dword to its end), which the wave's longest string sets
             bin[u] = ln ? min((q[u].s + ln - (q[u].s & ~3u)) >> 2, kSortBins - 1u) : 0u;
@@ -2024,13 +1845,11 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
     issue_chunk(cur, c * kSortStr);
     issue_span(pv, cur[0]);
     prepare(cur, c * kSortStr, 0u);
-#if HHUFF_ENC_EARLY
     // the next chunk's offsets are loaded a chunk ahead (after barrier 2) and waited for after barrier 3,
     // before the chunk's stores: no load is then waited for behind a data-dependent number of stores
     SortChunk nxt[SPT];
     issue_chunk(nxt, (c + gridDim.x < nch ? c + gridDim.x : c) * kSortStr);
     land(nxt);  // (once)
-#endif
     PROF_DECL  // profile builds: barrier 1 / ranks + barrier 2 / encode / barrier 3 + lengths / copy out / prepare
     for (;;) {
         const uint64_t cb = c * kSortStr;
@@ -2038,12 +1857,7 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
         EdgeRec* rec = A.edges + 2 * c;  // two records a chunk (sorted_edge_recs)
         const uint64_t cn = c + gridDim.x;
         const bool more = cn < nch;
-#if !HHUFF_ENC_EARLY
-        SortChunk nxt[SPT];
-        issue_chunk(nxt, (more ? cn : c) * kSortStr);  // in flight during this chunk
-#endif
-        const uint64_t cn2 = cn + gridDim.x;  // (HHUFF_ENC_EARLY) the chunk after next
-        (void)cn2;
+        const uint64_t cn2 = cn + gridDim.x;  // the chunk after next
         __syncthreads();  // the chunk's stage, strings and ranks are in
         PROF_MARK(0);
         if (span > (uint32_t)CH) {  // (workgroup-uniform) a chunk larger than the stage: one thread per string
@@ -2063,7 +1877,6 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
             if (!more) break;
             issue_span(pv, nxt[0]);
             prepare(nxt, cn * kSortStr, 0u);
-#if HHUFF_ENC_EARLY
             {
                 SortChunk nn[SPT];
                 issue_chunk(nn, (cn2 < nch ? cn2 : cn) * kSortStr);
@@ -2074,10 +1887,6 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
                     nxt[u] = nn[u];
                 }
             }
-#else
-#pragma unroll
-            for (int u = 0; u < SPT; ++u) cur[u] = nxt[u];
-#endif
             c = cn;
             continue;
         }
@@ -2087,69 +1896,34 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
 #pragma unroll
             for (int u = 0; u < SPT; ++u) {
                 const uint32_t eb = (uint32_t)__shfl((int)ex, (int)(bin[u] >> 1)), xb = (uint32_t)__shfl((int)x0, (int)(bin[u] >> 1));
-#if HHUFF_ENC_SORTREC
-                const uint32_t tt = t + (uint32_t)u * NT;
-                const uint32_t ln = cb + tt < A.n ? cur[u].e - cur[u].s : 0u;
-                mypos[u] = eb + ((bin[u] & 1u) ? xb : 0u) + rank[u];
-                s_rec[mypos[u]] = (cur[u].s - (cur[0].lo & ~15u)) | (ln << 14);
-#else
                 s_perm[eb + ((bin[u] & 1u) ? xb : 0u) + rank[u]] = (uint16_t)(t + (uint32_t)u * NT);
-#endif
             }
         }
         __syncthreads();
         PROF_MARK(1);
         for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // read by every wave above: cleared for the next chunk
         if (more) issue_span(pv, nxt[0]);     // the next chunk's span: in flight during the encode
-#if HHUFF_ENC_EARLY
         SortChunk nn[SPT];
         issue_chunk(nn, (cn2 < nch ? cn2 : (more ? cn : c)) * kSortStr);
-#endif
         // sorted position t = 64 wave + lane: wave w encodes the w-th length group (SPT = 2: then also the
         // sorted position NS - 1 - t, so the pair's lengths add up to about twice the mean)
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
-#if HHUFF_ENC_SORTREC
-            const uint32_t pj = u == 0 ? t : NS - 1u - t;
-            const uint32_t rj = s_rec[pj];
-            const uint2 sj = make_uint2(rj & 0x3FFFu, rj >> 14);
-            const bool vj = true;  // a string past n has length 0
-#else
             const uint32_t j = s_perm[u == 0 ? t : NS - 1u - t];
             const uint2 sj = s_str[j];
             const bool vj = cb + j < A.n;
-#endif
             const bool act = vj && sj.y != 0 && sj.y <= kMaxStrLen;
             const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U>(s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x, s_enc,
                                                 act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
             // the encoded length goes back to the string's own record (read by its own thread only), so the
             // lengths and statuses are stored in string order, coalesced
-#if HHUFF_ENC_SORTREC
-            s_rec[pj] = act && tb != kFailLen ? (tb + 7) >> 3 : kFailLen;
-#else
             s_str[j].x = act && tb != kFailLen ? (tb + 7) >> 3 : kFailLen;
-#endif
         }
         PROF_MARK(2);
         __syncthreads();
-#if HHUFF_ENC_COPY_BATCH && HHUFF_ENC_COPY_EARLY
-        // the copy-out's LDS reads right after barrier 3 (the stage is final; prepare() writes only past span),
-        // so their latency runs under the next chunk's prepare and this chunk's length stores
-        uint4 cv[NV];
-#pragma unroll
-        for (int jv = 0; jv < NV; ++jv) {
-            const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
-            if (k < span) cv[jv] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(s_out) + k);
-        }
-#endif
         uint32_t olen[SPT];
 #pragma unroll
-#if HHUFF_ENC_SORTREC
-        for (int u = 0; u < SPT; ++u) olen[u] = s_rec[mypos[u]];
-#else
         for (int u = 0; u < SPT; ++u) olen[u] = s_str[t + (uint32_t)u * NT].x;
-#endif
-#if HHUFF_ENC_EARLY
         // the next chunk goes in now, before this chunk's stores: its span loads (in flight since the encode
         // began) are then waited for with no store ahead of them in the memory counter
         if (more) prepare(nxt, cn * kSortStr, span);  // (overwrites this thread's records: olen read above)
@@ -2157,7 +1931,6 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
         // registers with no load pending, not behind this chunk's stores
         land(nn);
         PROF_MARK(5);
-#endif
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
             const uint64_t i = cb + t + (uint32_t)u * NT;
@@ -2167,16 +1940,13 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
         // the stage's MSB-first words, byte-swapped on the way out (each read chunk is zeroed for the next
         // chunk); the chunk's first and last 16-B chunks are deferred (edge_fix_kernel)
         const uint32_t kl = (span - 1u) & ~15u;
-#if HHUFF_ENC_COPY_BATCH
         // every chunk's LDS read first (NV of them), then the stores: one LDS round trip a chunk, not one each
-#if !HHUFF_ENC_COPY_EARLY
         uint4 cv[NV];
 #pragma unroll
         for (int jv = 0; jv < NV; ++jv) {
             const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
             if (k < span) cv[jv] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(s_out) + k);
         }
-#endif
 #pragma unroll
         for (int jv = 0; jv < NV; ++jv) {
             const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
@@ -2184,12 +1954,6 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
             const uint64_t g = (uint64_t)a0 + k;
             uint4* sp = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k);
             uint4 v = cv[jv];
-#else
-        for (uint32_t k = t * 16u; k < span; k += 16u * NT) {
-            const uint64_t g = (uint64_t)a0 + k;
-            uint4* sp = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k);
-            uint4 v = *sp;
-#endif
             const bool full = g >= lo && g + 16 <= hi;
             // (a partial edge chunk stored one byte a lane below is zeroed there, after its bytes are read)
             if (full || A.edges || !HHUFF_EDGE_BYTES) *sp = make_uint4(0u, 0u, 0u, 0u);
@@ -2225,18 +1989,10 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
             PROF_FLUSH(1);
             break;
         }
-#if !HHUFF_ENC_EARLY
-        // the stages are free (the input since the encode, the output but for this thread's chunks above):
-        // the next chunk goes in before this chunk's stores have landed
-        prepare(nxt, cn * kSortStr, span);
-        PROF_MARK(5);
-#endif
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
             cur[u] = nxt[u];
-#if HHUFF_ENC_EARLY
             nxt[u] = nn[u];
-#endif
         }
         c = cn;
     }
@@ -2304,14 +2060,6 @@ __device__ __forceinline__ void pl_clear_spare_edges(EdgeRec* edges, uint64_t nt
         edges[r].m = make_uint4(0u, 0u, 0u, 0u);
 }
 
-#ifndef HHUFF_NB8  // pass 1 of the proportional-lane kernels counts with a byte table of code lengths
-#define HHUFF_NB8 1
-#endif
-#ifndef HHUFF_PL_EARLY
-// 1: the next span committed and the next offsets waited for before the tile's stores (with the clamped,
-// unconditional offset loads: c5 encode 0.331 -> 0.320 ms, c3 0.226 -> 0.222, profiles/r04ac_pl_ab.log)
-#define HHUFF_PL_EARLY 1
-#endif
 template <int WAVES, int STAGE>
 __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32_t K, const uint32_t* __restrict__ kplan,
                                                                uint64_t rec_cap) {
@@ -2378,9 +2126,7 @@ __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32
     if (cur.fits) pf.issue(A.in, A.in_size, cur.a0, cur.span, lane);
     issue(min(t + tstride, ntiles - 1u), ns, ne);  // (unconditional: see issue)
     if (cur.fits) pf.commit(stage, A.in, A.in_size, cur.a0, cur.span, lane);
-#if HHUFF_PL_EARLY
     __asm__ volatile("" : "+v"(ns), "+v"(ne) : : "memory");  // (once: no load pending at the loop head)
-#endif
     for (;;) {
         const uint64_t tn = t + tstride;
         const bool have_next = tn < ntiles;
@@ -2428,11 +2174,7 @@ __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32
             bool sfail = false;
             wave_lds_sync();
             if (__any(multi && big)) {  // pass 1: code bits of every share, then starting bits and totals
-#if HHUFF_NB8
                 const uint32_t b = chunk_code_bits_nb(stage, last, cs, clen, big && multi && clen != 0, sm.nb);
-#else
-                const uint32_t b = chunk_code_bits_v2(stage, last, cs, clen, big && multi && clen != 0, s_enc);
-#endif
                 const uint32_t x = wave_excl_scan(b, lane);
                 const uint32_t xs = (uint32_t)__shfl((int)x, (int)Lj, 64);
                 const uint32_t xe = (uint32_t)__shfl((int)(x + b), (int)(Lj + gj - 1), 64);
@@ -2452,20 +2194,17 @@ __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32
             }
             ol = (uint32_t)__shfl((int)res, (int)L, 64);
             wave_lds_sync();
-#if HHUFF_PL_EARLY
             // the stage is free (pass 2 is done): the next span goes in now, and the offsets of the tile after
             // next are waited for here, before this tile's stores -- a load waited for behind a data-dependent
             // number of stores waits for the stores too (vmcnt counts both, in order)
             if (have_next && nxt.fits) pf.commit(stage, A.in, A.in_size, nxt.a0, nxt.span, lane);
             __asm__ volatile("" : "+v"(ns), "+v"(ne) : : "memory");
-#endif
             // byte-swapped on the way out; the (at most two) 16-B chunks shared with the neighbouring tiles
             // are deferred to edge_fix_kernel, or stored by byte range here (no records: small batches)
             if (A.edges)
                 region_copy_deferred<true>(A.out, cur.a0, obuf, cur.span, cur.lo, cur.hi, lane, A.edges + 2 * t);
             else
                 region_copy<(STAGE + 1023) / 1024, true>(A.out, cur.a0, obuf, cur.span, cur.lo, cur.hi, lane);
-#if HHUFF_PL_EARLY
             // (the prefetch registers stay allocated across the copy: were they reused as its store data, the
             // next tile's loads into them would wait for those stores -- gfx950 orders no store-data reads)
 #pragma unroll
@@ -2473,12 +2212,9 @@ __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32
                 const uint4 q = pf.v[k];
                 __asm__ volatile("" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
             }
-#endif
             wave_lds_sync();
         } else {
-#if HHUFF_PL_EARLY
             __asm__ volatile("" : "+v"(ns), "+v"(ne) : : "memory");  // (as above, on this rare path too)
-#endif
             if (own && len <= kMaxStrLen) {
                 RegSink sink;
                 sink.init(A.out + cur.s);
@@ -2488,13 +2224,7 @@ __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32
         }
         if (own) finish_encode(A, (uint32_t)(cur.i0 + lane), len, ol);
         if (!have_next) break;
-#if HHUFF_PL_EARLY
         if (!cur.fits && nxt.fits) pf.commit(stage, A.in, A.in_size, nxt.a0, nxt.span, lane);
-#else
-        if (nxt.fits) {
-            pf.commit(stage, A.in, A.in_size, nxt.a0, nxt.span, lane);
-        }
-#endif
         cur = nxt;
         t = tn;
     }
@@ -2758,15 +2488,7 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
             wave_lds_sync();
             PROF_MARK(1);
             // pass 1: code bits per share -> starting bit of each share, string totals, verdicts
-#ifdef HHUFF_X_FLAT_NOCOUNT  // ablation (output wrong by design): no counting pass, every share 6 bits a byte
-            const uint32_t b = ok && !rj ? 6u * clen : 0u;
-#else
-#if HHUFF_NB8
             const uint32_t b = chunk_code_bits_nb(stage, last, cs, clen, ok && !rj && clen != 0, sm.nb);
-#else
-            const uint32_t b = chunk_code_bits_v2(stage, last, cs, clen, ok && !rj && clen != 0, s_enc);
-#endif
-#endif
             PROF_MARK(2);
             const uint32_t x = wave_excl_scan(b, lane);
             const uint32_t xs = (uint32_t)__shfl((int)x, (int)Lj, 64);
@@ -2797,12 +2519,10 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
             // the next tile's offsets are waited for here, before this tile's stores (not at the next tile's
             // plan, where the wait would cover the stores too)
             __asm__ volatile("" : "+v"(nxi.s), "+v"(nxi.e), "+v"(nxi.first), "+v"(nxi.raww) : : "memory");
-#ifndef HHUFF_X_FLAT_NOSTORE  // ablation (output wrong by design): no output stores
             if (A.edges)
                 region_copy_deferred<true>(A.out, cur.ob, obuf, cur.ospan, cur.olo, cur.ohi, lane, A.edges + 2 * t);
             else
                 region_copy<1, true>(A.out, cur.ob, obuf, cur.ospan, cur.olo, cur.ohi, lane);
-#endif
             wave_lds_sync();
             PROF_MARK(5);
         } else {
@@ -3083,7 +2803,7 @@ __global__ void literal_fix_kernel(LitArgs A) {
     }
 }
 
-#if HHUFF_AB_VARIANTS
+#if HHUFF_AB_VARIANTS  // A/B builds only (tools/ab.py build; include path tools/ab)
 #include "hhuff_ab_decoders.h"
 #endif
 // ------------------------------------------------------------------------------------------------
@@ -3096,21 +2816,12 @@ __global__ void literal_fix_kernel(LitArgs A) {
 //   encode direct:         4 waves/WG                                      [2 KiB]
 // The variant is picked from the mean bytes per string (in_size / n).
 // ------------------------------------------------------------------------------------------------
-// A/B variants measured and not adopted: the store-wave staged decode, stream2, the
-// register-output stream decode and the in-place sorted encoder -- tools/ab/hhuff_variants.h, in A/B builds only.
-#if HHUFF_AB_VARIANTS
-#include "hhuff_variants.h"
-#endif
-
 // (measured shapes, kept for the record: stream kernel waves / window dwords / output bytes per lane, c3 /
 //  u400 decode ms: 12,12,96: 0.335 / 0.621; 16,8,64: 0.390 / 0.783; 8,16,112: 0.316 / 0.527.  Short-string
 //  encode waves per block, c4 ms: 16: 0.83; 12: 0.93; 20 does not launch at 118 VGPRs.)
 #ifndef HHUFF_ENCO_NS  // length-sorted encode chunks: strings per chunk, stage bytes (64 B a string: 4 per CU)
 #define HHUFF_ENCO_NS 256
 #define HHUFF_ENCO_CH 16384
-#endif
-#ifndef HHUFF_RK_W  // stream decode with register output: waves per block (16 x 6.4 KiB of windows + the LUT)
-#define HHUFF_RK_W 16
 #endif
 #ifndef HHUFF_DECT  // stream decode: waves per block, window dwords, output bytes per lane
 // 8 waves of 20-dword windows (the most the LDS holds beside the window table at these windows): against the
@@ -3121,61 +2832,20 @@ __global__ void literal_fix_kernel(LitArgs A) {
 #define HHUFF_DECT_NW 20
 #define HHUFF_DECT_OUT 144
 #endif
-#ifdef HHUFF_STREAM_RK
-constexpr int kDecTWaves = HHUFF_RK_W;
-#else
+#ifndef HHUFF_DECT_SEG
+#define HHUFF_DECT_SEG 16
+#endif
 constexpr int kDecTWaves = HHUFF_DECT_W;
-#endif
-#ifndef HHUFF_ENC_INPLACE  // 1: the contiguous short-string encoder is encode_inplace_kernel (512 strings, pairs)
-#define HHUFF_ENC_INPLACE 0
-#endif
-#ifndef HHUFF_ENCI_NS  // strings per chunk, stage bytes, strings per thread
-#define HHUFF_ENCI_NS 512
-#define HHUFF_ENCI_CH 28672
-#define HHUFF_ENCI_SPT 2
-#endif
-#if HHUFF_ENC_INPLACE
-constexpr int kEncOStr = HHUFF_ENCI_NS, kEncOThreads = HHUFF_ENCI_NS / HHUFF_ENCI_SPT;
-#else
 constexpr int kEncOStr = HHUFF_ENCO_NS, kEncOThreads = HHUFF_ENCO_NS / HHUFF_ENCO_SPT;
-#endif
 constexpr int kDecSWaves = 16, kEncSWaves = 16;
 #define DEC_S decode_staged_kernel<kDecSWaves, 3072, 4608, false>
-#ifndef HHUFF_DEC_SW  // 1: contiguous short-string decode through decode_staged_sw_kernel (a store wave)
-#define HHUFF_DEC_SW 0
-#endif
-
-#define DEC_SW decode_staged_sw_kernel<3072, 4608, HHUFF_DEC_SW_NSW>
-#ifndef HHUFF_DEC_RUN  // 1: the contiguous layout's stream decode runs decode_run_kernel (runs of HHUFF_RUN_RL strings)
-#define HHUFF_DEC_RUN 0
-#endif
-#ifndef HHUFF_RUN_RL
-#define HHUFF_RUN_RL 4
-#endif
-#define DEC_R decode_run_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT, HHUFF_RUN_RL>
 #define DEC_L decode_staged_kernel<6, 8192, 12928, false>
 #define DEC_SP decode_staged_kernel<kDecSWaves, 3072, 4608, true>
 #define DEC_LP decode_staged_kernel<6, 8192, 12928, true>
 #define DEC_D decode_direct_kernel<4>
-#ifdef HHUFF_STREAM2  // A/B: the stream kernel with prefetched next strings, window in place (HHUFF_DECT_OUT: dwords)
-#define DEC_T decode_stream2_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT>
-#else
-#ifndef HHUFF_DECT_SEG
-#define HHUFF_DECT_SEG 16
-#endif
-#ifdef HHUFF_STREAM_RK  // A/B builds: register output, 16 waves (c3 0.437 / c5 0.687 ms against 0.294 / 0.430:
-                        // the per-symbol register packing costs more than the occupancy gains, r05j_stream_rk_ab)
-#define DEC_T decode_stream_rk_kernel<HHUFF_RK_W, HHUFF_DECT_NW>
-#else
 #define DEC_T decode_stream_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT, HHUFF_DECT_SEG>
-#endif
-#endif
 #define ENC_S encode_staged_kernel<kEncSWaves, 3584, false>
-#if HHUFF_ENC_INPLACE
-#define ENC_O encode_inplace_kernel<HHUFF_ENCI_NS, HHUFF_ENCI_CH, HHUFF_ENCI_SPT>
-#else
 #define ENC_O encode_sorted_kernel<kEncOStr, HHUFF_ENCO_CH, HHUFF_ENCO_SPT>
-#endif
 #define ENC_L encode_staged_kernel<8, 8192, false>
 #define ENC_SP encode_staged_kernel<kEncSWaves, 3584, true>
 #define ENC_LP encode_staged_kernel<8, 8192, true>
@@ -3184,6 +2854,12 @@ constexpr int kDecSWaves = 16, kEncSWaves = 16;
 #define ENC_P encode_pl_kernel<16, kPlStage>
 #define FLAT_P flatten_pl_kernel<16, kPlStage>
 #define FLAT_P_THREADS 1024
+
+// A/B builds only (tools/ab.py build; include path tools/ab): the kernels measured and not adopted, and the
+// definitions above that a build selecting one of them replaces
+#if HHUFF_AB_VARIANTS
+#include "hhuff_variants.h"
+#endif
 
 enum Variant { kDecS, kDecL, kDecD, kEncS, kEncL, kEncD, kFlatD, kEncP, kFlatP, kDecT, kDecSP, kDecLP, kEncSP, kEncLP,
                kEncO, kNumVariants };
@@ -3494,13 +3170,18 @@ int set_decode_prices(int device, const float* in4) {
 #if HHUFF_AB_VARIANTS
 #include "hhuff_ab_launch.h"
 #else
-// The segment decoder and the length-sorted decode chunks are A/B-only builds (tools/ab/hhuff_ab_*.h); here the
-// contiguous-batch decode is always the staged / stream choice, and hhuff_set_decode_kernel takes mode 0 only.
+// The segment decoder, the length-sorted decode chunks, the run decoder and the store-wave decoder are A/B-only
+// builds (tools/ab/hhuff_ab_*.h, hhuff_variants.h); here the contiguous-batch decode is always the staged / stream
+// choice, and hhuff_set_decode_kernel takes mode 0 only.
 int set_decode_kernel(int mode) { return mode == 0 ? 0 : -1; }
 static bool use_seg(uint64_t, uint32_t, const uint32_t*, const uint32_t*) { return false; }
 static hipError_t launch_seg(DecArgs, uint64_t, uint32_t, uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
 static bool sorted_decode_on() { return false; }
 static hipError_t launch_sorted_decode(DecArgs, uint32_t, uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
+static constexpr bool use_run() { return false; }
+static void launch_run(const DecArgs&, int, unsigned long long*, hipStream_t) {}
+static constexpr bool use_sw() { return false; }
+static hipError_t launch_sw(const DecArgs&, int, uint32_t, uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
 #endif
 
 static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint32_t* in_len, uint32_t n, uint8_t* out,
@@ -3510,11 +3191,7 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
     if (in_len == nullptr && out_off == nullptr && sorted_decode_on() &&
         pick_decode(sel_bytes ? sel_bytes : in_size, n) == kDecS)
         return launch_sorted_decode(A, n, out, stream);
-#ifdef HHUFF_MIX_STREAM  // A/B builds: mixed lengths go to the stream kernel alone
-    const int v = pick_decode(sel_bytes ? sel_bytes : in_size, n) == kDecL ? (int)kDecT : pick_decode(sel_bytes ? sel_bytes : in_size, n);
-#else
     const int v = pick_decode(sel_bytes ? sel_bytes : in_size, n);
-#endif
     const int grid = grid_for(v, current_device(), n);
     const bool defer = (v == kDecS || v == kDecL) && in_len == nullptr && out_off == nullptr && defer_edges(n);
     if (v == kDecL) {  // mixed lengths: the device picks staged or stream (see below)
@@ -3539,12 +3216,9 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
         }
         if (e == hipSuccess) {
             A.edges = nullptr;
-#if HHUFF_DEC_RUN
-            if (in_len == nullptr && out_off == nullptr && A.n_dev == nullptr)
-                hipLaunchKernelGGL(DEC_R, dim3(grid_for(kDecT, current_device(), n)), dim3(kDecTWaves * 64), 0, stream,
-                                   A, ctr);
+            if (use_run() && in_len == nullptr && out_off == nullptr && A.n_dev == nullptr)
+                launch_run(A, grid_for(kDecT, current_device(), n), ctr, stream);
             else
-#endif
                 hipLaunchKernelGGL(DEC_T, dim3(grid_for(kDecT, current_device(), n)), dim3(kDecTWaves * 64), 0, stream,
                                    A, ctr);
             e = hipGetLastError();
@@ -3561,11 +3235,9 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
         hipError_t e = pool_alloc((void**)&ctr, sizeof(*ctr), stream);
         if (e == hipSuccess) e = hipMemsetAsync(ctr, 0, sizeof(*ctr), stream);
         if (e == hipSuccess) {
-#if HHUFF_DEC_RUN
-            if (in_len == nullptr && out_off == nullptr && A.n_dev == nullptr)
-                hipLaunchKernelGGL(DEC_R, dim3(grid), dim3(kDecTWaves * 64), 0, stream, A, ctr);
+            if (use_run() && in_len == nullptr && out_off == nullptr && A.n_dev == nullptr)
+                launch_run(A, grid, ctr, stream);
             else
-#endif
                 hipLaunchKernelGGL(DEC_T, dim3(grid), dim3(kDecTWaves * 64), 0, stream, A, ctr);
             e = hipGetLastError();
         }
@@ -3575,12 +3247,7 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
         }
         return e;
     }
-#if HHUFF_DEC_SW
-    if (v == kDecS && defer && A.n_dev == nullptr) {  // the store-wave variant (15 decode waves a block)
-        hipLaunchKernelGGL(DEC_SW, dim3(grid), dim3(1024), 0, stream, A);
-        return finish_deferred(out, A.edges, n, stream);
-    }
-#endif
+    if (use_sw() && v == kDecS && defer && A.n_dev == nullptr) return launch_sw(A, grid, n, out, stream);
     switch (v) {
         case kDecS: hipLaunchKernelGGL(DEC_S, dim3(grid), dim3(kDecSWaves * 64), 0, stream, A); break;
         case kDecL: hipLaunchKernelGGL(DEC_L, dim3(grid), dim3(384), 0, stream, A); break;
@@ -3596,17 +3263,11 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
 // lane would take the whole string's bits one after another).  Elsewhere the list
 // would cost a memset and a launch on every call for strings that are almost never there, and a rare long
 // string is decoded by one lane.
-#ifndef HHUFF_SPLIT
-#define HHUFF_SPLIT 1  // 0: no list (A/B builds: every long string decoded by one lane)
-#endif
 #ifndef HHUFF_SPLIT_WAVES
 #define HHUFF_SPLIT_WAVES 4
 #endif
 #ifndef HHUFF_BIG_GRID  // most blocks of the block-list launch
 #define HHUFF_BIG_GRID 128u
-#endif
-#ifndef HHUFF_SPLIT_BIG  // 0: no block list (every listed string on one wave)
-#define HHUFF_SPLIT_BIG 1
 #endif
 constexpr int kSplitWaves = HHUFF_SPLIT_WAVES;  // one-wave list: 4-wave blocks (16 measured 8 % slower)
 constexpr int kSplitBlockWaves = 16;             // block list: 1024 segments per string
@@ -3619,13 +3280,13 @@ hipError_t launch_decode(const uint8_t* in, uint64_t in_size, const uint32_t* in
     DecArgs A{in, in_size, in_off, in_len, n, is_name_bits, out, out_off, out_len, status, nullptr, nullptr, nullptr, nullptr, nullptr};
     const uint64_t bytes = sel_bytes ? sel_bytes : in_size;
     const uint32_t smin = n <= 16u ? kSplitMinFew : kSplitMin;
-    const bool split = HHUFF_SPLIT && bytes >= smin && (bytes / n >= 128u || n <= 16u);
+    const bool split = bytes >= smin && (bytes / n >= 128u || n <= 16u);
     uint32_t* sp = nullptr;
     if (split) {
         A.split_min = smin;
         A.split_cap = (uint32_t)std::min<uint64_t>(n, bytes / smin + 1);
         A.big_min = n <= 16u ? kSplitBigFew : kSplitBig;
-        A.big_cap = HHUFF_SPLIT_BIG ? (uint32_t)std::min<uint64_t>(n, bytes / A.big_min) : 0u;
+        A.big_cap = (uint32_t)std::min<uint64_t>(n, bytes / A.big_min);
         hipError_t e = pool_alloc((void**)&sp, 4ull * (2 + A.split_cap + A.big_cap), stream);
         if (e == hipSuccess) e = hipMemsetAsync(sp, 0, 8, stream);
         if (e != hipSuccess) return e;
@@ -3703,9 +3364,7 @@ hipError_t launch_encode(const uint8_t* in, uint64_t in_size, const uint32_t* in
         return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipSuccess;
     }
     int v = pick_encode(in_size, n);
-#ifndef HHUFF_ENC_TILES  // contiguous layout: length-sorted chunks (A/B builds -DHHUFF_ENC_TILES: 64-string tiles)
     if (v == kEncS && in_len == nullptr && out_off == nullptr) v = kEncO;
-#endif
     const int grid = grid_for(v, current_device(), n);
     const bool defer = v != kEncD && in_len == nullptr && out_off == nullptr && defer_edges(n);
     if (defer) {

@@ -2,7 +2,8 @@
 """In-process A/B timing of libhhuff builds (MI355X methodology rule: interleaved rounds, one process).
 
     python tools/ab.py build NAME -DFLAG ...     # hipcc the library into build/ab/libhhuff_NAME.so
-                                                  # (-DHHUFF_AB_VARIANTS=1: with the tools/ab variant kernels)
+                                                  # (-DHHUFF_AB_VARIANTS=1, or a flag selecting one of them:
+                                                  #  with the tools/ab variant kernels)
     python tools/ab.py run NAME1 NAME2 ...        # time c4 encode + decode for each build, interleaved
 """
 import ctypes
@@ -14,6 +15,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 ABDIR = os.path.join(ROOT, "build", "ab")
+# flags that select a variant kernel of tools/ab (hhuff_variants.h, hhuff_ab_launch.h): they imply HHUFF_AB_VARIANTS
+SELECTING = ("HHUFF_STREAM_RK", "HHUFF_STREAM2", "HHUFF_ENC_INPLACE", "HHUFF_DEC_SW", "HHUFF_DEC_RUN")
 
 
 def build(name, flags):
@@ -22,6 +25,9 @@ def build(name, flags):
     os.makedirs(ABDIR, exist_ok=True)
     out = os.path.join(ABDIR, "libhhuff_%s.so" % name)
     # tools/ab holds the variant kernels that are not in libhhuff.so (-DHHUFF_AB_VARIANTS=1 or a flag selecting one)
+    names = [f[2:].split("=")[0] for f in flags if f.startswith("-D")]
+    if "HHUFF_AB_VARIANTS" not in names and any(nm in SELECTING for nm in names):
+        flags = flags + ["-DHHUFF_AB_VARIANTS=1"]
     cmd = ["/opt/rocm/bin/hipcc", "-shared"] + hb.HIPCC_FLAGS + flags + ["-I" + os.path.join(ROOT, "include"), "-I" + hb.CSRC,
                                                                          "-I" + os.path.join(ROOT, "tools", "ab")] + \
         hb.sources() + ["-o", out]
@@ -137,7 +143,7 @@ def run(names, cfg="c4", rounds=5, steps=10):
                 chk = chk + (int(f_len.to(torch.int64).sum().item()), content_sum(f_out, f_pos))
             if ref is None:
                 ref = chk
-            assert chk == ref or nm.startswith("x_"), (nm, chk, ref)  # x_*: ablation builds, output not checked
+            assert chk == ref, (nm, chk, ref)
     # profile builds (-DHHUFF_PROFILE): per-phase shader cycles of one launch of each kernel
     phases = ["plan+issue", "steps", "verdicts/bswap", "commit", "out copy", "len/status", "direct", "plan next"]
     for nm in names:

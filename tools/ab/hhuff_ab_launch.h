@@ -95,3 +95,33 @@ static hipError_t launch_sorted_decode(DecArgs A, uint32_t n, uint8_t* out, hipS
     hipLaunchKernelGGL(decode_sorted_kernel<HHUFF_DS_CH>, dim3(grid), dim3(1024), 0, stream, A);
     return finish_deferred(out, A.edges, n, stream, nullptr, 2ull * nch);
 }
+
+// Run decode (decode_run_kernel, -DHHUFF_DEC_RUN=1): the contiguous layout's stream decode in runs of HHUFF_RUN_RL
+// strings; other layouts keep the stream kernel (launch_decode_kernels has the condition).
+#if HHUFF_DEC_RUN
+#ifndef HHUFF_RUN_RL
+#define HHUFF_RUN_RL 4
+#endif
+#define DEC_R decode_run_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT, HHUFF_RUN_RL>
+static constexpr bool use_run() { return true; }
+static void launch_run(const DecArgs& A, int grid, unsigned long long* ctr, hipStream_t stream) {
+    hipLaunchKernelGGL(DEC_R, dim3(grid), dim3(kDecTWaves * 64), 0, stream, A, ctr);
+}
+#else
+static constexpr bool use_run() { return false; }
+static void launch_run(const DecArgs&, int, unsigned long long*, hipStream_t) {}
+#endif
+
+// Store-wave staged decode (decode_staged_sw_kernel, -DHHUFF_DEC_SW=1: 15 decode waves a block and a store wave) for
+// the contiguous short-string batches whose edges are deferred.
+#if HHUFF_DEC_SW
+#define DEC_SW decode_staged_sw_kernel<3072, 4608, HHUFF_DEC_SW_NSW>
+static constexpr bool use_sw() { return true; }
+static hipError_t launch_sw(const DecArgs& A, int grid, uint32_t n, uint8_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(DEC_SW, dim3(grid), dim3(1024), 0, stream, A);
+    return finish_deferred(out, A.edges, n, stream);
+}
+#else
+static constexpr bool use_sw() { return false; }
+static hipError_t launch_sw(const DecArgs&, int, uint32_t, uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
+#endif

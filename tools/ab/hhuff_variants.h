@@ -1,7 +1,10 @@
-// hhuff_variants.h -- kernel variants kept for A/B builds (included by hhuff_kernels.hip after every helper
-// they use).  Each was built to parity and measured against the default kernel (DESIGN.md (e), round 5;
-// profiles/r05*): none is instantiated unless its build flag is set (HHUFF_DEC_SW, HHUFF_STREAM2,
-// HHUFF_STREAM_RK, HHUFF_ENC_INPLACE, HHUFF_DEC_RUN).
+// hhuff_variants.h -- kernel variants kept for A/B builds (included by hhuff_kernels.hip in HHUFF_AB_VARIANTS
+// builds, after every helper they use and after the product's launch configuration).  Each was built to parity
+// and measured against the default kernel (profiles/r05*): none is instantiated unless
+// its build flag is set (HHUFF_DEC_SW, HHUFF_STREAM2, HHUFF_STREAM_RK, HHUFF_ENC_INPLACE, HHUFF_DEC_RUN;
+// tools/ab.py build adds -DHHUFF_AB_VARIANTS=1 to any of them).  The selection is at the end of this file
+// (the stream and sorted-encode kernels) and in hhuff_ab_launch.h (the run and store-wave decoders): the
+// product source names neither these kernels nor their flags.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
@@ -893,11 +896,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream2_kernel(DecArgs A, u
             }();
             uint8_t* gchunk = A.out + ((dst + ocnt) & ~15ull);
             const uint32_t hs = (uint32_t)(dst & 15u);  // head chunk: the string's bytes start here
-#ifdef HHUFF_X_NOSTORE  // ablation builds (output wrong by design): no global stores at all
-            if (false) {
-#else
             if (!done || ok) {  // a failed string's output is unspecified: skip its last stores
-#endif
                 const uint32_t nfull = nb >> 4;
                 for (uint32_t k = 0; k < nfull; ++k) {
                     const uint4 v = lds_ld16(obuf + 16u * k);
@@ -918,10 +917,8 @@ __global__ __launch_bounds__(WAVES * 64) void decode_stream2_kernel(DecArgs A, u
             ocnt += made;
             P += (uint32_t)(pm - pm0);
             if (done) {
-#ifndef HHUFF_X_NOSTORE
                 A.out_len[i] = ok ? ocnt : kFailLen;
                 A.status[i] = ok ? soft_bits(is_name, ocnt, flags, first, lastb) : kStatusFail;
-#endif
                 busy = false;
             }
         }
@@ -1694,3 +1691,36 @@ __global__ __launch_bounds__(WAVES * 64) void decode_run_kernel(DecArgs A, unsig
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Selection: a flag replaces the product's launch configuration (hhuff_kernels.hip, just above this file's
+// include point) with a variant's.  The product's launch code goes through DEC_T / kDecTWaves and ENC_O /
+// kEncOStr / kEncOThreads only.
+// ------------------------------------------------------------------------------------------------
+#ifdef HHUFF_STREAM2  // the stream kernel with prefetched next strings, window in place (HHUFF_DECT_OUT: dwords, odd)
+#undef DEC_T
+#define DEC_T decode_stream2_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT>
+#elif defined(HHUFF_STREAM_RK)
+// register output, 16 waves (c3 0.437 / c5 0.687 ms against 0.294 / 0.430: the per-symbol register packing costs
+// more than the occupancy gains, r05j_stream_rk_ab)
+#ifndef HHUFF_RK_W  // waves per block (16 x 6.4 KiB of windows + the LUT)
+#define HHUFF_RK_W 16
+#endif
+constexpr int kRkWaves = HHUFF_RK_W;
+static_assert(kDecTWaves == HHUFF_DECT_W, "the product's constant, replaced from here on");
+#define kDecTWaves kRkWaves
+#undef DEC_T
+#define DEC_T decode_stream_rk_kernel<HHUFF_RK_W, HHUFF_DECT_NW>
+#endif
+#if HHUFF_ENC_INPLACE  // the contiguous short-string encoder is encode_inplace_kernel (512 strings, pairs)
+#ifndef HHUFF_ENCI_NS  // strings per chunk, stage bytes, strings per thread
+#define HHUFF_ENCI_NS 512
+#define HHUFF_ENCI_CH 28672
+#define HHUFF_ENCI_SPT 2
+#endif
+constexpr int kEncIStr = HHUFF_ENCI_NS, kEncIThreads = HHUFF_ENCI_NS / HHUFF_ENCI_SPT;
+static_assert(kEncOStr == HHUFF_ENCO_NS && kEncOThreads > 0, "the product's constants, replaced from here on");
+#define kEncOStr kEncIStr
+#define kEncOThreads kEncIThreads
+#undef ENC_O
+#define ENC_O encode_inplace_kernel<HHUFF_ENCI_NS, HHUFF_ENCI_CH, HHUFF_ENCI_SPT>
+#endif

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU replay of encode_inplace_lane / encode_redo (hhuff_kernels.hip, HHUFF_ENC_INPLACE): one chunk's stage as
+"""CPU replay of encode_inplace_lane / encode_redo (tools/ab/hhuff_variants.h, HHUFF_ENC_INPLACE): one chunk's stage as
 32-bit words, the strings' lanes run in lock step (one word step of every lane, in a seeded lane order, per
 round), checked against a plain encoder (hpack.c:774-804).  Test infrastructure for the kernel's algorithm."""
 import os
