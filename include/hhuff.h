@@ -77,9 +77,12 @@ int hhuff_service_stamps(uint32_t *out4);
  * ------------------------------------------------------------------------------------------- */
 
 /* Batched h2o_hpack_decode_huffman (hpack.c:117-156; callers hpack.c:241, qpack.c:228/370/579).
- *   out       decoded string i at out + (out_off ? out_off[i] : floor(8 * in_off[i] / 5)); the region
- *             must hold floor(8 * len_i / 5) bytes (the implicit layout is valid whenever the input
- *             strings do not overlap).  Bytes of the region past out_len[i] are unspecified.
+ *   out       decoded string i at out + (out_off ? out_off[i] : floor(8 * in_off[i] / 5)).  With out_off the
+ *             region must hold floor(8 * len_i / 5) bytes.  Without it the region is the string's slot, from
+ *             floor(8 * in_off[i] / 5) up to floor(8 * (in_off[i] + len_i) / 5) -- where the slot of the next
+ *             input byte begins: floor(8 * len_i / 5) bytes or one more, so `out` holds floor(8 * in_size / 5)
+ *             bytes and the layout is valid whenever the input strings do not overlap.  Bytes of the region
+ *             past out_len[i] are unspecified; no byte outside the regions is written.
  *   out_len   u32[n]: decoded length, or HHUFF_FAIL_LEN
  *   status    u8[n]:  soft-error bits on success, HHUFF_STATUS_FAIL on a hard error */
 int hhuff_decode_batch(const uint8_t *in, uint64_t in_size, const uint32_t *in_off, const uint32_t *in_len, uint32_t n,
@@ -132,7 +135,8 @@ int hhuff_flatten_batch(const uint8_t *in, uint64_t in_size, const uint32_t *in_
 /* ---------------------------------------------------------------------------------------------
  * (3) batch API, host arrays: pinned staging + H2D, kernels, D2H on an internal stream of `device`.
  *     Synchronous.  Same array contract; `out` is a host buffer sized for the implicit layout
- *     (decode: floor(8 * in_size / 5) bytes, encode: in_size bytes) when out_off is NULL.
+ *     (decode: floor(8 * in_size / 5) bytes, encode: in_size bytes) when out_off is NULL.  The results are
+ *     copied back in one piece: bytes of `out` that belong to no string's region are unspecified.
  * ------------------------------------------------------------------------------------------- */
 int hhuff_decode_batch_host(const uint8_t *in, uint64_t in_size, const uint32_t *in_off, const uint32_t *in_len,
                             uint32_t n, const uint32_t *is_name_bits, uint8_t *out, uint64_t out_size,
