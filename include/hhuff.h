@@ -188,6 +188,10 @@ int hhuff_decode_literals(const uint8_t *in, uint64_t in_size, const uint32_t *l
  *      raw name), HHUFF_BLK_ARENA (a string does not fit the block's arena slice: a Huffman literal needs
  *      floor(8 len / 5) bytes free, a raw one len, an indexed one its size), or HHUFF_BLK_SKIPPED (an
  *      earlier block of the connection failed: h2o drops the connection).  Fields before the error stand.
+ *      A string's room is checked in decode_string's order (hpack.c:223-261): a Huffman literal's before its
+ *      decoder runs (a literal that would not decode is HHUFF_BLK_ARENA in a slice too small for it), a raw
+ *      name's after its validation (an upper-case raw name is PROTOCOL whatever the slice).  A block may
+ *      write any byte of its own slice; it writes none outside, and an empty block writes nothing.
  *      Device arrays; scratch = device memory of hhuff_hpack_scratch_size(nconn, table_size) bytes (the
  *      dynamic tables, 16-byte aligned), kept by the caller between calls for HHUFF_BLK_CONTINUE;
  *      asynchronous on `stream`.  The call also takes a stream-ordered workspace from the library's device

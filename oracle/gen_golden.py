@@ -31,6 +31,8 @@ Fixture sets (numpy .npz, arrays only, no pickles):
                    h2o_hpack_flatten_request, with one encoder table per connection (oracle/ref_hpenc.c), the
                    restatement checked against them as they are written; sessions with invalid arguments and
                    short output regions
+  block_edges.npz  the hand-built table, arena and literal edge corpora (tests/blocks_corpora.py, qpack_corpora.py)
+                   through the reference's HPACK and QPACK decoders: statuses, fields, records
   qpenc.npz        HTTP/3 response HEADERS frames (f4, QPACK encode half): synthetic responses (datagram flow ids,
                    statuses outside the static table, dont_compress, names added without their token) flattened by
                    the real h2o_qpack_flatten_response as h2o's HTTP/3 server calls it (ref_shim.c ref_qpe_step),
@@ -941,7 +943,26 @@ def qpenc_set():
     return out
 
 
+def block_edges_set():
+    """tests/golden/block_edges.npz: the hand-built edge corpora of tests/blocks_corpora.py and tests/qpack_corpora.py
+    (the long-literal corpora's cases of 4 KiB and 64 KiB literals and the 8 MiB corpus left out) through the
+    reference: statuses, the decoded fields' bytes and lengths, one soft-error code and the header-list flag per
+    field, request / response records.
+    Arena slices are roomy here: h2o has no arena (tests/blocks_corpora.py roomy())."""
+    sys.path.insert(1, os.path.join(ROOT, "tests"))
+    import blocks_corpora as BC
+    import qpack_corpora as QC
+
+    out = BC.reference_results(O.ref())
+    out.update(QC.reference_results(O.ref()))
+    print("block_edges: %d arrays, %d bytes of fields" % (len(out), sum(v.nbytes for v in out.values())))
+    return out
+
+
 def main():
+    if "--only-block-edges" in sys.argv:
+        np.savez_compressed(os.path.join(GOLDEN, "block_edges.npz"), **block_edges_set())
+        return
     if "--only-resp" in sys.argv:
         np.savez_compressed(os.path.join(GOLDEN, "resp.npz"), **resp_set())
         return
@@ -985,6 +1006,7 @@ def main():
     sets["hpenc"] = hpenc_set()
     sets["qpenc"] = qpenc_set()
     sets["resp"] = resp_set()
+    sets["block_edges"] = block_edges_set()
     for name, arrays in sets.items():
         path = os.path.join(GOLDEN, name + ".npz")
         np.savez_compressed(path, **arrays)
