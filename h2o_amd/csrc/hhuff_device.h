@@ -521,7 +521,7 @@ __device__ __forceinline__ DecResult decode_staged_lane_v7(const uint32_t* stage
     // trash byte; a lane whose next code can never fit is parked by pushing c positive. ----
     int32_t c = parked ? 0x40000000 : pm - end;
     int32_t prog = 0;
-    auto step = [&](bool longchk) {
+    auto step = [&]() {  // (every tail step takes the long-code detour, so a step without progress is final)
         const uint32_t w = __builtin_amdgcn_alignbit(x0, x1, ~(uint32_t)pm);
         const uint32_t e = T.lut[w >> (32 - HHUFF_LUT_BITS)];
         const int32_t L1 = lut_l1(e), L12 = lut_l12(e);
@@ -550,7 +550,7 @@ __device__ __forceinline__ DecResult decode_staged_lane_v7(const uint32_t* stage
         }
         const bool lact = (s1 & (int32_t)e) < 0;
         uint32_t consl = 0;
-        if (longchk && __builtin_amdgcn_ballot_w64(lact) != 0) {
+        if (__builtin_amdgcn_ballot_w64(lact) != 0) {
             if (lact) {
                 const uint32_t k = min((uint32_t)__builtin_clz(~w | 1u), 30u);
                 const uint32_t ki = T.kinfo[k];
@@ -572,12 +572,19 @@ __device__ __forceinline__ DecResult decode_staged_lane_v7(const uint32_t* stage
         advance(cons);
         prog = cons;
     };
-    step(true);
-    for (;;) {  // the vote follows a long-code step: a lane with no progress there is finished
-        step(false);
-        step(true);
-        if (!__any(prog != 0)) break;
-    }
+    // The vote is taken ahead of a step, on the bits left: a lane can take another symbol only if it has at
+    // least the shortest code's 5 bits and they are not 5..7 ones (the accept rule's padding below; no code
+    // is all ones short of EOS's 30).  Parked lanes have c > 0, so R < 0.  A lane that took nothing in the
+    // last step never will (a code cut short by the string's end).  26 bits are at most five symbols: two
+    // steps finish a typical tile, where a vote on progress needed a third in which nothing moves.
+    auto live = [&]() {
+        const int32_t R = ~c;
+        const uint32_t w = __builtin_amdgcn_alignbit(x0, x1, ~(uint32_t)pm);
+        const bool pad = R <= 7 && (w | (0xFFFFFFFFu >> ((uint32_t)R & 31u))) == 0xFFFFFFFFu;
+        return prog != 0 && R >= 5 && !pad;
+    };
+    step();
+    while (__any(live())) step();
     DecResult r;
     const uint32_t R = ~(uint32_t)c;
     const uint32_t w = __builtin_amdgcn_alignbit(x0, x1, ~(uint32_t)pm);

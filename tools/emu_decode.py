@@ -2,8 +2,9 @@
 """Scalar emulation of the GPU decode step functions (one lane), for debugging kernel logic on the CPU.
 
 Emulates decode_staged_lane_v7 (bulk + tail) over a big-endian dword view of the input, with the
-lock-step details that matter for one lane: the long-code detour runs only on every other step
-(HHUFF_DEC_LONG2) and the step parity restarts at the tail.  Bytes past the buffer read as `fill`.
+lock-step details that matter for one lane: in the bulk loop the long-code detour runs only on every other
+step; in the tail it runs on every step, and a lane steps on while any lane of its wave can still take a
+symbol (`extra` further steps here: they must change nothing).  Bytes past the buffer read as `fill`.
 
     python tools/emu_decode.py [cfg] [n] [seed]    # compares against the CPU oracle (pairs layout)
 """
@@ -60,7 +61,7 @@ def long_entry(T, w):
     return ones[idx]
 
 
-def decode_v7(T, data, start, length, fill=0):
+def decode_v7(T, data, start, length, fill=0, extra=0):
     """-> (ok, out bytes, flags) following decode_staged_lane_v7"""
     lut = T[0]
     ln = Lane(T, data, start, length, fill)
@@ -109,12 +110,21 @@ def decode_v7(T, data, start, length, fill=0):
                 parked = True
                 lim = -(1 << 31)
         pm += cons
-    # tail: step(true), then pairs (false, true) until no lane progressed on a long-code step
+    # tail: a step, then steps while the lane can still take a symbol (it moved in the last step, has 5 bits
+    # or more left and they are not 5..7 ones of padding)
     c = 0x40000000 if parked else pm - end
-    step_i = 0
+    tail_steps = 0
     while True:
-        longchk = step_i % 2 == 0
-        step_i += 1
+        if tail_steps:  # (the first step runs unconditionally)
+            R = s32(~c)
+            q = pm >> 5
+            w = alignbit(ln.word(q), ln.word(q + 1), ~pm)
+            pad = R <= 7 and (w | (M32 >> (R & 31))) == M32
+            if not (cons != 0 and R >= 5 and not pad):
+                if extra == 0:
+                    break
+                extra -= 1
+        tail_steps += 1
         q = pm >> 5
         w = alignbit(ln.word(q), ln.word(q + 1), ~pm)
         e = lut[w >> 19]
@@ -142,7 +152,7 @@ def decode_v7(T, data, start, length, fill=0):
             flags |= eb & (3 << 26)
         cons += L12b if m2b else (L1b if m1b else 0)
         lact = (e >> 31) and L1 + c < 0
-        if longchk and lact:
+        if lact:
             le = long_entry(T, w)
             L = (le >> 9) & 31
             fits = L + c < 0
@@ -157,10 +167,6 @@ def decode_v7(T, data, start, length, fill=0):
                 c = 0x40000000
         c += cons
         pm += cons
-        if cons == 0 and longchk:
-            break
-        if cons == 0 and not lact:
-            break
     R = (~c) & M32
     q = pm >> 5
     w = alignbit(ln.word(q), ln.word(q + 1), ~pm)
@@ -190,6 +196,8 @@ def main():
         ref, _ = o.decode(src)
         ok, out, _ = decode_v7(T, enc, s, ln)
         got = out if ok else None
+        if (ok, out) != decode_v7(T, enc, s, ln, extra=2)[:2]:  # steps taken for the wave's other lanes
+            got = b"further tail steps changed the result"
         if got != ref:
             bad += 1
             if bad <= 5:
