@@ -117,6 +117,13 @@ def lib():
         L.hhuff_qpack_flatten_responses.restype = ctypes.c_int
         L.hhuff_qpack_flatten_responses.argtypes = ([_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
                                                      ctypes.c_uint32, ctypes.c_uint32] + [_vp] * 6)
+        L.hhuff_qpack_enc_scratch_size.restype = ctypes.c_uint64
+        L.hhuff_qpack_enc_scratch_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        L.hhuff_qpack_flatten_sessions.restype = ctypes.c_int
+        L.hhuff_qpack_flatten_sessions.argtypes = ([_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                    ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64,
+                                                    ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32] + [_vp] * 12 +
+                                                   [ctypes.c_uint64, ctypes.c_uint, _vp])
         L.hhuff_version.restype = ctypes.c_char_p
         L.hhuff_last_error_string.restype = ctypes.c_char_p
         L.hhuff_grid_size.restype = ctypes.c_int
@@ -162,7 +169,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_encode_batch_host_pipelined", "hhuff_version", "hhuff_last_error_string", "hhuff_per_string_calls",
             "hhuff_grid_size", "hhuff_decode_prices", "hhuff_calibrate_decode_prices", "hhuff_set_decode_prices",
             "hhuff_pool_trim", "hhuff_service_stamps", "hhuff_hpack_enc_scratch_size",
-            "hhuff_hpack_flatten_responses", "hhuff_qpack_flatten_responses", "hhuff_set_decode_kernel",
+            "hhuff_hpack_flatten_responses", "hhuff_qpack_flatten_responses", "hhuff_qpack_enc_scratch_size",
+            "hhuff_qpack_flatten_sessions", "hhuff_set_decode_kernel",
             "hhuff_decode_batch_host_packed", "hhuff_encode_batch_host_packed", "hhuff_set_edge_defer_min",
             "hhuff_decode_batch_multi", "hhuff_encode_batch_multi", "hhuff_shard_bounds")
 
@@ -521,6 +529,67 @@ def qpack_flatten_responses(data, hdr, res, nres, out_off, server_off=0, server_
         _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), nres, server_off, server_len, _dp(out),
         _dp(out_off), _dp(r["out_len"]), _dp(r["header_len"]), _dp(r["rstatus"]), _stream(stream)),
         "hhuff_qpack_flatten_responses")
+    return r
+
+
+# include/hhuff.h (2g'): QPACK encoder sessions
+HDR_LIKELY_TO_REPEAT = 4
+QRES_NO_ENCODER_STREAM = 32
+QENC_CONTINUE, QENC_SET_CAPACITY = 1, 2
+QPK_DECODER_STREAM = 0x30202
+QPK_DECOMPRESSION_FAILED = 0x30200
+QPK_SKIPPED, QPK_BLOCKED = -301, -302
+
+
+def qpack_session_response_bound(name_value_bytes, nhdr, server_len, dfid_len):
+    """include/hhuff.h hhuff_qpack_session_response_bound (numpy arrays or ints)"""
+    return qpack_response_bound(name_value_bytes, nhdr, server_len, dfid_len) + 8
+
+
+def qpack_enc_scratch_size(nconn, header_table_size=4096, max_inflight=64):
+    """include/hhuff.h hhuff_qpack_enc_scratch_size"""
+    return int(lib().hhuff_qpack_enc_scratch_size(nconn, header_table_size, max_inflight))
+
+
+def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off, dec_off=None, dec_len=None,
+                           header_table_size=4096, max_blocked=100, max_inflight=64, server_off=0, server_len=0,
+                           enc_out_off=None, in_size=None, out=None, enc_out=None, scratch=None, cont=False,
+                           set_capacity=False, stream=None):
+    """One step of many QPACK encoder sessions (include/hhuff.h hhuff_qpack_flatten_sessions) on device tensors:
+    hdr = uint8 tensor of HPE_HEADER_DTYPE records, res = uint8 tensor of QPE_RESPONSE_DTYPE records, conn_first
+    int32 (u32 bits) [nconn + 1], stream_id int64 per response, out_off int64 [nres + 1], dec_off / dec_len int32
+    per connection (the decoder streams in `data`; None = none), enc_out_off int64 [nconn + 1] (None:
+    header_table_size + 4 bytes per connection).  nres = conn_first[-1] as a host int.  Returns a dict of device
+    tensors: out, out_len, header_len, rstatus, rflags (per response), enc_out, enc_out_off, enc_out_len,
+    dec_status, dec_consumed (per connection) and the scratch holding the sessions (pass it back with cont=True
+    for the connections' next step)."""
+    import torch
+
+    dev = data.device
+    in_size = data.numel() if in_size is None else in_size
+    nconn = conn_first.numel() - 1
+    nhdr = hdr.numel() // HPE_HEADER_DTYPE.itemsize
+    if enc_out_off is None:
+        enc_out_off = torch.arange(nconn + 1, dtype=torch.int64, device=dev) * ((header_table_size + 4 + 15) // 16 * 16)
+    if out is None:
+        out = torch.empty(max(1, int(out_off[-1].item())), dtype=torch.uint8, device=dev)
+    if enc_out is None:
+        enc_out = torch.empty(max(1, int(enc_out_off[-1].item())), dtype=torch.uint8, device=dev)
+    i32 = lambda n: torch.empty(max(1, n), dtype=torch.int32, device=dev)  # noqa: E731
+    r = dict(out=out, out_len=i32(nres), header_len=i32(nres), rstatus=i32(nres),
+             rflags=torch.empty(max(1, nres), dtype=torch.uint8, device=dev), enc_out=enc_out, enc_out_off=enc_out_off,
+             enc_out_len=i32(nconn), dec_status=i32(nconn), dec_consumed=i32(nconn))
+    ss = qpack_enc_scratch_size(nconn, header_table_size, max_inflight)
+    if scratch is None:
+        scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
+    flags = (QENC_CONTINUE if cont else 0) | (QENC_SET_CAPACITY if set_capacity else 0)
+    _check(lib().hhuff_qpack_flatten_sessions(
+        _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), _dp(conn_first), nconn, nres, _dp(stream_id),
+        _dp(dec_off), _dp(dec_len), header_table_size, max_blocked, max_inflight, server_off, server_len, _dp(out),
+        _dp(out_off), _dp(r["out_len"]), _dp(r["header_len"]), _dp(r["rstatus"]), _dp(r["rflags"]), _dp(enc_out),
+        _dp(enc_out_off), _dp(r["enc_out_len"]), _dp(r["dec_status"]), _dp(r["dec_consumed"]), _dp(scratch),
+        scratch.numel(), flags, _stream(stream)), "hhuff_qpack_flatten_sessions")
+    r["scratch"] = scratch
     return r
 
 

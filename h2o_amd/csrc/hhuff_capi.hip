@@ -301,6 +301,43 @@ HHUFF_API int hhuff_qpack_flatten_responses(const uint8_t* in, uint64_t in_size,
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack flatten launch");
 }
 
+HHUFF_API uint64_t hhuff_qpack_enc_scratch_size(uint32_t nconn, uint32_t header_table_size, uint32_t max_inflight) {
+    return (uint64_t)nconn * hhuff::qpenc_conn_scratch(header_table_size, max_inflight);
+}
+
+HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr, uint32_t nhdr,
+                                           const hhuff_qpack_response_t* res, const uint32_t* conn_first, uint32_t nconn,
+                                           uint32_t nres, const uint64_t* stream_id, const uint32_t* dec_off,
+                                           const uint32_t* dec_len, uint32_t header_table_size, uint64_t max_blocked,
+                                           uint32_t max_inflight, uint32_t server_off, uint32_t server_len, uint8_t* out,
+                                           const uint64_t* out_off, uint32_t* out_len, uint32_t* header_len,
+                                           int32_t* rstatus, uint8_t* rflags, uint8_t* enc_out, const uint64_t* enc_out_off,
+                                           uint32_t* enc_out_len, int32_t* dec_status, uint32_t* dec_consumed, void* scratch,
+                                           uint64_t scratch_size, unsigned flags, void* stream) {
+    if (header_table_size > 65536u) {
+        arg_fail("header_table_size must not exceed 65536");
+        return HHUFF_RES_EINVAL;
+    }
+    if (nconn == 0) return HHUFF_OK;
+    if (!conn_first || !scratch || !enc_out || !enc_out_off || !enc_out_len || !dec_status || !dec_consumed ||
+        (nres && (!res || !stream_id || !out || !out_off || !out_len || !header_len || !rstatus || !rflags)) ||
+        (nhdr && !hdr) || ((nhdr || dec_off || server_len) && !in) || ((dec_off == nullptr) != (dec_len == nullptr)))
+        return arg_fail("NULL array");
+    if (in_size >= (1ull << 32)) return arg_fail("in_size must stay below 2^32 (u32 offsets)");
+    if (scratch_size < hhuff_qpack_enc_scratch_size(nconn, header_table_size, max_inflight))
+        return arg_fail("scratch smaller than hhuff_qpack_enc_scratch_size");
+    if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
+    if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)hdr & 3u) != 0 || ((uintptr_t)out_off & 7u) != 0 ||
+        ((uintptr_t)enc_out_off & 7u) != 0 || ((uintptr_t)stream_id & 7u) != 0)
+        return arg_fail("misaligned hdr / res / out_off / enc_out_off / stream_id");
+    const hhuff::QseCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, stream_id, dec_off, dec_len,
+                              header_table_size, max_blocked, max_inflight, server_off, server_len, out, out_off, out_len,
+                              header_len, rstatus, rflags, enc_out, enc_out_off, enc_out_len, dec_status, dec_consumed,
+                              (uint8_t*)scratch, flags};
+    hipError_t e = hhuff::launch_qpack_sessions(call, (hipStream_t)stream);
+    return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack sessions launch");
+}
+
 HHUFF_API uint64_t hhuff_qpack_scratch_size(uint32_t nconn, uint32_t header_table_size) {
     return (uint64_t)nconn * hhuff::qpack_conn_scratch(header_table_size);
 }

@@ -107,6 +107,38 @@ hipError_t launch_qpack_flatten(const uint8_t* in, uint64_t in_size, const hhuff
                                 uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint32_t* header_len,
                                 int32_t* rstatus, hipStream_t stream);
 
+// HTTP/3 encoder sessions (hhuff_hpenc.hip): include/hhuff.h hhuff_qpack_flatten_sessions; scratch = nconn x
+// qpenc_conn_scratch(header_table_size, max_inflight) bytes
+struct QseCall {
+    const uint8_t* in;
+    uint64_t in_size;
+    const hhuff_hpack_header_t* hdr;
+    uint32_t nhdr;
+    const hhuff_qpack_response_t* res;
+    const uint32_t* conn_first;
+    uint32_t nconn, nres;
+    const uint64_t* stream_id;
+    const uint32_t *dec_off, *dec_len;
+    uint32_t header_table_size;
+    uint64_t max_blocked;
+    uint32_t max_inflight;
+    uint32_t server_off, server_len;
+    uint8_t* out;
+    const uint64_t* out_off;
+    uint32_t *out_len, *header_len;
+    int32_t* rstatus;
+    uint8_t* rflags;
+    uint8_t* enc_out;
+    const uint64_t* enc_out_off;
+    uint32_t* enc_out_len;
+    int32_t* dec_status;
+    uint32_t* dec_consumed;
+    uint8_t* scratch;
+    uint32_t flags;
+};
+uint64_t qpenc_conn_scratch(uint32_t header_table_size, uint32_t max_inflight);
+hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream);
+
 // HPACK header blocks (f4): see include/hhuff.h hhuff_hpack_decode_blocks; scratch = nconn x
 // hpack_conn_scratch(table_size) bytes of device memory
 uint64_t hpack_conn_scratch(uint32_t table_size);

@@ -17,8 +17,9 @@ Several steps of one session continue the same connections (HHUFF_ENC_CONTINUE).
 """
 import numpy as np
 
-from .codec import HPE_HEADER_DTYPE, HPE_RESPONSE_DTYPE, QPE_RESPONSE_DTYPE, HDR_DONT_COMPRESS, HDR_TOKEN, \
-    QRES_DATAGRAM, QRES_REQUEST, RES_END_STREAM, RES_REQUEST, RES_SERVER, RES_TRAILERS, hpack_response_bound, qpack_response_bound
+from .codec import HPE_HEADER_DTYPE, HPE_RESPONSE_DTYPE, QPE_RESPONSE_DTYPE, HDR_DONT_COMPRESS, HDR_LIKELY_TO_REPEAT, \
+    HDR_TOKEN, QRES_DATAGRAM, QRES_REQUEST, RES_END_STREAM, RES_REQUEST, RES_SERVER, RES_TRAILERS, hpack_response_bound, \
+    qpack_response_bound, qpack_session_response_bound
 
 SERVER = b"h2o/2.3.0-dev"
 _CTYPES = [b"text/html; charset=utf-8", b"text/css", b"application/javascript", b"image/png", b"image/jpeg",
@@ -413,3 +414,66 @@ def qpack_out_offsets(hdr, res, server_len):
     b = qpack_response_bound(csum[first + nh] - csum[first], nh, sl, res["dfid_len"].astype(np.int64))
     b = (b + 15) // 16 * 16
     return np.concatenate([[0], np.cumsum(b)]).astype(np.uint64)
+
+
+# h2o_token_t.flags.likely_to_repeat (misc/tokens.pl) among the names this module uses
+_LIKELY_TO_REPEAT = {b":authority", b":protocol", b"accept", b"accept-encoding", b"accept-language", b"accept-ranges",
+                     b"access-control-allow-origin", b"alt-svc", b"cache-control", b"content-encoding",
+                     b"content-security-policy", b"content-type", b"date", b"expect", b"forwarded", b"link", b"origin",
+                     b"priority", b"referer", b"retry-after", b"server", b"strict-transport-security", b"te",
+                     b"user-agent", b"vary", b"x-content-type-options", b"x-forwarded-for", b"x-frame-options",
+                     b"x-xss-protection"}
+
+
+def likely_to_repeat(data, hdr):
+    """hdr with HHUFF_HDR_LIKELY_TO_REPEAT set on the token headers whose token h2o flags likely_to_repeat"""
+    hdr = hdr.copy()
+    raw = np.asarray(data).tobytes()
+    for h in hdr:
+        if h["flags"] & HDR_TOKEN and raw[h["name_off"]:int(h["name_off"]) + int(h["name_len"])] in _LIKELY_TO_REPEAT:
+            h["flags"] |= HDR_LIKELY_TO_REPEAT
+    return hdr
+
+
+def qpack_session_out_offsets(hdr, res, server_len):
+    """[nres + 1] u64 region starts: hhuff_qpack_session_response_bound per response, 16-byte aligned"""
+    nv = (hdr["name_len"].astype(np.int64) + hdr["value_len"]) if hdr.size else np.zeros(0, np.int64)
+    csum = np.concatenate([[0], np.cumsum(nv)])
+    first = res["hdr_first"].astype(np.int64)
+    nh = res["nhdr"].astype(np.int64)
+    sl = np.where(res["flags"] & RES_SERVER, server_len, 0)
+    b = qpack_session_response_bound(csum[first + nh] - csum[first], nh, sl, res["dfid_len"].astype(np.int64))
+    b = (b + 15) // 16 * 16
+    return np.concatenate([[0], np.cumsum(b)]).astype(np.uint64)
+
+
+def to_qpack_sessions(batch, steps, seed=0, requests=False, dfid_frac=0.02, odd_status_frac=0.01):
+    """A make_session / make_request_session batch as `steps` steps of QPACK encoder sessions (include/hhuff.h
+    hhuff_qpack_flatten_sessions): every connection's responses (trailers dropped) are cut into `steps` runs in
+    order, response k of a connection goes out on stream 4 k (client-initiated bidirectional streams), and the token
+    headers h2o flags likely_to_repeat get HHUFF_HDR_LIKELY_TO_REPEAT.  -> list of dicts data, hdr, res,
+    conn_first, stream_id, server_off, server_len, out_off (all steps share data and hdr)"""
+    rng = np.random.default_rng(seed)
+    q = to_qpack_requests(batch, seed, dfid_frac) if requests else to_qpack(batch, seed, dfid_frac, odd_status_frac)
+    keep = np.ones(batch["res"].size, bool) if requests else (batch["res"]["flags"] & RES_TRAILERS) == 0
+    hdr = likely_to_repeat(q["data"], q["hdr"])
+    nconn = batch["conn_first"].size - 1
+    kept = np.concatenate([[0], np.cumsum(keep)])
+    cf = kept[batch["conn_first"].astype(np.int64)]  # conn_first without the trailers
+    cuts = np.zeros((nconn, steps + 1), np.int64)
+    for c in range(nconn):
+        n = int(cf[c + 1] - cf[c])
+        inner = np.sort(rng.integers(0, n + 1, steps - 1)) if n else np.zeros(steps - 1, np.int64)
+        cuts[c] = cf[c] + np.concatenate([[0], inner, [n]])
+    out = []
+    for s in range(steps):
+        idx = np.concatenate([np.arange(cuts[c, s], cuts[c, s + 1]) for c in range(nconn)] + [np.zeros(0, np.int64)])
+        idx = idx.astype(np.int64)
+        res = q["res"][idx]
+        conn = np.searchsorted(cf, idx, side="right") - 1
+        sid = (4 * (idx - cf[conn])).astype(np.uint64)
+        conn_first = np.concatenate([[0], np.cumsum(cuts[:, s + 1] - cuts[:, s])]).astype(np.uint32)
+        out.append(dict(data=q["data"], hdr=hdr, res=res, conn_first=conn_first, stream_id=sid,
+                        server_off=q["server_off"], server_len=q["server_len"],
+                        out_off=qpack_session_out_offsets(hdr, res, q["server_len"])))
+    return out

@@ -511,6 +511,91 @@ int hhuff_qpack_flatten_responses(const uint8_t *in, uint64_t in_size, const hhu
                                   uint32_t server_len, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
                                   uint32_t *header_len, int32_t *rstatus, void *stream);
 
+/* (2g') HTTP/3 encoder sessions: h2o_qpack_flatten_response / _request WITH an encoder-stream buffer
+ *      (lib/http3/qpack.c:1148-1213, :1244-1310) and h2o_qpack_encoder_handle_input (:902-1005) for many
+ *      connections, each with its own encoder: a dynamic table, the list of sections the peer has not
+ *      acknowledged yet (inflight) and largest_known_received, kept in scratch between calls.  One call is one
+ *      step of every connection c, in the order h2o reaches them on a connection:
+ *        1. decoder stream in[dec_off[c] .. + dec_len[c]) (dec_off == NULL: none) through handle_input:
+ *           Insert Count Increment (00, 6-bit prefix; an error when the increment is 0 or
+ *           largest_known_received + n >= total_inserts, the table's count plus 1), Section Acknowledgment
+ *           (1, 7-bit; the first inflight entry of the stream leaves, largest_known_received rises to its
+ *           largest_ref, num_blocked drops if it was blocking; an unknown stream is an error), Stream
+ *           Cancellation (01, 6-bit; every inflight entry of the stream leaves; never an error).
+ *           dec_consumed[c] = bytes of the complete instructions taken (an instruction cut inside its integer
+ *           is no error: the rest waits, as enc_consumed does on the decode side); dec_status[c] = 0,
+ *           HHUFF_QPK_DECODER_STREAM, HHUFF_QPK_DECOMPRESSION_FAILED (an integer that overflows),
+ *           HHUFF_QPK_SKIPPED (an earlier step failed) or HHUFF_RES_EINVAL (dec_off + dec_len past in_size).
+ *           After any of these but 0, this step's responses and every later response of the connection get
+ *           HHUFF_RES_SKIPPED and write nothing.
+ *        2. the responses conn_first[c] .. conn_first[c+1]-1 in order (records, headers, own fields, frame
+ *           header, out regions and header_len[] as for hhuff_qpack_flatten_responses), response r on the
+ *           request stream stream_id[r].
+ *      Table: 1-based, never evicts; an insert needs name_len + value_len + 32 <= header_table_size - used;
+ *      base_index = the insert count at the section's start.  The section has an encoder buffer only without
+ *      HHUFF_QRES_NO_ENCODER_STREAM and with num_blocked < max_blocked at its start (:1250).
+ *      Lookup (lookup_dynamic): newest to oldest, the first entry with the name and value, else the newest with
+ *      the name; without an encoder buffer only entries <= largest_known_received.  Names compare by bytes
+ *      (h2o compares token names by pointer: the same, since only token names are ever inserted).
+ *      Per field, in this order: an exact static match -> static indexed; an exact dynamic match -> dynamic
+ *      indexed (pre-base 0x80 6-bit, post-base 0x10 4-bit); likely_to_repeat && buffer && ((no static && no
+ *      dynamic name match) || value_len >= 8) && it fits -> an insert on the encoder stream (0xC0 static name
+ *      reference, 0x80 dynamic name reference, 0x40 name string with prefix 5; then the value string, prefix 7)
+ *      and a post-base reference to the new entry; else a static name reference; else a dynamic name reference
+ *      (0x40|N 4-bit pre-base, 0x00|N<<3 3-bit post-base); else a literal with a literal name.  The call's own
+ *      fields carry h2o's token flags: server is likely to repeat, :status, content-length and
+ *      datagram-flow-id are not.  A request's own fields are headers; set HHUFF_HDR_LIKELY_TO_REPEAT on
+ *      :authority and :protocol.
+ *      Section prefix (:1263-1298): no dynamic reference -> 00 00 and nothing becomes inflight.  Otherwise
+ *      largest_ref below largest_known_received is raised to it; above it the section is blocking
+ *      (++num_blocked); {stream_id, largest_ref, blocking} joins the inflight list; Required Insert Count =
+ *      largest_ref + 1 (8-bit prefix), then the delta base with its sign bit (7-bit prefix).
+ *      Three deliberate differences from the reference: Insert With Name Reference on a dynamic
+ *      name writes the RELATIVE index (insert count - 1 - absolute, RFC 9204 4.3.2; the reference writes the
+ *      absolute one, :1177/:1073, which its own decoder :336-341 misreads); an inflight entry is removed entry
+ *      by entry (:928 moves size - index bytes); the inflight list holds max_inflight entries per connection: a
+ *      section that would need a slot when it is full is flattened as with no encoder at all -- the bytes of
+ *      hhuff_qpack_flatten_responses --, rflags[r] |= 1, rstatus[r] = 0, no state change.
+ *      Outputs: out_len[r], header_len[r]; rstatus[r] = 0, HHUFF_RES_EINVAL, HHUFF_RES_SPACE (the frame does
+ *      not fit its region, or the section's inserts do not fit what is left of the connection's encoder-stream
+ *      region) or HHUFF_RES_SKIPPED; a failed response writes nothing and changes no state (the connection goes
+ *      on).  enc_out_len[c] = the step's encoder-stream bytes at enc_out + enc_out_off[c] (region up to
+ *      enc_out_off[c+1]): header_table_size + 4 bytes always fit, because the table never evicts.  With
+ *      HHUFF_QENC_SET_CAPACITY a call without HHUFF_QENC_CONTINUE starts every encoder stream with Set Dynamic
+ *      Table Capacity; where not even that fits, the step's responses get HHUFF_RES_SPACE.
+ *      hhuff_qpack_session_response_bound() always fits a response's region.
+ *      Device arrays; scratch = hhuff_qpack_enc_scratch_size(nconn, header_table_size, max_inflight) bytes
+ *      (16-byte aligned): HHUFF_QENC_CONTINUE carries tables, inflight lists and failed state over from the
+ *      previous call (same nconn, header_table_size, max_inflight); the tables hold scratch offsets, not
+ *      addresses, so scratch may be moved between calls.  header_table_size <= 65536 (else the call
+ *      returns HHUFF_RES_EINVAL).  nres = conn_first[nconn] (host copy).  in_size < 2^32.  Asynchronous on `stream`: a prep pass
+ *      (one lane per header), the walk (one lane per connection: decides, writes no output byte), the emit pass
+ *      (one lane per field, insert and response head).  Stream-ordered pool workspace of 124 bytes per header,
+ *      112 per response and 16 per connection. */
+#define HHUFF_HDR_LIKELY_TO_REPEAT 4u    /* h2o_token_t.flags.likely_to_repeat of the header's token (caller-supplied,
+                                            like HHUFF_HDR_TOKEN; meaningful only with HHUFF_HDR_TOKEN) */
+#define HHUFF_QRES_NO_ENCODER_STREAM 32u /* this response is flattened with encoder_buf == NULL */
+#define HHUFF_QENC_CONTINUE 1u
+#define HHUFF_QENC_SET_CAPACITY 2u       /* 0x20 | 5-bit-prefix int header_table_size */
+#define HHUFF_QPK_DECODER_STREAM 0x30202 /* H2O_HTTP3_ERROR_QPACK_DECODER_STREAM */
+/* the longer section prefix and dynamic indices at up to 2,048 entries */
+static inline uint64_t hhuff_qpack_session_response_bound(uint64_t name_value_bytes, uint32_t nhdr, uint32_t server_len,
+                                                          uint32_t dfid_len)
+{
+    uint64_t bound = hhuff_qpack_response_bound(name_value_bytes, nhdr, server_len, dfid_len);
+    return bound + 8;
+}
+uint64_t hhuff_qpack_enc_scratch_size(uint32_t nconn, uint32_t header_table_size, uint32_t max_inflight);
+int hhuff_qpack_flatten_sessions(const uint8_t *in, uint64_t in_size, const hhuff_hpack_header_t *hdr, uint32_t nhdr,
+                                 const hhuff_qpack_response_t *res, const uint32_t *conn_first, uint32_t nconn,
+                                 uint32_t nres, const uint64_t *stream_id, const uint32_t *dec_off,
+                                 const uint32_t *dec_len, uint32_t header_table_size, uint64_t max_blocked,
+                                 uint32_t max_inflight, uint32_t server_off, uint32_t server_len, uint8_t *out,
+                                 const uint64_t *out_off, uint32_t *out_len, uint32_t *header_len, int32_t *rstatus,
+                                 uint8_t *rflags, uint8_t *enc_out, const uint64_t *enc_out_off, uint32_t *enc_out_len,
+                                 int32_t *dec_status, uint32_t *dec_consumed, void *scratch, uint64_t scratch_size,
+                                 unsigned flags, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
