@@ -281,9 +281,9 @@ HHUFF_API int hhuff_hpack_flatten_responses(const uint8_t* in, uint64_t in_size,
     if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
     if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)hdr & 3u) != 0 || ((uintptr_t)out_off & 7u) != 0)
         return arg_fail("misaligned hdr / res / out_off");
-    hipError_t e = hhuff::launch_hpack_flatten(in, in_size, hdr, nhdr, res, conn_first, nconn, nres, server_off, server_len,
-                                               out, out_off, out_len, headers_size, rstatus, (uint8_t*)scratch, flags,
-                                               (hipStream_t)stream);
+    const hhuff::HpeCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, server_off, server_len,
+                              out, out_off, out_len, headers_size, rstatus, (uint8_t*)scratch, flags};
+    hipError_t e = hhuff::launch_hpack_flatten(call, (hipStream_t)stream);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "hpack flatten launch");
 }
 
@@ -296,8 +296,9 @@ HHUFF_API int hhuff_qpack_flatten_responses(const uint8_t* in, uint64_t in_size,
     if (in_size >= (1ull << 32)) return arg_fail("in_size must stay below 2^32 (u32 offsets)");
     if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)hdr & 3u) != 0 || ((uintptr_t)out_off & 7u) != 0)
         return arg_fail("misaligned hdr / res / out_off");
-    hipError_t e = hhuff::launch_qpack_flatten(in, in_size, hdr, nhdr, res, nres, server_off, server_len, out, out_off, out_len,
-                                               header_len, rstatus, (hipStream_t)stream);
+    const hhuff::QpeCall call{in, in_size, hdr, nhdr, res, nres, server_off, server_len, out, out_off, out_len,
+                              header_len, rstatus};
+    hipError_t e = hhuff::launch_qpack_flatten(call, (hipStream_t)stream);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack flatten launch");
 }
 
@@ -728,16 +729,7 @@ HHUFF_API int hhuff_service_stamps(uint32_t* out4) {
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-struct Carve {
-    uint8_t* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + off);
-        off += up16(count * sizeof(T));
-        return p;
-    }
-};
+using hhuff::Carve;  // the device buffer's pieces (hhuff_launch.h)
 
 size_t in_off_count(const uint32_t* in_len, uint32_t n) { return in_len ? n : (size_t)n + 1; }
 

@@ -92,22 +92,60 @@ hipError_t work_alloc(void** p, uint64_t bytes, hipStream_t stream);
 // hand the pool's kept memory on the current device back to the driver (hhuff_pool_trim)
 hipError_t pool_trim();
 
-// HTTP/2 response header blocks, encode side (hhuff_hpenc.hip): include/hhuff.h hhuff_hpack_flatten_responses;
-// scratch = nconn x hpenc_conn_scratch() bytes
+// A buffer cut into 16-byte aligned pieces by one sequence of take<T>(count) calls.  Run on a null base the
+// sequence yields the size in `off` (the pointers mean nothing), run again on the allocation it yields the
+// pointers: no size is written twice.
+struct Carve {
+    uint8_t* base;
+    uint64_t off = 0;
+    template <class T>
+    T* take(uint64_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + 15u) & ~15ull;
+        return p;
+    }
+};
+
+// HTTP/2 response header blocks, encode side (hhuff_hpenc.hip): include/hhuff.h hhuff_hpack_flatten_responses,
+// its arguments in its order; scratch = nconn x hpenc_conn_scratch() bytes
+struct HpeCall {
+    const uint8_t* in;
+    uint64_t in_size;
+    const hhuff_hpack_header_t* hdr;
+    uint32_t nhdr;
+    const hhuff_hpack_response_t* res;
+    const uint32_t* conn_first;
+    uint32_t nconn, nres;
+    uint32_t server_off, server_len;
+    uint8_t* out;
+    const uint64_t* out_off;
+    uint32_t* out_len;
+    uint32_t* headers_size;
+    int32_t* rstatus;
+    uint8_t* scratch;
+    uint32_t flags;
+};
 uint64_t hpenc_conn_scratch();
-hipError_t launch_hpack_flatten(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr, uint32_t nhdr,
-                                const hhuff_hpack_response_t* res, const uint32_t* conn_first, uint32_t nconn, uint32_t nres,
-                                uint32_t server_off, uint32_t server_len, uint8_t* out, const uint64_t* out_off,
-                                uint32_t* out_len, uint32_t* headers_size, int32_t* rstatus, uint8_t* scratch,
-                                uint32_t flags, hipStream_t stream);
+hipError_t launch_hpack_flatten(const HpeCall& call, hipStream_t stream);
 
-// HTTP/3 response HEADERS frames (hhuff_hpenc.hip): include/hhuff.h hhuff_qpack_flatten_responses
-hipError_t launch_qpack_flatten(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr, uint32_t nhdr,
-                                const hhuff_qpack_response_t* res, uint32_t nres, uint32_t server_off, uint32_t server_len,
-                                uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint32_t* header_len,
-                                int32_t* rstatus, hipStream_t stream);
+// HTTP/3 response HEADERS frames (hhuff_qpenc.hip): include/hhuff.h hhuff_qpack_flatten_responses
+struct QpeCall {
+    const uint8_t* in;
+    uint64_t in_size;
+    const hhuff_hpack_header_t* hdr;
+    uint32_t nhdr;
+    const hhuff_qpack_response_t* res;
+    uint32_t nres;
+    uint32_t server_off, server_len;
+    uint8_t* out;
+    const uint64_t* out_off;
+    uint32_t* out_len;
+    uint32_t* header_len;
+    int32_t* rstatus;
+};
+hipError_t launch_qpack_flatten(const QpeCall& call, hipStream_t stream);
 
-// HTTP/3 encoder sessions (hhuff_hpenc.hip): include/hhuff.h hhuff_qpack_flatten_sessions; scratch = nconn x
+// HTTP/3 encoder sessions (hhuff_qpenc.hip): include/hhuff.h hhuff_qpack_flatten_sessions; scratch = nconn x
 // qpenc_conn_scratch(header_table_size, max_inflight) bytes
 struct QseCall {
     const uint8_t* in;

@@ -6,6 +6,8 @@
   hpenc[N]   f4 encode half: HTTP/2 responses of N connections (default 65536) flattened with their encoder
              tables (hhuff_hpack_flatten_responses)
   reqenc[N]  the same for the client's requests (h2o_hpack_flatten_request)
+  qpenc[N]   the same responses as HTTP/3 HEADERS frames without an encoder stream (hhuff_qpack_flatten_responses)
+  qsess[N]   ... and with one: QPACK encoder sessions (hhuff_qpack_flatten_sessions), a fresh step and a continued one
   blocks[N]  f4: N synthetic HPACK connections (default 65536), header blocks decoded with a dynamic
       table per connection; CPU baselines: the reference (1 thread) and the restatement (16 threads)
   lit 16M c4 strings framed as HPACK literals (h2o_hpack_encode_string), then decoded as literals
@@ -308,6 +310,86 @@ def hpenc_line(torch, codec, nconn=65536, requests=False):
     return line
 
 
+def _qpack_tiled(q, k, out_offsets):
+    """k copies of the QPACK batch q (hpenc_synth.to_qpack / one step of to_qpack_sessions), as hpenc_synth.tile
+    makes them of an HTTP/2 batch: independent connections with the same responses, the strings shared"""
+    nres, nhdr = q["res"].size, q["hdr"].size
+    res, hdr = np.tile(q["res"], k), np.tile(q["hdr"], k)
+    res["hdr_first"] += np.repeat(np.arange(k, dtype=np.uint32) * nhdr, nres)
+    t = dict(q, hdr=hdr, res=res, out_off=out_offsets(hdr, res, q["server_len"]))
+    if "conn_first" in q:
+        cf = q["conn_first"].astype(np.int64)
+        t["conn_first"] = np.concatenate([cf[:-1] + j * nres for j in range(k)] + [[k * nres]]).astype(np.uint32)
+        t["stream_id"] = np.tile(q["stream_id"], k)
+    return t
+
+
+def qpenc_line(torch, codec, nconn=65536):
+    """HTTP/3 response HEADERS frames without an encoder stream (hhuff_qpack_flatten_responses): hpenc_line's 4,096
+    synthetic connections as HTTP/3 responses (hpenc_synth.to_qpack), tiled to nconn"""
+    from h2o_amd import hpenc_synth as HE
+
+    q = _qpack_tiled(HE.to_qpack(HE.make_session(4096, seed=13)[0], seed=13), max(1, nconn // 4096), HE.qpack_out_offsets)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()  # noqa: E731
+    d, hd, rs = dev(q["data"]), dev(q["hdr"].view(np.uint8)), dev(q["res"].view(np.uint8))
+    oo = dev(q["out_off"].view(np.int64))
+    nres, nhdr = int(q["res"].size), int(q["hdr"].size)
+    out = torch.empty(int(q["out_off"][-1]), dtype=torch.uint8, device="cuda")
+    res = {}
+
+    def run():
+        res["r"] = codec.qpack_flatten_responses(d, hd, rs, nres, oo, q["server_off"], q["server_len"],
+                                                 in_size=int(q["data"].size), out=out)
+
+    t = timed(torch, run, steps=10, warmup=2)
+    r = res["r"]
+    return {"config": "qpenc", "connections": max(1, nconn // 4096) * 4096, "responses": nres, "fields": nhdr,
+            "frame_bytes": int(r["out_len"][:nres].to(torch.int64).sum().item()),
+            "ok_responses": int((r["rstatus"][:nres] == 0).sum().item()), "flatten_ms": round(t, 4),
+            "responses_per_s": round(nres / (t * 1e-3), 1), "fields_per_s": round(nhdr / (t * 1e-3), 1)}
+
+
+def qsess_line(torch, codec, nconn=65536):
+    """QPACK encoder sessions (hhuff_qpack_flatten_sessions): hpenc_line's 4,096 synthetic connections cut into two
+    steps (hpenc_synth.to_qpack_sessions), tiled to nconn.  fresh: the first step on new sessions, with Set
+    Dynamic Table Capacity.  continued: the second step with HHUFF_QENC_CONTINUE and no decoder input, every call
+    on the sessions as the call before left them -- after the warm-up the tables hold the step's strings, so this
+    is the steady state of connections that repeat themselves: dynamic references, no inserts.  max_inflight and
+    max_blocked are set so that the unacknowledged sections of all timed calls fit."""
+    from h2o_amd import hpenc_synth as HE
+
+    k = max(1, nconn // 4096)
+    steps = [_qpack_tiled(s, k, HE.qpack_session_out_offsets)
+             for s in HE.to_qpack_sessions(HE.make_session(4096, seed=13)[0], 2, seed=13)]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()  # noqa: E731
+    d, hd = dev(steps[0]["data"]), dev(steps[0]["hdr"].view(np.uint8))  # the steps share data and hdr
+    nc, nhdr = int(steps[0]["conn_first"].size - 1), int(steps[0]["hdr"].size)
+    kw = dict(header_table_size=4096, max_blocked=1 << 20, max_inflight=128, server_off=steps[0]["server_off"],
+              server_len=steps[0]["server_len"], in_size=int(steps[0]["data"].size))
+    kw["scratch"] = torch.empty(codec.qpack_enc_scratch_size(nc, 4096, 128), dtype=torch.uint8, device="cuda")
+    kw["enc_out_off"] = torch.arange(nc + 1, dtype=torch.int64, device="cuda") * 4112
+    kw["enc_out"] = torch.empty(nc * 4112, dtype=torch.uint8, device="cuda")
+    line = {"config": "qsess", "connections": nc, "fields": nhdr}
+    for name, q, cont in (("fresh", steps[0], False), ("continued", steps[1], True)):
+        rs, cf = dev(q["res"].view(np.uint8)), dev(q["conn_first"].view(np.int32))
+        sid, oo = dev(q["stream_id"].view(np.int64)), dev(q["out_off"].view(np.int64))
+        nres = int(q["res"].size)
+        out = torch.empty(int(q["out_off"][-1]), dtype=torch.uint8, device="cuda")
+        res = {}
+
+        def run():
+            res["r"] = codec.qpack_flatten_sessions(d, hd, rs, cf, nres, sid, oo, out=out, cont=cont,
+                                                    set_capacity=not cont, **kw)
+
+        t = timed(torch, run, steps=10, warmup=2)
+        r = res["r"]
+        line[name] = {"responses": nres, "ok_responses": int((r["rstatus"][:nres] == 0).sum().item()),
+                      "frame_bytes": int(r["out_len"][:nres].to(torch.int64).sum().item()),
+                      "encoder_stream_bytes": int(r["enc_out_len"][:nc].to(torch.int64).sum().item()),
+                      "flatten_ms": round(t, 4), "responses_per_s": round(nres / (t * 1e-3), 1)}
+    return line
+
+
 def responses_line(torch, codec, nconn=65536):
     """f4, client side: HTTP/2 response blocks as h2o's client receives them (h2o_amd/hpack_synth.py
     make_response_connections: 1-8 response heads per connection, a tenth of them trailers, 1 % adversarial)
@@ -378,6 +460,10 @@ def main():
         if cfg.startswith("hpenc"):
             n = int(cfg[5:]) if len(cfg) > 5 else 65536
             print(json.dumps(hpenc_line(torch, codec, n)), flush=True)
+            continue
+        if cfg.startswith("qpenc") or cfg.startswith("qsess"):
+            n = int(cfg[5:]) if len(cfg) > 5 else 65536
+            print(json.dumps((qpenc_line if cfg.startswith("qpenc") else qsess_line)(torch, codec, n)), flush=True)
             continue
         if cfg.startswith("resp"):
             n = int(cfg[4:]) if len(cfg) > 4 else 65536
