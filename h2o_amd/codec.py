@@ -172,7 +172,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_hpack_flatten_responses", "hhuff_qpack_flatten_responses", "hhuff_qpack_enc_scratch_size",
             "hhuff_qpack_flatten_sessions", "hhuff_set_decode_kernel",
             "hhuff_decode_batch_host_packed", "hhuff_encode_batch_host_packed", "hhuff_set_edge_defer_min",
-            "hhuff_decode_batch_multi", "hhuff_encode_batch_multi", "hhuff_shard_bounds")
+            "hhuff_decode_batch_multi", "hhuff_encode_batch_multi", "hhuff_shard_bounds",
+            "hhuff_debug_encode_blocks_per_cu")
 
 
 def _check(rc, what):

@@ -834,7 +834,9 @@ struct EncV2 {
 #define HHUFF_ENC_OTHER_U 1
 #endif
 // U: whole dwords a trip of the bulk loop (1 or 2; the loop's ballots keep the compiler from unrolling it)
-template <int U = 1, class O>
+// T257: `enc` has 257 entries (entry 256 zero) instead of 512 (256..511 zero): the head and tail words are
+// masked, so a byte outside the string looks up entry 256 (as chunk_code_bits_nb does)
+template <int U = 1, bool T257 = false, class O>
 __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint32_t last, uint32_t start, uint32_t len,
                                                     bool active, O obase, uint32_t startbit,
                                                     const uint2* __restrict__ enc, uint32_t limit, bool pad) {
@@ -852,6 +854,7 @@ __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint3
         vm &= (j + 1 == ndw) ? mlast : 0xFFFFFFFFu;
         vm = on ? vm : 0u;
         const uint32_t iw = ~vm & 0x01010101u;
+        if constexpr (T257) w &= vm;
         E.put4(enc[__builtin_amdgcn_perm(iw, w, 0x0C0C0400u)], enc[__builtin_amdgcn_perm(iw, w, 0x0C0C0501u)],
                enc[__builtin_amdgcn_perm(iw, w, 0x0C0C0602u)], enc[__builtin_amdgcn_perm(iw, w, 0x0C0C0703u)], on);
     };

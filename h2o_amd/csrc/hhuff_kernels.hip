@@ -1758,6 +1758,7 @@ __global__ __launch_bounds__(WAVES * 64) void encode_staged_kernel(EncArgs A) {
 // group, the other's waves keep the SIMDs busy.  Every string is encoded in place in the chunk's output
 // stage (slot = input offset), which is then copied out whole.
 constexpr uint32_t kSortBins = 128;  // whole dwords 0..126, and 127+
+constexpr uint32_t kSortFail = 0xFFFFu;  // kFailLen in the 16-bit encoded lengths
 struct SortChunk {  // per thread: its string of a chunk and the chunk's input span
     uint32_t s, e, lo, hi;
 };
@@ -1997,6 +1998,305 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
         c = cn;
     }
 }
+
+// The same kernel trimmed to five workgroups a CU, for batches whose chunks fit a smaller stage (launch_encode:
+// a mean string of at most HHUFF_ENCO_SMALL_MEAN bytes).  LDS: a stage of at most 13,568 B, a 257-entry code
+// table (the head and tail words are masked and look up entry 256 outside the string), one packed record a string,
+// 16-bit encoded lengths, byte ranks: 31,072 B at CH = 13,312.  Registers, 96 VGPRs for five waves a SIMD (a wave
+// of each workgroup on every SIMD): the chunk's span in scalar registers, a chunk's offsets kept in its LDS
+// records only, the next span handed on through LDS, two copy-out chunks in flight, and the thread index a fresh
+// value in each phase of the loop (fresh() below).  At four workgroups a CU the trimmed kernel is 2-4 % slower than
+// the one above (the phase-local index arithmetic alone costs 2 %), so the large stage keeps that kernel.
+namespace five {  // (the kernel keeps its name: profiles and bench.py file it under the sorted encoder)
+template <int NS, int CH, int SPT = 1>
+__global__ __launch_bounds__(NS / SPT) __attribute__((amdgpu_waves_per_eu(5)))
+void encode_sorted_kernel(EncArgs A) {
+    static_assert(SPT == 1 || SPT == 2, "one string a thread, or a sorted pair");
+    constexpr uint32_t kSortStr = NS, NT = NS / SPT;
+    static_assert(NS <= 256 && CH % 16 == 0 && CH <= 13568, "a rank is a byte, a span offset 14 bits; five stages a CU");
+    constexpr int NV = (CH + 16 * NT - 1) / (16 * NT);  // 16-B span chunks per thread
+    constexpr int CB = 2;  // those of the copy-out read ahead of their stores (96 VGPRs hold two)
+    __shared__ __attribute__((aligned(16))) uint2 s_enc[257];  // 256: bytes outside a string
+    __shared__ __attribute__((aligned(16))) uint32_t s_in[CH / 4 + 8];
+    __shared__ __attribute__((aligned(16))) uint32_t s_out[CH / 4 + 8];
+    __shared__ uint32_t s_str[kSortStr];  // offset in the span | length << 14 of chunk string t
+    __shared__ uint16_t s_olen[kSortStr];  // its encoded length (kSortFail: none), back to its own thread
+    __shared__ uint8_t s_perm[kSortStr];
+    __shared__ uint32_t s_bin[kSortBins];  // strings per bin, then the bins' first places
+    __shared__ uint32_t s_lohi[2][2];       // the next chunk's input span {lo, hi}, by the parity of the trip
+    uint32_t t = threadIdx.x;
+    // fresh(): the thread index as a new value.  What a phase of the loop derives from it (addresses of the
+    // thread's records and stage chunks, its predicates) is then computed in that phase, not once before the loop
+    // and kept in registers across the encode: fourteen VGPRs (111 -> 97 as the allocator leaves them).
+    auto fresh = [&] { __asm__ volatile("" : "+v"(t)); };
+    const uint32_t lane = threadIdx.x & 63u;  // (PROF_FLUSH's, in profile builds)
+    (void)lane;
+    for (uint32_t k = t; k < 257; k += NT) s_enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
+    const uint64_t nch = ((uint64_t)A.n + kSortStr - 1) / kSortStr;
+    uint64_t c = blockIdx.x;
+    if (c >= nch) return;
+    auto span_of = [](const SortChunk& q) { return q.hi > q.lo ? ((q.hi + 15u) & ~15u) - (q.lo & ~15u) : 0u; };
+    auto issue_span = [&](uint4 (&v)[NV], const SortChunk& q) {
+        const uint32_t a0 = q.lo & ~15u, span = span_of(q);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const uint32_t k = (uint32_t)j * (16u * NT) + t * 16u;
+            const uint64_t g = (uint64_t)a0 + k;
+            if (k < span && span <= (uint32_t)CH && g + 16 <= A.in_size) v[j] = *reinterpret_cast<const uint4*>(A.in + g);
+        }
+    };
+    auto commit_span = [&](const uint4 (&v)[NV], const SortChunk& q) {
+        const uint32_t a0 = q.lo & ~15u, span = span_of(q);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const uint32_t k = (uint32_t)j * (16u * NT) + t * 16u;
+            const uint64_t g = (uint64_t)a0 + k;
+            if (k < span) *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_in) + k) =
+                g + 16 <= A.in_size ? v[j] : load16_tail(A.in, A.in_size, g);
+        }
+    };
+    auto issue_chunk = [&](SortChunk (&q)[SPT], uint64_t qb) {
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) q[u] = sort_chunk_issue(A, qb, t + (uint32_t)u * NT, NS);
+    };
+    auto land = [](SortChunk (&q)[SPT]) {  // wait for a chunk's offsets here (see below)
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e), "+v"(q[u].lo), "+v"(q[u].hi) : : "memory");
+            // the chunk's span is the same in every lane: kept in scalar registers from here on
+            q[u].lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)q[u].lo);
+            q[u].hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)q[u].hi);
+        }
+    };
+    // In the loop a thread loads its own strings' offsets only (two registers in flight across the encode, not
+    // four): the span is the first string's start and the last one's end (sort_chunk_issue's clamps make
+    // them so in a short last chunk too), handed to the next trip through s_lohi[par].
+    auto issue_strings = [&](SortChunk (&q)[SPT], uint64_t qb) {
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            const uint64_t ic = min(qb + t + (uint32_t)u * NT, (uint64_t)A.n - 1u);
+            q[u] = SortChunk{A.in_off[ic], A.in_off[ic + 1], 0u, 0u};
+        }
+    };
+    auto land_strings = [&](SortChunk (&q)[SPT], uint32_t par) {
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e) : : "memory");
+        if (t == 0) s_lohi[par][0] = q[0].s;
+        if (t == NT - 1u) s_lohi[par][1] = q[SPT - 1].e;
+    };
+    for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // then cleared by each chunk once every wave has read it
+    __syncthreads();
+    // prepare(q): chunk q's span into the input stage, the output stage zeroed from z0 on ([0, z0) is zero
+    // already), its strings' {offset, length} and their ranks within their length bins.  Called once
+    // nothing reads those areas any more (three barriers a chunk in all).
+    uint4 pv[NV];
+    uint32_t bin[SPT], rank[SPT];
+    auto prepare = [&](const SortChunk (&q)[SPT], uint64_t qb, uint32_t z0) {
+        const uint32_t sp = span_of(q[0]);
+        if (sp > (uint32_t)CH) return;  // workgroup-uniform: the per-thread path needs none of it
+        commit_span(pv, q[0]);
+        for (uint32_t k = z0 + t * 16u; k < sp + 16u; k += 16u * NT)
+            *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k) = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            const uint32_t tt = t + (uint32_t)u * NT;
+            const uint32_t ln = qb + tt < A.n ? q[u].e - q[u].s : 0u;
+            // (an empty string may start at the span's end, offset CH: it is never read, and is recorded at 0)
+            s_str[tt] = ln ? (q[u].s - (q[0].lo & ~15u)) | ln << 14 : 0u;
+            // counting sort by the bulk loop's trip count (encode_chunk_v2: dwords from the string's first
+            // aligned dword to its end), which the wave's longest string sets
+            bin[u] = ln ? min((q[u].s + ln - (q[u].s & ~3u)) >> 2, kSortBins - 1u) : 0u;
+            rank[u] = atomicAdd(&s_bin[bin[u]], 1u);
+        }
+    };
+    SortChunk cur[SPT];
+    issue_chunk(cur, c * kSortStr);
+    land(cur);
+    issue_span(pv, cur[0]);
+    prepare(cur, c * kSortStr, 0u);
+    // the next chunk's offsets are loaded a chunk ahead (after barrier 2) and waited for after barrier 3,
+    // before the chunk's stores: no load is then waited for behind a data-dependent number of stores
+    SortChunk nxt[SPT];
+    issue_chunk(nxt, (c + gridDim.x < nch ? c + gridDim.x : c) * kSortStr);
+    land(nxt);  // (once)
+    if (t == 0) {
+        s_lohi[0][0] = nxt[0].lo;
+        s_lohi[0][1] = nxt[0].hi;
+    }
+    uint32_t par = 0;
+    PROF_DECL  // profile builds: barrier 1 / ranks + barrier 2 / encode / barrier 3 + lengths / copy out / prepare
+    for (;;) {
+        const uint64_t cb = c * kSortStr;
+        const uint32_t lo = cur[0].lo, hi = cur[0].hi, a0 = lo & ~15u, span = span_of(cur[0]);
+        EdgeRec* rec = A.edges + 2 * c;  // two records a chunk (sorted_edge_recs)
+        const uint64_t cn = c + gridDim.x;
+        const bool more = cn < nch;
+        const uint64_t cn2 = cn + gridDim.x;  // the chunk after next
+        __syncthreads();  // the chunk's stage, strings and ranks are in, and the next chunk's span
+        PROF_MARK(0);
+        fresh();
+        const uint32_t nlo = s_lohi[par][0], nhi = s_lohi[par][1];  // read here, used after the next barrier
+        auto next_span = [&] {
+            nxt[0].lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nlo);
+            nxt[0].hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)nhi);
+        };
+        if (span > (uint32_t)CH) {  // (workgroup-uniform) a chunk larger than the stage: one thread per string
+#pragma unroll
+            for (int u = 0; u < SPT; ++u) {
+                const uint64_t i = cb + t + (uint32_t)u * NT;
+                // (a staged chunk's offsets live on in its LDS records only: loaded again on this rare path)
+                const uint32_t s = A.in_off[min(i, (uint64_t)A.n - 1u)];
+                const uint32_t len = i < A.n ? A.in_off[i + 1] - s : 0u;
+                uint32_t ol = kFailLen;
+                if (i < A.n && len <= kMaxStrLen) {
+                    RegSink sink;
+                    sink.init(A.out + s);
+                    ol = encode_core(GlobalSource{A.in, A.in_size}, s, len, sink, s_enc);
+                }
+                if (i < A.n) finish_encode(A, (uint32_t)i, len, ol);
+            }
+            if (A.edges && t < 2) rec[t].m = make_uint4(0u, 0u, 0u, 0u);  // direct stores: no edges to defer
+            if (!more) break;
+            next_span();
+            issue_span(pv, nxt[0]);
+            prepare(nxt, cn * kSortStr, 0u);
+            {
+                SortChunk nn[SPT];
+                issue_strings(nn, (cn2 < nch ? cn2 : cn) * kSortStr);
+                land_strings(nn, par ^ 1u);
+#pragma unroll
+                for (int u = 0; u < SPT; ++u) {
+                    cur[u] = nxt[u];
+                    nxt[u] = nn[u];
+                }
+            }
+            c = cn;
+            par ^= 1u;
+            continue;
+        }
+        {  // every wave scans the bin counts (two per lane)
+            const uint32_t ln = t & 63u;
+            const uint32_t x0 = s_bin[2 * ln], x1 = s_bin[2 * ln + 1];
+            const uint32_t ex = wave_excl_scan(x0 + x1, (int)ln);
+#pragma unroll
+            for (int u = 0; u < SPT; ++u) {
+                const uint32_t eb = (uint32_t)__shfl((int)ex, (int)(bin[u] >> 1)), xb = (uint32_t)__shfl((int)x0, (int)(bin[u] >> 1));
+                s_perm[eb + ((bin[u] & 1u) ? xb : 0u) + rank[u]] = (uint8_t)(t + (uint32_t)u * NT);
+            }
+        }
+        __syncthreads();
+        PROF_MARK(1);
+        fresh();
+        next_span();
+        for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // read by every wave above: cleared for the next chunk
+        if (more) issue_span(pv, nxt[0]);     // the next chunk's span: in flight during the encode
+        SortChunk nn[SPT];
+        issue_strings(nn, (cn2 < nch ? cn2 : (more ? cn : c)) * kSortStr);
+        // sorted position t = 64 wave + lane: wave w encodes the w-th length group (SPT = 2: then also the
+        // sorted position NS - 1 - t, so the pair's lengths add up to about twice the mean)
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            const uint32_t j = s_perm[u == 0 ? t : NS - 1u - t];
+            const uint32_t rj = s_str[j];
+            const uint2 sj = make_uint2(rj & 0x3FFFu, rj >> 14);
+            const bool vj = cb + j < A.n;
+            const bool act = vj && sj.y != 0 && sj.y <= kMaxStrLen;
+            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, true>(s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x,
+                                                                          s_enc, act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
+            // the encoded length goes back to the string's own thread (shorter than the string: 16 bits hold
+            // it), so the lengths and statuses are stored in string order, coalesced
+            s_olen[j] = (uint16_t)(act && tb != kFailLen ? (tb + 7) >> 3 : kSortFail);
+        }
+        PROF_MARK(2);
+        __syncthreads();
+        fresh();
+        uint32_t olen[SPT], len[SPT];
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {  // (the string's length from its record: its offsets are kept no longer)
+            const uint32_t o = s_olen[t + (uint32_t)u * NT];
+            olen[u] = o == kSortFail ? kFailLen : o;
+            len[u] = s_str[t + (uint32_t)u * NT] >> 14;
+        }
+        // the next chunk goes in now, before this chunk's stores: its span loads (in flight since the encode
+        // began) are then waited for with no store ahead of them in the memory counter
+        if (more) prepare(nxt, cn * kSortStr, span);  // (overwrites this thread's records: read above)
+        // the chunk after next's offsets are waited for here too, on every path: `nxt = nn` below then copies
+        // registers with no load pending, not behind this chunk's stores
+        land_strings(nn, par ^ 1u);
+        PROF_MARK(5);
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            const uint64_t i = cb + t + (uint32_t)u * NT;
+            if (i < A.n) finish_encode(A, (uint32_t)i, len[u], olen[u]);
+        }
+        PROF_MARK(3);
+        fresh();
+        // the stage's MSB-first words, byte-swapped on the way out (each read chunk is zeroed for the next
+        // chunk); the chunk's first and last 16-B chunks are deferred (edge_fix_kernel)
+        const uint32_t kl = (span - 1u) & ~15u;
+        // CB chunks' LDS reads first, then their stores: an LDS round trip a batch, not one each (all NV at once,
+        // as in encode_sorted_kernel, takes 8 more registers than five waves a SIMD leave)
+#pragma unroll
+        for (int j0 = 0; j0 < NV; j0 += CB) {
+            uint4 cv[CB];
+#pragma unroll
+            for (int jv = j0; jv < NV && jv < j0 + CB; ++jv) {
+                const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
+                if (k < span) cv[jv - j0] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(s_out) + k);
+            }
+#pragma unroll
+            for (int jv = j0; jv < NV && jv < j0 + CB; ++jv) {
+                const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
+                if (k >= span) break;
+                const uint64_t g = (uint64_t)a0 + k;
+                uint4* sp = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k);
+                uint4 v = cv[jv - j0];
+                const bool full = g >= lo && g + 16 <= hi;
+                // (a partial edge chunk stored one byte a lane below is zeroed there, after its bytes are read)
+                if (full || A.edges || !HHUFF_EDGE_BYTES) *sp = make_uint4(0u, 0u, 0u, 0u);
+                v = make_uint4(bswap32(v.x), bswap32(v.y), bswap32(v.z), bswap32(v.w));
+                if (full) st16_out(A.out + g, v);
+                if (k == 0 || k == kl) {
+                    const uint32_t elo = lo > g ? (uint32_t)(lo - g) : 0u;
+                    const uint32_t ehi = hi - g < 16 ? (uint32_t)(hi - g) : 16u;
+                    if (A.edges) {
+                        EdgeRec* e = rec + (k == 0 ? 0 : 1);
+                        e->v = v;
+                        e->m = make_uint4((uint32_t)g, (uint32_t)(g >> 32), full ? 0u : elo, full ? 0u : ehi);
+                    } else if (!HHUFF_EDGE_BYTES && !full && ehi > elo) {  // small batches: the shared chunk's own bytes
+                        store_range16r(A.out + g, v, elo, ehi);
+                    }
+                }
+            }
+        }
+        if (HHUFF_EDGE_BYTES && !A.edges && t < 64u) {  // small batches: the two partial chunks, a byte a lane (wave 0)
+            const uint8_t* so = reinterpret_cast<const uint8_t*>(s_out);
+            edge_bytes<true>(A.out, a0, so, span, lo, hi, (int)t);
+            // lane b read byte b ^ 3 of its chunk and zeroes byte b: every read lands before any lane's zeroing
+            wave_lds_sync();
+            if (t < 32u && span != 0) {  // zero the bytes read (the chunk was left in place above when partial)
+                const uint32_t ke = t < 16u ? 0u : kl;
+                if (!((uint64_t)a0 + ke >= lo && (uint64_t)a0 + ke + 16 <= hi))
+                    reinterpret_cast<uint8_t*>(s_out)[ke + (t & 15u)] = 0;
+            }
+        }
+        if (A.edges && t == 0 && (kl == 0 || span == 0)) rec[1].m = make_uint4(0u, 0u, 0u, 0u);  // one chunk, or none
+        if (A.edges && t == 0 && span == 0) rec[0].m = make_uint4(0u, 0u, 0u, 0u);
+        PROF_MARK(4);
+        if (!more) {
+            PROF_FLUSH(1);
+            break;
+        }
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            cur[u] = nxt[u];
+            nxt[u] = nn[u];
+        }
+        c = cn;
+        par ^= 1u;
+    }
+}
+}  // namespace five
 
 // ------------------------------------------------------------------------------------------------
 // Proportional-lane staged encode (contiguous layout, output slot = in_off: the wire / bench layout).
@@ -2814,6 +3114,8 @@ __global__ void literal_fix_kernel(LitArgs A) {
 //   encode staged:        16 waves/WG, 3.5 KiB in + out per wave          [~114 KiB, 1 WG/CU]
 //   encode staged (long):  8 waves/WG, 8 KiB in + out per wave            [~130 KiB, 1 WG/CU]
 //   encode direct:         4 waves/WG                                      [2 KiB]
+//   encode sorted:         4 waves/WG, 256 strings a chunk, 16 KiB in + out [39.1 KiB, 4 WG/CU]
+//   encode sorted (small): the same with 13 KiB in + out, <= 96 VGPRs       [30.3 KiB, 5 WG/CU]
 // The variant is picked from the mean bytes per string (in_size / n).
 // ------------------------------------------------------------------------------------------------
 // (measured shapes, kept for the record: stream kernel waves / window dwords / output bytes per lane, c3 /
@@ -2822,6 +3124,15 @@ __global__ void literal_fix_kernel(LitArgs A) {
 #ifndef HHUFF_ENCO_NS  // length-sorted encode chunks: strings per chunk, stage bytes (64 B a string: 4 per CU)
 #define HHUFF_ENCO_NS 256
 #define HHUFF_ENCO_CH 16384
+#endif
+// Batches with a mean string of at most HHUFF_ENCO_SMALL_MEAN bytes take the small stage: 256 x 48 = 12,288
+// B and the spread of a chunk's lengths fit 13,312 (U[24,72]: mean span 12,305, sd 227), five workgroups
+// share a CU's LDS, and a chunk over the stage goes to the per-thread path as with any stage.  (0: never.)
+#ifndef HHUFF_ENCO_SMALL_MEAN
+#define HHUFF_ENCO_SMALL_MEAN 48
+#endif
+#ifndef HHUFF_ENCO_SMALL_CH
+#define HHUFF_ENCO_SMALL_CH 13312
 #endif
 #ifndef HHUFF_DECT  // stream decode: waves per block, window dwords, output bytes per lane
 // 8 waves of 20-dword windows (the most the LDS holds beside the window table at these windows): against the
@@ -2846,6 +3157,7 @@ constexpr int kDecSWaves = 16, kEncSWaves = 16;
 #define DEC_T decode_stream_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT, HHUFF_DECT_SEG>
 #define ENC_S encode_staged_kernel<kEncSWaves, 3584, false>
 #define ENC_O encode_sorted_kernel<kEncOStr, HHUFF_ENCO_CH, HHUFF_ENCO_SPT>
+#define ENC_OS five::encode_sorted_kernel<kEncOStr, HHUFF_ENCO_SMALL_CH, HHUFF_ENCO_SPT>
 #define ENC_L encode_staged_kernel<8, 8192, false>
 #define ENC_SP encode_staged_kernel<kEncSWaves, 3584, true>
 #define ENC_LP encode_staged_kernel<8, 8192, true>
@@ -2862,7 +3174,7 @@ constexpr int kDecSWaves = 16, kEncSWaves = 16;
 #endif
 
 enum Variant { kDecS, kDecL, kDecD, kEncS, kEncL, kEncD, kFlatD, kEncP, kFlatP, kDecT, kDecSP, kDecLP, kEncSP, kEncLP,
-               kEncO, kNumVariants };
+               kEncO, kEncOS, kNumVariants };
 
 static const void* variant_fn(int v) {
     switch (v) {
@@ -2876,6 +3188,7 @@ static const void* variant_fn(int v) {
         case kDecT: return (const void*)DEC_T;
         case kEncS: return (const void*)ENC_S;
         case kEncO: return (const void*)ENC_O;
+        case kEncOS: return (const void*)ENC_OS;
         case kEncL: return (const void*)ENC_L;
         case kFlatD: return (const void*)FLAT_D;
         case kEncP: return (const void*)ENC_P;
@@ -2894,7 +3207,8 @@ static int variant_threads(int v) {
         case kDecLP: return 384;
         case kEncL:
         case kEncLP: return 512;
-        case kEncO: return kEncOThreads;
+        case kEncO:
+        case kEncOS: return kEncOThreads;
         case kEncP: return 1024;
         case kFlatP: return FLAT_P_THREADS;
         default: return 256;
@@ -3057,6 +3371,11 @@ static int pick_encode(uint64_t in_size, uint32_t n) {
     if (mean <= 52) return kEncS;
     if (mean <= 120) return kEncL;
     return kEncD;
+}
+// Contiguous short-string batches: the sorted encoder with the stage that the mean string fills (the choice
+// sets the speed only: a chunk whose span exceeds its stage is encoded a string a thread, with the same results)
+static int pick_sorted(uint64_t in_size, uint32_t n) {
+    return HHUFF_ENCO_SMALL_MEAN != 0 && n && in_size / n <= (uint64_t)HHUFF_ENCO_SMALL_MEAN ? kEncOS : kEncO;
 }
 
 // Staged / stream prices of each device (select_verdict).  The launch path only reads them: the fitted
@@ -3364,7 +3683,7 @@ hipError_t launch_encode(const uint8_t* in, uint64_t in_size, const uint32_t* in
         return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipSuccess;
     }
     int v = pick_encode(in_size, n);
-    if (v == kEncS && in_len == nullptr && out_off == nullptr) v = kEncO;
+    if (v == kEncS && in_len == nullptr && out_off == nullptr) v = pick_sorted(in_size, n);
     const int grid = grid_for(v, current_device(), n);
     const bool defer = v != kEncD && in_len == nullptr && out_off == nullptr && defer_edges(n);
     if (defer) {
@@ -3374,12 +3693,23 @@ hipError_t launch_encode(const uint8_t* in, uint64_t in_size, const uint32_t* in
     switch (v) {
         case kEncS: hipLaunchKernelGGL(ENC_S, dim3(grid), dim3(kEncSWaves * 64), 0, stream, A); break;
         case kEncO: hipLaunchKernelGGL(ENC_O, dim3(grid), dim3(kEncOThreads), 0, stream, A); break;
+        case kEncOS: hipLaunchKernelGGL(ENC_OS, dim3(grid), dim3(kEncOThreads), 0, stream, A); break;
         case kEncL: hipLaunchKernelGGL(ENC_L, dim3(grid), dim3(512), 0, stream, A); break;
         default: hipLaunchKernelGGL(ENC_D, dim3(grid), dim3(256), 0, stream, A); break;
     }
     // the sorted encoder writes two records per chunk of kEncOStr strings, the tile kernels two per 64
-    const uint64_t recs = v == kEncO ? 2 * (((uint64_t)n + kEncOStr - 1) / kEncOStr) : 0;
+    const uint64_t recs = v == kEncO || v == kEncOS ? 2 * (((uint64_t)n + kEncOStr - 1) / kEncOStr) : 0;
     return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipGetLastError();
+}
+
+// Debug query (tests only): the resident workgroups a CU of the sorted encoder that launch_encode picks for a
+// contiguous batch of n strings in in_size bytes on the current device; 0 where it picks another kernel.
+int debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n) {
+    if (n == 0 || use_pl_encode(in_size, n) || pick_encode(in_size, n) != kEncS) return 0;
+    const int v = pick_sorted(in_size, n);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, variant_fn(v), variant_threads(v), 0) != hipSuccess) return -1;
+    return per_cu;
 }
 
 
@@ -4350,6 +4680,10 @@ hipError_t pool_trim() {
 int grid_size(int device, int which) { return grid_for(which == 0 ? kDecS : kEncS, device, 0xFFFFFFFFu); }
 
 }  // namespace hhuff
+
+extern "C" __attribute__((visibility("default"))) int hhuff_debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n) {
+    return hhuff::debug_encode_blocks_per_cu(in_size, n);
+}
 
 #ifdef HHUFF_PROFILE
 namespace hhuff {

@@ -694,6 +694,11 @@ uint32_t hhuff_set_edge_defer_min(uint32_t n);
 /* Return the memory the library's stream-ordered pool on the caller's current device keeps between calls
  * (batch workspaces, edge records) to the driver.  Synchronises the device first.  HHUFF_OK or an error. */
 int hhuff_pool_trim(void);
+/* Debug query for the tests: the resident workgroups per compute unit of the length-sorted encode kernel that
+ * hhuff_encode_batch would launch on the caller's current device for a contiguous batch of `n` strings in
+ * `in_size` bytes (the kernel has two stage sizes, picked from in_size / n).  0 where another kernel would run;
+ * negative on a runtime error. */
+int hhuff_debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n);
 
 #ifdef __cplusplus
 }

@@ -1723,4 +1723,6 @@ static_assert(kEncOStr == HHUFF_ENCO_NS && kEncOThreads > 0, "the product's cons
 #define kEncOThreads kEncIThreads
 #undef ENC_O
 #define ENC_O encode_inplace_kernel<HHUFF_ENCI_NS, HHUFF_ENCI_CH, HHUFF_ENCI_SPT>
+#undef ENC_OS  // (the small-stage choice of the sorted encoder: the same kernel here)
+#define ENC_OS ENC_O
 #endif
