@@ -319,6 +319,10 @@ HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, 
         arg_fail("header_table_size must not exceed 65536");
         return HHUFF_RES_EINVAL;
     }
+    if (flags & ~(HHUFF_QENC_CONTINUE | HHUFF_QENC_SET_CAPACITY | HHUFF_QENC_EVICT)) {
+        arg_fail("unknown HHUFF_QENC_* flag");
+        return HHUFF_RES_EINVAL;
+    }
     if (nconn == 0) return HHUFF_OK;
     if (!conn_first || !scratch || !enc_out || !enc_out_off || !enc_out_len || !dec_status || !dec_consumed ||
         (nres && (!res || !stream_id || !out || !out_off || !out_len || !header_len || !rstatus || !rflags)) ||

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "hhuff_enc.h"
+#include "hhuff_qtable.h"
 
 namespace hhuff {
 namespace {
@@ -407,19 +408,20 @@ constexpr uint32_t kSiStatic = 1u << 7, kSiExact = 1u << 8, kSiDc = 1u << 9, kSi
 // encoder-stream instruction of an insert (bits 0-1; the name reference above)
 constexpr uint32_t kInsNone = 0, kInsStatic = 1, kInsDynamic = 2, kInsLiteral = 3;
 
+// Without HHUFF_QENC_EVICT: entries 1 .. count in slots 0 .. count - 1, evicted stays 0.  With it: the live
+// entries evicted + 1 .. count in a ring (hhuff_qtable.h), bit 1 of `failed` marks the session as evicting, and
+// an inflight record's last word is the section's smallest reference with `blocking` in bit 31.
 struct QsState {
-    uint32_t count, used;      // entries 1 .. count (never evicted), their bytes with the 32 per entry
+    uint32_t count, used;      // the inserts so far; the live entries' bytes with the 32 per entry
     uint32_t lkr;              // largest_known_received
     uint32_t num_blocked, ninflight, failed;
-    uint32_t str_used, pad;
-};
-struct QsEntry {
-    uint32_t noff, nl, vl, nh, vh, pad0, pad1, pad2;  // name at str + noff, value behind it
+    uint32_t str_used, evicted;
 };
 struct QsInflight {
     uint64_t sid;
     uint32_t largest, blocking;
 };
+constexpr uint32_t kQsEvicting = 2u;  // in QsState::failed
 static_assert(sizeof(QsState) == 32 && sizeof(QsEntry) == 32 && sizeof(QsInflight) == 16, "scratch records");
 
 __host__ __device__ inline uint64_t qs_conn_scratch(uint32_t H, uint32_t M) {
@@ -448,6 +450,7 @@ struct QsConn {
     QsInflight* inf;
     uint8_t* str;
     uint32_t cap;
+    uint32_t slots, imin;  // evicting: the ring's size; the smallest reference of any inflight section
 };
 struct QsField {
     const uint8_t *n, *v;
@@ -455,6 +458,7 @@ struct QsField {
 };
 struct QsSection {
     uint32_t base, largest, pos, enc, mode;  // mode 2: with an encoder buffer, 1: without, 0: no encoder at all
+    uint32_t smallest;                       // evicting: the smallest index referenced so far
 };
 
 // h2o_hpack_decode_int (lib/http2/hpack.c:52-83) through decode_int (qpack.c:215-220): 0, 1 incomplete, 2 overflow
@@ -476,6 +480,7 @@ __device__ int qs_decode_int(const uint8_t* b, uint32_t n, uint32_t& p, uint32_t
 }
 
 // h2o_qpack_encoder_handle_input (qpack.c:963-1005): `consumed` = the bytes of the instructions taken
+template <bool EV>
 __device__ int32_t qs_handle_input(QsConn& t, const uint8_t* b, uint32_t n, uint32_t& consumed) {
     uint32_t p = 0;
     while (p < n) {
@@ -493,7 +498,7 @@ __device__ int32_t qs_handle_input(QsConn& t, const uint8_t* b, uint32_t n, uint
             for (uint32_t k = 0; k < t.s.ninflight; ++k) {
                 const QsInflight e = t.inf[k];
                 if (e.sid == v) {
-                    t.s.num_blocked -= e.blocking;
+                    t.s.num_blocked -= EV ? e.blocking >> 31 : e.blocking;
                 } else {
                     if (w != k) t.inf[w] = e;
                     ++w;
@@ -506,7 +511,7 @@ __device__ int32_t qs_handle_input(QsConn& t, const uint8_t* b, uint32_t n, uint
             if (k == t.s.ninflight) return HHUFF_QPK_DECODER_STREAM;
             const QsInflight e = t.inf[k];
             if (t.s.lkr < e.largest) t.s.lkr = e.largest;
-            t.s.num_blocked -= e.blocking;
+            t.s.num_blocked -= EV ? e.blocking >> 31 : e.blocking;
             for (; k + 1 < t.s.ninflight; ++k) t.inf[k] = t.inf[k + 1];  // entry by entry (:928 moves bytes)
             --t.s.ninflight;
         }
@@ -515,11 +520,16 @@ __device__ int32_t qs_handle_input(QsConn& t, const uint8_t* b, uint32_t n, uint
 }
 
 // lookup_dynamic (qpack.c:1007-1037): newest to oldest, the first exact match, else the newest name match
+template <bool EV>
 __device__ uint32_t qs_lookup(const QsConn& t, const QsField& F, bool acked_only, bool& exact) {
     uint32_t found = 0;
     exact = false;
-    for (uint32_t i = acked_only ? t.s.lkr : t.s.count; i >= 1; --i) {
-        const QsEntry e = t.ent[i - 1];
+    uint32_t i = EV ? qt_scan_top(t.s.count, t.s.lkr, acked_only) : acked_only ? t.s.lkr : t.s.count;
+    const uint32_t low = EV ? t.s.evicted : 0u;
+    uint32_t slot = EV && i > low ? qt_slot(i, t.slots) : 0u;
+    for (; i > low; --i) {
+        const QsEntry e = t.ent[EV ? slot : i - 1];
+        if (EV) slot = qt_prev(slot, t.slots);
         if (e.nl != F.nl || e.nh != F.nh || !bytes_eq(t.str + e.noff, F.n, F.nl)) continue;
         if (e.vl == F.vl && e.vh == F.vh && bytes_eq(t.str + e.noff + e.nl, F.v, F.vl)) {
             exact = true;
@@ -530,8 +540,10 @@ __device__ uint32_t qs_lookup(const QsConn& t, const QsField& F, bool acked_only
     return found;
 }
 
+template <bool EV>
 __device__ __forceinline__ uint32_t qs_dyn_indexed(QsSection& S, uint32_t i, uint32_t& len) {  // flatten_dynamic_indexed
     if (i > S.largest) S.largest = i;
+    if (EV && i < S.smallest) S.smallest = i;
     if (i <= S.base) {
         len = int_len(S.base - i, 6);
         return kSDyn | (S.base - i) << kSIdxShift;
@@ -541,6 +553,7 @@ __device__ __forceinline__ uint32_t qs_dyn_indexed(QsSection& S, uint32_t i, uin
 }
 
 // do_flatten_header (qpack.c:1148-1213): the field's code and length; an insert's instruction and length
+template <bool EV>
 __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t& len, uint32_t& ins, uint32_t& ins_len) {
     const bool has_s = (F.info & kSiStatic) != 0, dc = (F.info & kSiDc) != 0;
     const uint32_t sidx = F.info & 0x7Fu;
@@ -552,10 +565,26 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
         return code;
     }
     bool dexact = false;
-    const uint32_t dyn = S.mode ? qs_lookup(t, F, S.mode == 1, dexact) : 0u;
-    if (dyn && dexact) return qs_dyn_indexed(S, dyn, len);
-    if ((F.info & kSiLtr) && S.mode == 2 && ((!has_s && !dyn) || F.vl >= 8) &&
-        (uint64_t)F.nl + F.vl + 32u <= (uint64_t)(t.cap - t.s.used)) {
+    const uint32_t dyn = S.mode ? qs_lookup<EV>(t, F, S.mode == 1, dexact) : 0u;
+    if (dyn && dexact) return qs_dyn_indexed<EV>(S, dyn, len);
+    bool fits = (F.info & kSiLtr) && S.mode == 2 && ((!has_s && !dyn) || F.vl >= 8);
+    uint32_t slot = t.s.count;
+    if (!EV) {
+        fits = fits && (uint64_t)F.nl + F.vl + 32u <= (uint64_t)(t.cap - t.s.used);
+    } else if (fits) {  // the oldest entries below every pin make the room, or the field is not inserted
+        uint32_t pin = min(t.imin, S.smallest), used = 0;
+        if (!has_s && dyn && dyn < pin) pin = dyn;  // the entry the instruction names
+        const uint32_t ev = qt_evict_prefix(t.ent, t.slots, t.cap, t.s.used, t.s.evicted, t.s.count, pin,
+                                            (uint64_t)F.nl + F.vl + 32u, used);
+        fits = ev != kQtNoInsert;
+        if (fits) {
+            t.s.evicted = ev;
+            t.s.used = used;
+            t.s.str_used = qt_place(t.str, t.cap, t.ent, t.slots, ev, t.s.count, t.s.str_used, F.nl + F.vl);
+            slot = qt_slot(t.s.count + 1u, t.slots);
+        }
+    }
+    if (fits) {
         if (has_s) {
             ins = kInsStatic | sidx << 2;
             ins_len = int_len(sidx, 6);
@@ -570,11 +599,11 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
         uint8_t* d = t.str + t.s.str_used;
         for (uint32_t k = 0; k < F.nl; ++k) d[k] = F.n[k];
         for (uint32_t k = 0; k < F.vl; ++k) d[F.nl + k] = F.v[k];
-        t.ent[t.s.count] = QsEntry{t.s.str_used, F.nl, F.vl, F.nh, F.vh, 0u, 0u, 0u};
+        t.ent[slot] = QsEntry{t.s.str_used, F.nl, F.vl, F.nh, F.vh, 0u, 0u, 0u};
         ++t.s.count;
         t.s.used += F.nl + F.vl + 32u;
         t.s.str_used += F.nl + F.vl;
-        return qs_dyn_indexed(S, t.s.count, len);
+        return qs_dyn_indexed<EV>(S, t.s.count, len);
     }
     const uint32_t dcb = dc ? kSDc : 0u;
     if (has_s) {
@@ -588,6 +617,7 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
     }
     const uint32_t vlen = q_str_len(F.vl, F.vb, 7, dc);  // flatten_dynamic_nameref
     if (dyn > S.largest) S.largest = dyn;
+    if (EV && dyn < S.smallest) S.smallest = dyn;
     if (dyn <= S.base) {
         len = int_len(S.base - dyn, 4) + vlen;
         return kSDynRef | dcb | (S.base - dyn) << kSIdxShift;
@@ -614,10 +644,11 @@ struct QsNames {
 
 // One section: prepare_flatten and the fields of h2o_qpack_flatten_response / _request in their order.
 // enc0 = the connection's encoder-stream bytes before this section.
+template <bool EV>
 __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_response_t& R, uint32_t r, uint32_t mode,
                                 uint64_t enc0, const QsNames& N, QsSection& S, QsOwn& O) {
     const QseCall& C = A.c;
-    S = QsSection{t.s.count, 0u, 0u, 0u, mode};
+    S = QsSection{t.s.count, 0u, 0u, 0u, mode, ~0u};
     O = QsOwn{{kOpSkip, kOpSkip, kOpSkip, kOpSkip}, kInsNone, 0u, 0u, false};
     const bool request = (R.flags & HHUFF_QRES_REQUEST) != 0;
     uint32_t len, ins, ins_len;
@@ -632,12 +663,12 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
             hash_bits_lane(dg, F.vl, e_enc_nbits, F.vh, F.vb);
             F.info = 24u | kSiStatic;
         }
-        O.code[0] = qs_field(t, S, F, len, ins, ins_len);
+        O.code[0] = qs_field<EV>(t, S, F, len, ins, ins_len);
         S.pos += len;
         if ((R.flags & HHUFF_RES_SERVER) && C.server_len != 0) {
             const uint4 rc = A.rec[C.nhdr];
             const QsField G{e_server, C.in + C.server_off, 6u, C.server_len, rc.x, rc.y, rc.z, rc.w, A.info[C.nhdr]};
-            O.code[1] = qs_field(t, S, G, len, ins, ins_len);
+            O.code[1] = qs_field<EV>(t, S, G, len, ins, ins_len);
             S.pos += len;
             O.sins = ins;
             O.sins_at = S.enc;
@@ -651,7 +682,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
                 G.vl = qs_decimal(R.content_length, dg);
                 hash_bits_lane(dg, G.vl, e_enc_nbits, G.vh, G.vb);
             }
-            O.code[2] = qs_field(t, S, G, len, ins, ins_len);
+            O.code[2] = qs_field<EV>(t, S, G, len, ins, ins_len);
             S.pos += len;
         }
     }
@@ -665,7 +696,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
         const hhuff_hpack_header_t H = C.hdr[h];
         const uint4 rc = A.rec[h];
         const QsField F{C.in + H.name_off, C.in + H.value_off, H.name_len, H.value_len, rc.x, rc.y, rc.z, rc.w, info};
-        const uint32_t code = qs_field(t, S, F, len, ins, ins_len);
+        const uint32_t code = qs_field<EV>(t, S, F, len, ins, ins_len);
         A.op[h] = make_uint4(S.pos, r, code, 0u);
         const uint64_t at = enc0 + S.enc;
         A.ins[h] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), ins, 0u);
@@ -676,7 +707,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
         QsField F{q_dfid_name, C.in + R.dfid_off, 16u, R.dfid_len, N.dfid, 0u, 0u, 0u, 0u};
         hash_bits_lane(q_dfid_name, 16u, e_enc_nbits, F.nh, F.nb);
         hash_bits_lane(F.v, F.vl, e_enc_nbits, F.vh, F.vb);
-        O.code[3] = qs_field(t, S, F, len, ins, ins_len);
+        O.code[3] = qs_field<EV>(t, S, F, len, ins, ins_len);
         O.df_len = len;
         S.pos += len;
     }
@@ -715,7 +746,18 @@ __global__ __launch_bounds__(256) void qse_prep_kernel(QseArgs A) {
     }
 }
 
-// the walk: one lane per connection -- its decoder stream, then its responses in order
+namespace {
+// hhuff_qpack_session_response_bound (include/hhuff.h) of one response, on the device
+__device__ __forceinline__ uint64_t qs_response_bound(uint64_t name_value_bytes, uint32_t nhdr, uint32_t server_len,
+                                                      uint32_t dfid_len) {
+    return 9u + 2u + 8u + 23u + 26u + (uint64_t)dfid_len + (server_len ? 12ull + server_len : 0ull) + 21ull * nhdr +
+           name_value_bytes + 8u;
+}
+}  // namespace
+
+// the walk: one lane per connection -- its decoder stream, then its responses in order.  EV: the session evicts
+// (HHUFF_QENC_EVICT); the other instantiation is the table that only grows.
+template <bool EV>
 __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     const QseCall& C = A.c;
     const uint64_t c = (uint64_t)blockIdx.x * 64u + threadIdx.x;
@@ -727,20 +769,29 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     t.s = QsState{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     const bool fresh = !(C.flags & HHUFF_QENC_CONTINUE);
     if (!fresh) t.s = *ts;
+    // a session is evicting or it is not: the other kind of call touches nothing of it
+    const bool wrong = !fresh && ((t.s.failed & kQsEvicting) != 0) != EV;
+    t.s.failed &= 1u;
     t.ent = reinterpret_cast<QsEntry*>(scr + sizeof(QsState));
     t.inf = reinterpret_cast<QsInflight*>(scr + sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry));
     t.str = scr + sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry) + (uint64_t)M * sizeof(QsInflight);
     t.cap = H;
+    t.slots = qt_slots(H);
+    t.imin = ~0u;
 
     int32_t dst = 0;
     uint32_t consumed = 0;
-    if (t.s.failed) {
+    if (wrong) {
+        dst = HHUFF_RES_EINVAL;
+    } else if (t.s.failed) {
         dst = HHUFF_QPK_SKIPPED;
     } else if (C.dec_off != nullptr) {
         const uint32_t off = C.dec_off[c], len = C.dec_len[c];
-        dst = (uint64_t)off + len > C.in_size ? HHUFF_RES_EINVAL : qs_handle_input(t, C.in + off, len, consumed);
+        dst = (uint64_t)off + len > C.in_size ? HHUFF_RES_EINVAL : qs_handle_input<EV>(t, C.in + off, len, consumed);
         if (dst != 0) t.s.failed = 1u;
     }
+    if (EV && !wrong)
+        for (uint32_t k = 0; k < t.s.ninflight; ++k) t.imin = min(t.imin, t.inf[k].blocking & 0x7FFFFFFFu);
     C.dec_status[c] = dst;
     C.dec_consumed[c] = consumed;
 
@@ -768,7 +819,9 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
         int32_t st = 0;
         uint32_t rf = 0, body = 0;
         uint64_t total = 0;
-        if (t.s.failed) {
+        if (wrong) {
+            st = HHUFF_RES_EINVAL;
+        } else if (t.s.failed) {
             st = HHUFF_RES_SKIPPED;
         } else if (nospace) {
             st = HHUFF_RES_SPACE;
@@ -779,15 +832,63 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
             if ((uint64_t)R.hdr_first + R.nhdr > C.nhdr || limit < base || (server && (A.info[C.nhdr] & kSiBad)) ||
                 ((R.flags & HHUFF_QRES_DATAGRAM) && (uint64_t)R.dfid_off + R.dfid_len > C.in_size)) {
                 st = HHUFF_RES_EINVAL;
+            } else if (EV) {
+                // every refusal comes before the section touches the table: eviction cannot be undone
+                const uint32_t h0 = R.hdr_first, h1 = R.hdr_first + R.nhdr;
+                bool bad = false;
+                uint64_t nv = 0, ibound = server ? 26ull + C.server_len : 0ull;
+                for (uint32_t h = h0; h < h1 && !bad; ++h) {
+                    const uint32_t info = A.info[h];
+                    const hhuff_hpack_header_t Hd = C.hdr[h];
+                    bad = (info & kSiBad) != 0;
+                    nv += (uint64_t)Hd.name_len + Hd.value_len;
+                    if (info & kSiLtr) ibound += 20ull + Hd.name_len + Hd.value_len;
+                }
+                const uint64_t bound = qs_response_bound(nv, R.nhdr, server ? C.server_len : 0u,
+                                                         (R.flags & HHUFF_QRES_DATAGRAM) ? R.dfid_len : 0u);
+                uint32_t mode = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < C.max_blocked ? 2u : 1u;
+                if (t.s.ninflight >= M) mode = 0u;  // no slot: as with no encoder at all
+                if (bad) {
+                    st = HHUFF_RES_EINVAL;
+                } else if (limit - base < bound || bound > 0xFFFFFFFFull || (mode == 2u && room - enc_len < ibound)) {
+                    st = HHUFF_RES_SPACE;
+                } else {
+                    rf = mode == 0u ? 1u : 0u;
+                    QsSection S;
+                    QsOwn O;
+                    qs_walk_section<EV>(A, t, R, r, mode, ebase + enc_len, N, S, O);
+                    uint32_t ric = 0, delta = 0, plen = 2, largest = S.largest;
+                    bool blocking = false;
+                    if (largest != 0) {  // finalize_flatten (:1263-1298), the Required Insert Count wrapped (RFC 9204 4.5.1.1)
+                        if (largest < t.s.lkr) largest = t.s.lkr;
+                        blocking = largest > t.s.lkr;
+                        ric = largest % (2u * t.slots) + 1u;
+                        delta = largest <= S.base ? S.base - largest : 0x80000000u | (largest - S.base - 1u);
+                        plen = int_len(ric, 8) + int_len(delta & 0x7FFFFFFFu, 7);
+                        t.inf[t.s.ninflight] = QsInflight{C.stream_id[r], largest, S.smallest | (blocking ? 0x80000000u : 0u)};
+                        ++t.s.ninflight;
+                        t.s.num_blocked += blocking ? 1u : 0u;
+                        t.imin = min(t.imin, S.smallest);
+                    }
+                    const uint64_t body64 = (uint64_t)plen + S.pos;
+                    total = 1u + q_varint_len(body64) + body64;
+                    body = (uint32_t)body64;
+                    const uint64_t sat = ebase + enc_len + O.sins_at;
+                    A.plan[4 * (uint64_t)r] = make_uint4((uint32_t)base, (uint32_t)(base >> 32), body, (uint32_t)total);
+                    A.plan[4 * (uint64_t)r + 1] = make_uint4(ric, delta, 1u + q_varint_len(body64) + plen, O.df_len);
+                    A.plan[4 * (uint64_t)r + 2] = make_uint4(O.code[0], O.code[1], O.code[2], O.code[3]);
+                    A.plan[4 * (uint64_t)r + 3] = make_uint4((uint32_t)sat, (uint32_t)(sat >> 32), O.sins, 0u);
+                    enc_len += S.enc;
+                }
             } else {
                 const QsState snap = t.s;
                 const bool buf = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < C.max_blocked;
                 QsSection S;
                 QsOwn O;
-                qs_walk_section(A, t, R, r, buf ? 2u : 1u, ebase + enc_len, N, S, O);
+                qs_walk_section<EV>(A, t, R, r, buf ? 2u : 1u, ebase + enc_len, N, S, O);
                 if (!O.bad && S.largest != 0 && t.s.ninflight >= M) {  // no slot: as with no encoder at all
                     t.s = snap;
-                    qs_walk_section(A, t, R, r, 0u, ebase + enc_len, N, S, O);
+                    qs_walk_section<EV>(A, t, R, r, 0u, ebase + enc_len, N, S, O);
                     rf = 1u;
                 }
                 uint32_t ric = 0, delta = 0, plen = 2, largest = S.largest;
@@ -833,7 +934,8 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
         C.rstatus[r] = st;
         C.rflags[r] = (uint8_t)rf;
     }
-    *ts = t.s;
+    if (EV) t.s.failed |= kQsEvicting;
+    if (!wrong) *ts = t.s;
     C.enc_out_len[c] = (uint32_t)enc_len;
 }
 
@@ -1001,7 +1103,11 @@ hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream) {
     const uint32_t ge = (uint32_t)std::min<uint64_t>((2ull * nhdr + nres + nconn + 255u) / 256u, 16384ull);
     HHUFF_LAUNCH(e, qse_prep_kernel, gp, 256, stream, A);
     if (e == hipSuccess) e = launch_long_bits(true, call.in, call.hdr, nhdr, call.server_off, call.server_len, A.rec, A.lw, stream);
-    HHUFF_LAUNCH(e, qse_walk_kernel, (nconn + 63u) / 64u, 64, stream, A);
+    if (call.flags & HHUFF_QENC_EVICT) {
+        HHUFF_LAUNCH(e, qse_walk_kernel<true>, (nconn + 63u) / 64u, 64, stream, A);
+    } else {
+        HHUFF_LAUNCH(e, qse_walk_kernel<false>, (nconn + 63u) / 64u, 64, stream, A);
+    }
     HHUFF_LAUNCH(e, qse_emit_kernel, ge, 256, stream, A);
     if (e == hipSuccess) e = launch_long_payload(call.in, A.lw, stream);
     const hipError_t f = hipFreeAsync(ws, stream);

@@ -531,7 +531,7 @@ int hhuff_qpack_flatten_responses(const uint8_t *in, uint64_t in_size, const hhu
  *        2. the responses conn_first[c] .. conn_first[c+1]-1 in order (records, headers, own fields, frame
  *           header, out regions and header_len[] as for hhuff_qpack_flatten_responses), response r on the
  *           request stream stream_id[r].
- *      Table: 1-based, never evicts; an insert needs name_len + value_len + 32 <= header_table_size - used;
+ *      Table: 1-based, never evicts (but see HHUFF_QENC_EVICT below); an insert needs name_len + value_len + 32 <= header_table_size - used;
  *      base_index = the insert count at the section's start.  The section has an encoder buffer only without
  *      HHUFF_QRES_NO_ENCODER_STREAM and with num_blocked < max_blocked at its start (:1250).
  *      Lookup (lookup_dynamic): newest to oldest, the first entry with the name and value, else the newest with
@@ -571,12 +571,51 @@ int hhuff_qpack_flatten_responses(const uint8_t *in, uint64_t in_size, const hhu
  *      returns HHUFF_RES_EINVAL).  nres = conn_first[nconn] (host copy).  in_size < 2^32.  Asynchronous on `stream`: a prep pass
  *      (one lane per header), the walk (one lane per connection: decides, writes no output byte), the emit pass
  *      (one lane per field, insert and response head).  Stream-ordered pool workspace of 124 bytes per header,
- *      112 per response and 16 per connection. */
+ *      112 per response and 16 per connection.
+ *
+ *      HHUFF_QENC_EVICT: the table evicts entries no section still needs (a fourth deliberate difference: h2o's
+ *      encoder "never triggers eviction", :1168-1170).  Without the flag everything above holds unchanged.  A
+ *      session is evicting or it is not: a call with HHUFF_QENC_CONTINUE whose flag differs from the one the
+ *      scratch was started with is refused with HHUFF_RES_EINVAL.  The mode lives in the scratch, on the device,
+ *      and the call is asynchronous, so the refusal is reported per connection: dec_status[c] and every
+ *      rstatus[r] of the connection are HHUFF_RES_EINVAL, nothing is written and the scratch stays as it was.
+ *      Under the flag:
+ *        1. Indices.  Entries keep absolute 1-based indices; count = the total number of inserts, evicted = the
+ *           number of entries gone, the live entries are evicted+1 .. count and `used` counts them alone.
+ *           lookup_dynamic scans from count (without an encoder buffer: from min(largest_known_received, count))
+ *           down to evicted+1.  The Insert Count Increment check still uses count.
+ *        2. Pins.  Entry i is pinned while an inflight section's smallest reference is <= i, or the section
+ *           being flattened has already referenced an index <= i, or i is the dynamic entry this insert's
+ *           instruction names (Insert With Name Reference, dynamic).  Section Acknowledgment and Stream
+ *           Cancellation release a section's pins, nothing more.
+ *        3. Insert rule.  The condition above with another room test; need = name_len + value_len + 32.  The
+ *           insert happens iff need <= header_table_size and the oldest live entries, taken in order and
+ *           stopping at the first pinned one, free enough that used + need <= header_table_size.  Then exactly
+ *           the shortest such prefix is evicted and the entry inserted; else nothing is evicted and the field
+ *           falls through to the static name reference, dynamic name reference or literal form.  No Duplicate
+ *           instruction, no draining heuristic.  A connection stops inserting at count == 2^31 - 1.
+ *        4. Section prefix.  Required Insert Count = (largest_ref mod (2 * (header_table_size / 32))) + 1
+ *           (RFC 9204 4.5.1.1; the bytes above while largest_ref < 2 * (header_table_size / 32)); the delta base
+ *           is unchanged.
+ *        5. Transactions.  A failed response writes nothing and changes no state; since an eviction cannot be
+ *           undone, every refusal is decided before the section touches the table.  HHUFF_RES_EINVAL: a string
+ *           past in_size or a bad range, as above.  HHUFF_RES_SPACE: the response's region is smaller than
+ *           hhuff_qpack_session_response_bound() of it (its headers' name and value bytes, its nhdr, server_len
+ *           when it sends the server name, dfid_len when it has HHUFF_QRES_DATAGRAM) or that bound is 2^32 or
+ *           more; or the section has an encoder buffer and the room left in the connection's encoder-stream
+ *           region is smaller than its insert bound: the sum of 20 + name_len + value_len over its headers with
+ *           HHUFF_HDR_TOKEN | HHUFF_HDR_LIKELY_TO_REPEAT and over the server name when it sends it.  A section
+ *           that starts with the inflight list full (max_inflight entries) is flattened as with no encoder at
+ *           all, rflags[r] |= 1, whether or not it would have needed a slot.
+ *           hhuff_qpack_session_enc_bound() always fits a connection's encoder-stream region for a step;
+ *           "header_table_size + 4 bytes always fit" holds only without the flag.
+ *        6. hhuff_qpack_enc_scratch_size() is the same with and without the flag. */
 #define HHUFF_HDR_LIKELY_TO_REPEAT 4u    /* h2o_token_t.flags.likely_to_repeat of the header's token (caller-supplied,
                                             like HHUFF_HDR_TOKEN; meaningful only with HHUFF_HDR_TOKEN) */
 #define HHUFF_QRES_NO_ENCODER_STREAM 32u /* this response is flattened with encoder_buf == NULL */
 #define HHUFF_QENC_CONTINUE 1u
 #define HHUFF_QENC_SET_CAPACITY 2u       /* 0x20 | 5-bit-prefix int header_table_size */
+#define HHUFF_QENC_EVICT 4u              /* the table evicts entries no section still needs (contract above) */
 #define HHUFF_QPK_DECODER_STREAM 0x30202 /* H2O_HTTP3_ERROR_QPACK_DECODER_STREAM */
 /* the longer section prefix and dynamic indices at up to 2,048 entries */
 static inline uint64_t hhuff_qpack_session_response_bound(uint64_t name_value_bytes, uint32_t nhdr, uint32_t server_len,
@@ -584,6 +623,14 @@ static inline uint64_t hhuff_qpack_session_response_bound(uint64_t name_value_by
 {
     uint64_t bound = hhuff_qpack_response_bound(name_value_bytes, nhdr, server_len, dfid_len);
     return bound + 8;
+}
+/* a connection's encoder-stream bytes of one step with HHUFF_QENC_EVICT: Set Dynamic Table Capacity, the insert
+ * bounds of its headers with HHUFF_HDR_TOKEN | HHUFF_HDR_LIKELY_TO_REPEAT and of the server name per response */
+static inline uint64_t hhuff_qpack_session_enc_bound(uint64_t name_value_bytes_of_ltr_headers, uint32_t n_ltr_headers,
+                                                     uint32_t server_len, uint32_t nres_of_conn)
+{
+    return 4 + name_value_bytes_of_ltr_headers + 20ull * n_ltr_headers +
+           (server_len ? (uint64_t)nres_of_conn * (26ull + server_len) : 0);
 }
 uint64_t hhuff_qpack_enc_scratch_size(uint32_t nconn, uint32_t header_table_size, uint32_t max_inflight);
 int hhuff_qpack_flatten_sessions(const uint8_t *in, uint64_t in_size, const hhuff_hpack_header_t *hdr, uint32_t nhdr,

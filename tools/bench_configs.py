@@ -349,36 +349,78 @@ def qpenc_line(torch, codec, nconn=65536):
             "responses_per_s": round(nres / (t * 1e-3), 1), "fields_per_s": round(nhdr / (t * 1e-3), 1)}
 
 
-def qsess_line(torch, codec, nconn=65536):
+def qsess_line(torch, codec, nconn=65536, evict=False):
     """QPACK encoder sessions (hhuff_qpack_flatten_sessions): hpenc_line's 4,096 synthetic connections cut into two
     steps (hpenc_synth.to_qpack_sessions), tiled to nconn.  fresh: the first step on new sessions, with Set
     Dynamic Table Capacity.  continued: the second step with HHUFF_QENC_CONTINUE and no decoder input, every call
     on the sessions as the call before left them -- after the warm-up the tables hold the step's strings, so this
     is the steady state of connections that repeat themselves: dynamic references, no inserts.  max_inflight and
-    max_blocked are set so that the unacknowledged sections of all timed calls fit."""
+    max_blocked are set so that the unacknowledged sections of all timed calls fit.
+    evict (qsessev): the same batch with HHUFF_QENC_EVICT and a table of 256 bytes, which holds three or four of a
+    connection's strings, so it turns over in every call.  Every call's decoder stream cancels all of the
+    connection's streams (never an error, unlike an acknowledgment of a section that did not become inflight):
+    the sections of the call before release their pins, and the inflight lists stay short.  The server name is
+    left out: an entry that every section refers to first becomes the oldest and stays (no Duplicate
+    instruction), and then nothing turns over; and the calls alternate between the batch and a copy whose
+    likely-to-repeat values have every digit turned on by one, so that a call's values are not the ones the call
+    before left in the table."""
     from h2o_amd import hpenc_synth as HE
 
     k = max(1, nconn // 4096)
-    steps = [_qpack_tiled(s, k, HE.qpack_session_out_offsets)
-             for s in HE.to_qpack_sessions(HE.make_session(4096, seed=13)[0], 2, seed=13)]
+    H = 256 if evict else 4096
+    base = HE.to_qpack_sessions(HE.make_session(4096, seed=13)[0], 2, seed=13)
+    steps = [_qpack_tiled(s, k, HE.qpack_session_out_offsets) for s in base]
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()  # noqa: E731
-    d, hd = dev(steps[0]["data"]), dev(steps[0]["hdr"].view(np.uint8))  # the steps share data and hdr
+    data = steps[0]["data"]  # the steps share data and hdr
     nc, nhdr = int(steps[0]["conn_first"].size - 1), int(steps[0]["hdr"].size)
-    kw = dict(header_table_size=4096, max_blocked=1 << 20, max_inflight=128, server_off=steps[0]["server_off"],
-              server_len=steps[0]["server_len"], in_size=int(steps[0]["data"].size))
-    kw["scratch"] = torch.empty(codec.qpack_enc_scratch_size(nc, 4096, 128), dtype=torch.uint8, device="cuda")
-    kw["enc_out_off"] = torch.arange(nc + 1, dtype=torch.int64, device="cuda") * 4112
-    kw["enc_out"] = torch.empty(nc * 4112, dtype=torch.uint8, device="cuda")
-    line = {"config": "qsess", "connections": nc, "fields": nhdr}
+    kw = dict(header_table_size=H, max_blocked=1 << 20, max_inflight=128, server_off=steps[0]["server_off"],
+              server_len=steps[0]["server_len"], in_size=int(data.size))
+    room = 4112
+    if evict:
+        from h2o_amd.hpack_synth import encode_int
+
+        h, ltr = base[0]["hdr"], HE.HDR_TOKEN | HE.HDR_LIKELY_TO_REPEAT
+        cost = np.where((h["flags"] & ltr) == ltr, 20 + h["name_len"].astype(np.int64) + h["value_len"], 0)
+        csum = np.concatenate([[0], np.cumsum(cost)])
+        cancels, per_conn = [], np.zeros(4096, np.int64)
+        for s in base:  # hhuff_qpack_session_enc_bound, the largest of any connection and step
+            first, cf = s["res"]["hdr_first"].astype(np.int64), s["conn_first"].astype(np.int64)
+            rb = np.concatenate([[0], np.cumsum(csum[first + s["res"]["nhdr"]] - csum[first] + 26 + s["server_len"])])
+            per_conn = np.maximum(per_conn, 4 + rb[cf[1:]] - rb[cf[:-1]])
+            cancels.append([b"".join(encode_int(int(x), 6, 0x40) for x in s["stream_id"][cf[c]:cf[c + 1]]) for c in range(4096)])
+        room = (int(per_conn.max()) + 15) // 16 * 16
+        dec = [a + b for a, b in zip(*cancels)]
+        lens = np.array([len(x) for x in dec], np.int64)
+        offs = data.size + np.concatenate([[0], np.cumsum(lens)[:-1]])
+        # every other call sends the values with their digits turned on by one (dates, ages, lengths ...): what a
+        # call finds in the table is the call before's, so its inserts need the room of entries released since
+        turned = data.copy()
+        digit = (turned >= 48) & (turned <= 57)
+        turned[digit] = (turned[digit] - 48 + 1) % 10 + 48
+        data = np.concatenate([data, np.frombuffer(b"".join(dec), np.uint8)])
+        hdr2 = steps[0]["hdr"].copy()
+        hdr2["value_off"] += np.where((hdr2["flags"] & ltr) == ltr, data.size, 0).astype(hdr2["value_off"].dtype)
+        data = np.concatenate([data, turned])
+        kw.update(evict=True, server_len=0, in_size=int(data.size), dec_off=dev(np.tile(offs, k).astype(np.uint32).view(np.int32)),
+                  dec_len=dev(np.tile(lens, k).astype(np.uint32).view(np.int32)))
+    d, hd = dev(data), dev(steps[0]["hdr"].view(np.uint8))
+    hds = [hd, dev(hdr2.view(np.uint8))] if evict else [hd]
+    kw["scratch"] = torch.empty(codec.qpack_enc_scratch_size(nc, H, 128), dtype=torch.uint8, device="cuda")
+    kw["enc_out_off"] = torch.arange(nc + 1, dtype=torch.int64, device="cuda") * room
+    kw["enc_out"] = torch.empty(nc * room, dtype=torch.uint8, device="cuda")
+    line = {"config": "qsessev" if evict else "qsess", "connections": nc, "fields": nhdr}
+    if evict:
+        line["header_table_size"] = H
     for name, q, cont in (("fresh", steps[0], False), ("continued", steps[1], True)):
         rs, cf = dev(q["res"].view(np.uint8)), dev(q["conn_first"].view(np.int32))
         sid, oo = dev(q["stream_id"].view(np.int64)), dev(q["out_off"].view(np.int64))
         nres = int(q["res"].size)
         out = torch.empty(int(q["out_off"][-1]), dtype=torch.uint8, device="cuda")
-        res = {}
+        res = {"calls": 0}
 
         def run():
-            res["r"] = codec.qpack_flatten_sessions(d, hd, rs, cf, nres, sid, oo, out=out, cont=cont,
+            res["calls"] += 1
+            res["r"] = codec.qpack_flatten_sessions(d, hds[res["calls"] % len(hds)], rs, cf, nres, sid, oo, out=out, cont=cont,
                                                     set_capacity=not cont, **kw)
 
         t = timed(torch, run, steps=10, warmup=2)
@@ -460,6 +502,10 @@ def main():
         if cfg.startswith("hpenc"):
             n = int(cfg[5:]) if len(cfg) > 5 else 65536
             print(json.dumps(hpenc_line(torch, codec, n)), flush=True)
+            continue
+        if cfg.startswith("qsessev"):
+            n = int(cfg[7:]) if len(cfg) > 7 else 65536
+            print(json.dumps(qsess_line(torch, codec, n, evict=True)), flush=True)
             continue
         if cfg.startswith("qpenc") or cfg.startswith("qsess"):
             n = int(cfg[5:]) if len(cfg) > 5 else 65536

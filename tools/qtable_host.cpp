@@ -1,0 +1,160 @@
+// The evicting encoder table's operations (h2o_amd/csrc/hhuff_qtable.h: evict-prefix, ring slot, string
+// compaction, lookup bounds) on the host, against list bookkeeping, for AddressSanitizer and
+// UndefinedBehaviorSanitizer.  The ring and the string area are heap blocks of exactly the sizes the device
+// gives them (header_table_size / 32 entries, header_table_size bytes), so a step outside them is reported.
+//
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ih2o_amd/csrc
+//       tools/qtable_host.cpp -o build/qtable_host && build/qtable_host 4000
+//
+// Every sequence: a table size of 64 .. 512, then random sections (references to live entries, inserts with and
+// without a name-reference pin), acknowledgments and cancellations that release the sections' pins.  After
+// every operation the ring is compared with the list: indices, lengths, every string byte, `used`.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <deque>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "hhuff_qtable.h"
+
+using namespace hhuff;
+
+namespace {
+struct Table {
+    uint32_t cap, slots, count = 0, evicted = 0, used = 0, str_used = 0;
+    std::unique_ptr<QsEntry[]> ent;
+    std::unique_ptr<uint8_t[]> str;
+    std::deque<std::string> live;  // the bookkeeping: name + value of entries evicted + 1 .. count
+    std::deque<uint32_t> name_len;
+    explicit Table(uint32_t H) : cap(H), slots(qt_slots(H)), ent(new QsEntry[qt_slots(H)]), str(new uint8_t[H]) {}
+};
+
+#define CHECK(c)                                                       \
+    do {                                                               \
+        if (!(c)) {                                                    \
+            printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c);      \
+            exit(1);                                                   \
+        }                                                              \
+    } while (0)
+
+void compare(const Table& t) {
+    CHECK(t.count - t.evicted == t.live.size() && t.live.size() <= t.slots);
+    uint32_t used = 0, run = 0;
+    for (uint32_t i = t.evicted + 1; i <= t.count; ++i) {
+        const QsEntry& e = t.ent[qt_slot(i, t.slots)];
+        const std::string& s = t.live[i - t.evicted - 1];
+        CHECK(e.nl == t.name_len[i - t.evicted - 1] && e.nl + e.vl == s.size());
+        CHECK((uint64_t)e.noff + s.size() <= t.cap && memcmp(t.str.get() + e.noff, s.data(), s.size()) == 0);
+        if (i > t.evicted + 1) CHECK(e.noff == run);  // one contiguous run in insert order
+        run = e.noff + e.nl + e.vl;
+        used += (uint32_t)s.size() + 32u;
+    }
+    CHECK(used == t.used && t.used <= t.cap);
+    if (!t.live.empty()) CHECK(run == t.str_used);
+}
+
+uint64_t g_compactions = 0;
+
+// -> whether the entry went in; pin = the smallest pinned index (~0u: none)
+bool insert(Table& t, const std::string& name, const std::string& value, uint32_t pin) {
+    const uint64_t need = name.size() + value.size() + 32u;
+    // the list's answer
+    size_t k = 0;
+    uint64_t u = t.used;
+    bool want = need <= t.cap;
+    while (want && u + need > t.cap) {
+        if (k == t.live.size() || t.evicted + k + 1 >= pin) {
+            want = false;
+            break;
+        }
+        u -= t.live[k].size() + 32u;
+        ++k;
+    }
+    uint32_t used_after = 0;
+    const uint32_t ev = qt_evict_prefix(t.ent.get(), t.slots, t.cap, t.used, t.evicted, t.count, pin, need, used_after);
+    CHECK((ev != kQtNoInsert) == want);
+    if (!want) return false;
+    CHECK(ev == t.evicted + k && used_after == u);
+    t.evicted = ev;
+    t.used = used_after;
+    for (; k; --k) t.live.pop_front(), t.name_len.pop_front();
+    const uint32_t len = (uint32_t)(name.size() + value.size());
+    const uint32_t tail = t.str_used;
+    t.str_used = qt_place(t.str.get(), t.cap, t.ent.get(), t.slots, t.evicted, t.count, t.str_used, len);
+    g_compactions += t.str_used != tail ? 1u : 0u;
+    CHECK((uint64_t)t.str_used + len <= t.cap);
+    memcpy(t.str.get() + t.str_used, name.data(), name.size());
+    memcpy(t.str.get() + t.str_used + name.size(), value.data(), value.size());
+    t.ent[qt_slot(t.count + 1u, t.slots)] =
+        QsEntry{t.str_used, (uint32_t)name.size(), (uint32_t)value.size(), 0u, 0u, 0u, 0u, 0u};
+    ++t.count;
+    t.used += len + 32u;
+    t.str_used += len;
+    t.live.push_back(name + value);
+    t.name_len.push_back((uint32_t)name.size());
+    return true;
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+    const int nseq = argc > 1 ? atoi(argv[1]) : 2000;
+    std::mt19937 rng(12345);
+    auto pick = [&](uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rng() % (hi - lo + 1)); };
+    uint64_t inserts = 0, refused = 0, evictions = 0;
+    for (int s = 0; s < nseq; ++s) {
+        Table t(pick(64, 512));
+        std::vector<uint32_t> inflight;  // the sections' smallest references
+        uint32_t lkr = 0;
+        for (int op = 0, nop = (int)pick(20, 200); op < nop; ++op) {
+            const uint32_t kind = pick(0, 9);
+            if (kind < 6) {  // a section: some references, some inserts
+                uint32_t smallest = ~0u;
+                for (uint32_t f = 0, nf = pick(1, 4); f < nf; ++f) {
+                    uint32_t imin = smallest;
+                    for (uint32_t x : inflight) imin = x < imin ? x : imin;
+                    if (pick(0, 2) == 0 && t.count > t.evicted) {  // a reference to a live entry
+                        const uint32_t top = qt_scan_top(t.count, lkr, pick(0, 1) != 0);
+                        CHECK(top <= t.count);
+                        if (top > t.evicted) {
+                            const uint32_t i = pick(t.evicted + 1, top);
+                            (void)t.ent[qt_slot(i, t.slots)].noff;
+                            smallest = i < smallest ? i : smallest;
+                        }
+                        continue;
+                    }
+                    uint32_t pin = imin;
+                    if (pick(0, 3) == 0 && t.count > t.evicted) {  // Insert With Name Reference, dynamic
+                        const uint32_t d = pick(t.evicted + 1, t.count);
+                        pin = d < pin ? d : pin;
+                    }
+                    const std::string name(pick(1, 24), (char)('a' + op % 26)), value(pick(0, t.cap / 2 + 8), (char)('A' + f));
+                    const uint32_t ev0 = t.evicted;
+                    if (insert(t, name, value, pin)) {
+                        ++inserts;
+                        evictions += t.evicted - ev0;
+                        smallest = t.count < smallest ? t.count : smallest;
+                    } else {
+                        ++refused;
+                        CHECK(t.evicted == ev0);
+                    }
+                    compare(t);
+                }
+                if (smallest != ~0u && inflight.size() < 8) inflight.push_back(smallest);
+            } else if (!inflight.empty()) {  // acknowledgment (7, 8: the first; raises lkr) or cancellation (9: any)
+                const size_t k = kind == 9 ? pick(0, (uint32_t)inflight.size() - 1) : 0;
+                if (kind != 9) lkr = t.count;
+                inflight.erase(inflight.begin() + (long)k);
+            }
+            compare(t);
+        }
+    }
+    printf("ok: %d sequences, %llu inserts (%llu entries evicted, %llu compactions), %llu refused\n", nseq,
+           (unsigned long long)inserts, (unsigned long long)evictions, (unsigned long long)g_compactions,
+           (unsigned long long)refused);
+    return 0;
+}
