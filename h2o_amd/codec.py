@@ -536,7 +536,7 @@ def qpack_flatten_responses(data, hdr, res, nres, out_off, server_off=0, server_
 # include/hhuff.h (2g'): QPACK encoder sessions
 HDR_LIKELY_TO_REPEAT = 4
 QRES_NO_ENCODER_STREAM = 32
-QENC_CONTINUE, QENC_SET_CAPACITY, QENC_EVICT = 1, 2, 4
+QENC_CONTINUE, QENC_SET_CAPACITY, QENC_EVICT, QENC_DUP = 1, 2, 4, 8
 QPK_DECODER_STREAM = 0x30202
 QPK_DECOMPRESSION_FAILED = 0x30200
 QPK_SKIPPED, QPK_BLOCKED = -301, -302
@@ -561,7 +561,7 @@ def qpack_enc_scratch_size(nconn, header_table_size=4096, max_inflight=64):
 def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off, dec_off=None, dec_len=None,
                            header_table_size=4096, max_blocked=100, max_inflight=64, server_off=0, server_len=0,
                            enc_out_off=None, in_size=None, out=None, enc_out=None, scratch=None, cont=False,
-                           set_capacity=False, stream=None, evict=False):
+                           set_capacity=False, stream=None, evict=False, dup=False):
     """One step of many QPACK encoder sessions (include/hhuff.h hhuff_qpack_flatten_sessions) on device tensors:
     hdr = uint8 tensor of HPE_HEADER_DTYPE records, res = uint8 tensor of QPE_RESPONSE_DTYPE records, conn_first
     int32 (u32 bits) [nconn + 1], stream_id int64 per response, out_off int64 [nres + 1], dec_off / dec_len int32
@@ -570,7 +570,9 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
     tensors: out, out_len, header_len, rstatus, rflags (per response), enc_out, enc_out_off, enc_out_len,
     dec_status, dec_consumed (per connection) and the scratch holding the sessions (pass it back with cont=True
     for the connections' next step).  evict=True: HHUFF_QENC_EVICT, on every step of a session or on none; give
-    enc_out_off then (qpack_session_enc_bound), since header_table_size + 4 bytes need not hold a step's inserts."""
+    enc_out_off then (qpack_session_enc_bound), since header_table_size + 4 bytes need not hold a step's inserts.
+    dup=True: HHUFF_QENC_DUP, with evict=True only and likewise on every step or on none: entries about to be pinned
+    as the oldest are re-inserted by a Duplicate instruction."""
     import torch
 
     dev = data.device
@@ -590,7 +592,8 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
     ss = qpack_enc_scratch_size(nconn, header_table_size, max_inflight)
     if scratch is None:
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
-    flags = (QENC_CONTINUE if cont else 0) | (QENC_SET_CAPACITY if set_capacity else 0) | (QENC_EVICT if evict else 0)
+    flags = (QENC_CONTINUE if cont else 0) | (QENC_SET_CAPACITY if set_capacity else 0) | (QENC_EVICT if evict else 0) | \
+        (QENC_DUP if dup else 0)
     _check(lib().hhuff_qpack_flatten_sessions(
         _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), _dp(conn_first), nconn, nres, _dp(stream_id),
         _dp(dec_off), _dp(dec_len), header_table_size, max_blocked, max_inflight, server_off, server_len, _dp(out),

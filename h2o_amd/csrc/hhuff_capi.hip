@@ -319,8 +319,12 @@ HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, 
         arg_fail("header_table_size must not exceed 65536");
         return HHUFF_RES_EINVAL;
     }
-    if (flags & ~(HHUFF_QENC_CONTINUE | HHUFF_QENC_SET_CAPACITY | HHUFF_QENC_EVICT)) {
+    if (flags & ~(HHUFF_QENC_CONTINUE | HHUFF_QENC_SET_CAPACITY | HHUFF_QENC_EVICT | HHUFF_QENC_DUP)) {
         arg_fail("unknown HHUFF_QENC_* flag");
+        return HHUFF_RES_EINVAL;
+    }
+    if ((flags & HHUFF_QENC_DUP) && !(flags & HHUFF_QENC_EVICT)) {
+        arg_fail("HHUFF_QENC_DUP needs HHUFF_QENC_EVICT");
         return HHUFF_RES_EINVAL;
     }
     if (nconn == 0) return HHUFF_OK;

@@ -405,12 +405,15 @@ __device__ const uint8_t __attribute__((aligned(16))) q_cl_name[16] = {'c', 'o',
 
 // info word of a prepped header: static index (bits 0-6)
 constexpr uint32_t kSiStatic = 1u << 7, kSiExact = 1u << 8, kSiDc = 1u << 9, kSiLtr = 1u << 10, kSiBad = 1u << 11;
-// encoder-stream instruction of an insert (bits 0-1; the name reference above)
-constexpr uint32_t kInsNone = 0, kInsStatic = 1, kInsDynamic = 2, kInsLiteral = 3;
+// encoder-stream instruction of an insert (bits 0-2; the name reference, or the duplicated entry's relative index,
+// above)
+constexpr uint32_t kInsNone = 0, kInsStatic = 1, kInsDynamic = 2, kInsLiteral = 3, kInsDup = 4;
+constexpr uint32_t kInsMask = 7u, kInsShift = 3;
 
 // Without HHUFF_QENC_EVICT: entries 1 .. count in slots 0 .. count - 1, evicted stays 0.  With it: the live
 // entries evicted + 1 .. count in a ring (hhuff_qtable.h), bit 1 of `failed` marks the session as evicting, and
-// an inflight record's last word is the section's smallest reference with `blocking` in bit 31.
+// an inflight record's last word is the section's smallest reference with `blocking` in bit 31.  With
+// HHUFF_QENC_DUP as well, bit 2 of `failed` marks the session as duplicating.
 struct QsState {
     uint32_t count, used;      // the inserts so far; the live entries' bytes with the 32 per entry
     uint32_t lkr;              // largest_known_received
@@ -421,7 +424,7 @@ struct QsInflight {
     uint64_t sid;
     uint32_t largest, blocking;
 };
-constexpr uint32_t kQsEvicting = 2u;  // in QsState::failed
+constexpr uint32_t kQsEvicting = 2u, kQsDuplicating = 4u;  // in QsState::failed
 static_assert(sizeof(QsState) == 32 && sizeof(QsEntry) == 32 && sizeof(QsInflight) == 16, "scratch records");
 
 __host__ __device__ inline uint64_t qs_conn_scratch(uint32_t H, uint32_t M) {
@@ -435,7 +438,7 @@ struct QseArgs {
     uint4* rec;      // [nhdr + 1] {name hash, value hash, name code bits, value code bits}; item nhdr: server
     uint32_t* info;  // [nhdr + 1]
     uint4* op;       // [nhdr] {place among the section's fields, response, code, 0}
-    uint4* ins;      // [nhdr] {place in enc_out lo, hi, instruction | name reference << 2, 0}
+    uint4* ins;      // [nhdr] {place in enc_out lo, hi, instruction | name reference << 3, 0}
     uint4* plan;     // [4 nres] {base lo, base hi, section length, frame total} {Required Insert Count, delta base |
                      // sign << 31, first field's offset in the frame, datagram-flow-id size} {codes of :status, server,
                      // content-length, datagram-flow-id} {server's insert: place lo, hi, instruction, 0}
@@ -552,8 +555,11 @@ __device__ __forceinline__ uint32_t qs_dyn_indexed(QsSection& S, uint32_t i, uin
     return kSDynPost | (i - S.base - 1u) << kSIdxShift;
 }
 
-// do_flatten_header (qpack.c:1148-1213): the field's code and length; an insert's instruction and length
-template <bool EV>
+// do_flatten_header (qpack.c:1148-1213): the field's code and length; an insert's instruction and length.
+// DUP (HHUFF_QENC_DUP, with EV only): an exact match on a draining entry is duplicated when the room test lets
+// it -- the insert below with the matched entry no pin (the prefix that goes may hold it: the strings come from
+// the field's bytes, never from the entry) and the Duplicate instruction in place of the insert's.
+template <bool EV, bool DUP>
 __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t& len, uint32_t& ins, uint32_t& ins_len) {
     const bool has_s = (F.info & kSiStatic) != 0, dc = (F.info & kSiDc) != 0;
     const uint32_t sidx = F.info & 0x7Fu;
@@ -566,14 +572,18 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
     }
     bool dexact = false;
     const uint32_t dyn = S.mode ? qs_lookup<EV>(t, F, S.mode == 1, dexact) : 0u;
-    if (dyn && dexact) return qs_dyn_indexed<EV>(S, dyn, len);
-    bool fits = (F.info & kSiLtr) && S.mode == 2 && ((!has_s && !dyn) || F.vl >= 8);
+    bool dup = false;
+    if (dyn && dexact) {
+        if (DUP) dup = S.mode == 2 && (F.info & kSiLtr) && qt_draining(t.ent, t.slots, t.cap, t.s.used, t.s.evicted, dyn);
+        if (!dup) return qs_dyn_indexed<EV>(S, dyn, len);
+    }
+    bool fits = dup || ((F.info & kSiLtr) && S.mode == 2 && ((!has_s && !dyn) || F.vl >= 8));
     uint32_t slot = t.s.count;
     if (!EV) {
         fits = fits && (uint64_t)F.nl + F.vl + 32u <= (uint64_t)(t.cap - t.s.used);
     } else if (fits) {  // the oldest entries below every pin make the room, or the field is not inserted
         uint32_t pin = min(t.imin, S.smallest), used = 0;
-        if (!has_s && dyn && dyn < pin) pin = dyn;  // the entry the instruction names
+        if (!dup && !has_s && dyn && dyn < pin) pin = dyn;  // the entry the instruction names
         const uint32_t ev = qt_evict_prefix(t.ent, t.slots, t.cap, t.s.used, t.s.evicted, t.s.count, pin,
                                             (uint64_t)F.nl + F.vl + 32u, used);
         fits = ev != kQtNoInsert;
@@ -585,17 +595,20 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
         }
     }
     if (fits) {
-        if (has_s) {
-            ins = kInsStatic | sidx << 2;
+        if (dup) {  // Duplicate (RFC 9204 4.3.4): relative to the newest entry before this one, no strings
+            ins = kInsDup | (t.s.count - dyn) << kInsShift;
+            ins_len = int_len(t.s.count - dyn, 5);
+        } else if (has_s) {
+            ins = kInsStatic | sidx << kInsShift;
             ins_len = int_len(sidx, 6);
         } else if (dyn) {  // relative to the newest entry (RFC 9204 4.3.2), as the decoder reads it (:336-341)
-            ins = kInsDynamic | (t.s.count - dyn) << 2;
+            ins = kInsDynamic | (t.s.count - dyn) << kInsShift;
             ins_len = int_len(t.s.count - dyn, 6);
         } else {
             ins = kInsLiteral;
             ins_len = q_str_len(F.nl, F.nb, 5, false);
         }
-        ins_len += q_str_len(F.vl, F.vb, 7, false);
+        if (!dup) ins_len += q_str_len(F.vl, F.vb, 7, false);
         uint8_t* d = t.str + t.s.str_used;
         for (uint32_t k = 0; k < F.nl; ++k) d[k] = F.n[k];
         for (uint32_t k = 0; k < F.vl; ++k) d[F.nl + k] = F.v[k];
@@ -605,6 +618,7 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
         t.s.str_used += F.nl + F.vl;
         return qs_dyn_indexed<EV>(S, t.s.count, len);
     }
+    if (dup) return qs_dyn_indexed<EV>(S, dyn, len);  // no room below the pins: the reference, as without the flag
     const uint32_t dcb = dc ? kSDc : 0u;
     if (has_s) {
         const uint32_t code = kSStaticRef | dcb | sidx << kSIdxShift;
@@ -644,7 +658,7 @@ struct QsNames {
 
 // One section: prepare_flatten and the fields of h2o_qpack_flatten_response / _request in their order.
 // enc0 = the connection's encoder-stream bytes before this section.
-template <bool EV>
+template <bool EV, bool DUP>
 __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_response_t& R, uint32_t r, uint32_t mode,
                                 uint64_t enc0, const QsNames& N, QsSection& S, QsOwn& O) {
     const QseCall& C = A.c;
@@ -663,12 +677,12 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
             hash_bits_lane(dg, F.vl, e_enc_nbits, F.vh, F.vb);
             F.info = 24u | kSiStatic;
         }
-        O.code[0] = qs_field<EV>(t, S, F, len, ins, ins_len);
+        O.code[0] = qs_field<EV, DUP>(t, S, F, len, ins, ins_len);
         S.pos += len;
         if ((R.flags & HHUFF_RES_SERVER) && C.server_len != 0) {
             const uint4 rc = A.rec[C.nhdr];
             const QsField G{e_server, C.in + C.server_off, 6u, C.server_len, rc.x, rc.y, rc.z, rc.w, A.info[C.nhdr]};
-            O.code[1] = qs_field<EV>(t, S, G, len, ins, ins_len);
+            O.code[1] = qs_field<EV, DUP>(t, S, G, len, ins, ins_len);
             S.pos += len;
             O.sins = ins;
             O.sins_at = S.enc;
@@ -682,7 +696,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
                 G.vl = qs_decimal(R.content_length, dg);
                 hash_bits_lane(dg, G.vl, e_enc_nbits, G.vh, G.vb);
             }
-            O.code[2] = qs_field<EV>(t, S, G, len, ins, ins_len);
+            O.code[2] = qs_field<EV, DUP>(t, S, G, len, ins, ins_len);
             S.pos += len;
         }
     }
@@ -696,7 +710,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
         const hhuff_hpack_header_t H = C.hdr[h];
         const uint4 rc = A.rec[h];
         const QsField F{C.in + H.name_off, C.in + H.value_off, H.name_len, H.value_len, rc.x, rc.y, rc.z, rc.w, info};
-        const uint32_t code = qs_field<EV>(t, S, F, len, ins, ins_len);
+        const uint32_t code = qs_field<EV, DUP>(t, S, F, len, ins, ins_len);
         A.op[h] = make_uint4(S.pos, r, code, 0u);
         const uint64_t at = enc0 + S.enc;
         A.ins[h] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), ins, 0u);
@@ -707,7 +721,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
         QsField F{q_dfid_name, C.in + R.dfid_off, 16u, R.dfid_len, N.dfid, 0u, 0u, 0u, 0u};
         hash_bits_lane(q_dfid_name, 16u, e_enc_nbits, F.nh, F.nb);
         hash_bits_lane(F.v, F.vl, e_enc_nbits, F.vh, F.vb);
-        O.code[3] = qs_field<EV>(t, S, F, len, ins, ins_len);
+        O.code[3] = qs_field<EV, DUP>(t, S, F, len, ins, ins_len);
         O.df_len = len;
         S.pos += len;
     }
@@ -756,9 +770,11 @@ __device__ __forceinline__ uint64_t qs_response_bound(uint64_t name_value_bytes,
 }  // namespace
 
 // the walk: one lane per connection -- its decoder stream, then its responses in order.  EV: the session evicts
-// (HHUFF_QENC_EVICT); the other instantiation is the table that only grows.
-template <bool EV>
+// (HHUFF_QENC_EVICT), DUP: it also duplicates draining entries (HHUFF_QENC_DUP, with EV only); <false, false> is
+// the table that only grows.
+template <bool EV, bool DUP>
 __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
+    static_assert(EV || !DUP, "HHUFF_QENC_DUP is a mode of the evicting table");
     const QseCall& C = A.c;
     const uint64_t c = (uint64_t)blockIdx.x * 64u + threadIdx.x;
     if (c >= C.nconn) return;
@@ -769,8 +785,9 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     t.s = QsState{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     const bool fresh = !(C.flags & HHUFF_QENC_CONTINUE);
     if (!fresh) t.s = *ts;
-    // a session is evicting or it is not: the other kind of call touches nothing of it
-    const bool wrong = !fresh && ((t.s.failed & kQsEvicting) != 0) != EV;
+    // a session is evicting or it is not, duplicating or not: another kind of call touches nothing of it
+    constexpr uint32_t kMode = (EV ? kQsEvicting : 0u) | (DUP ? kQsDuplicating : 0u);
+    const bool wrong = !fresh && (t.s.failed & (kQsEvicting | kQsDuplicating)) != kMode;
     t.s.failed &= 1u;
     t.ent = reinterpret_cast<QsEntry*>(scr + sizeof(QsState));
     t.inf = reinterpret_cast<QsInflight*>(scr + sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry));
@@ -856,7 +873,7 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
                     rf = mode == 0u ? 1u : 0u;
                     QsSection S;
                     QsOwn O;
-                    qs_walk_section<EV>(A, t, R, r, mode, ebase + enc_len, N, S, O);
+                    qs_walk_section<EV, DUP>(A, t, R, r, mode, ebase + enc_len, N, S, O);
                     uint32_t ric = 0, delta = 0, plen = 2, largest = S.largest;
                     bool blocking = false;
                     if (largest != 0) {  // finalize_flatten (:1263-1298), the Required Insert Count wrapped (RFC 9204 4.5.1.1)
@@ -885,10 +902,10 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
                 const bool buf = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < C.max_blocked;
                 QsSection S;
                 QsOwn O;
-                qs_walk_section<EV>(A, t, R, r, buf ? 2u : 1u, ebase + enc_len, N, S, O);
+                qs_walk_section<EV, DUP>(A, t, R, r, buf ? 2u : 1u, ebase + enc_len, N, S, O);
                 if (!O.bad && S.largest != 0 && t.s.ninflight >= M) {  // no slot: as with no encoder at all
                     t.s = snap;
-                    qs_walk_section<EV>(A, t, R, r, 0u, ebase + enc_len, N, S, O);
+                    qs_walk_section<EV, DUP>(A, t, R, r, 0u, ebase + enc_len, N, S, O);
                     rf = 1u;
                 }
                 uint32_t ric = 0, delta = 0, plen = 2, largest = S.largest;
@@ -934,19 +951,21 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
         C.rstatus[r] = st;
         C.rflags[r] = (uint8_t)rf;
     }
-    if (EV) t.s.failed |= kQsEvicting;
+    t.s.failed |= kMode;
     if (!wrong) *ts = t.s;
     C.enc_out_len[c] = (uint32_t)enc_len;
 }
 
 namespace {
-// an insert's instruction (emit_insert_with_nameref / _without_nameref, qpack.c:1068-1086)
+// an insert's instruction (emit_insert_with_nameref / _without_nameref, qpack.c:1068-1086); Duplicate is one
+// prefix integer and no strings
 __device__ __forceinline__ void qs_emit_insert(RegSink& sink, const GlobalSource& nsrc, const GlobalSource& vsrc, uint32_t ins,
                                                uint32_t noff, uint32_t nl, uint32_t voff, uint32_t vl, uint32_t nbits,
                                                uint32_t vbits, const uint2* enc, const LongWork& L) {
-    switch (ins & 3u) {
-        case kInsStatic: sink_int(sink, 0xc0u, ins >> 2, 6); break;
-        case kInsDynamic: sink_int(sink, 0x80u, ins >> 2, 6); break;
+    switch (ins & kInsMask) {
+        case kInsDup: sink_int(sink, 0u, ins >> kInsShift, 5); return;
+        case kInsStatic: sink_int(sink, 0xc0u, ins >> kInsShift, 6); break;
+        case kInsDynamic: sink_int(sink, 0x80u, ins >> kInsShift, 6); break;
         default: q_sink_string(sink, nsrc, 0x40u, noff, nl, nbits, 5, false, enc, L); break;
     }
     q_sink_string(sink, vsrc, 0u, voff, vl, vbits, 7, false, enc, L);
@@ -975,7 +994,7 @@ __global__ __launch_bounds__(256) void qse_emit_kernel(QseArgs A) {
             RegSink sink;
             if (insert) {
                 const uint4 I = A.ins[h];
-                if ((I.z & 3u) == kInsNone) continue;
+                if ((I.z & kInsMask) == kInsNone) continue;
                 sink.init(C.enc_out + ((uint64_t)I.y << 32 | I.x));
                 qs_emit_insert(sink, src, src, I.z, Hd.name_off, Hd.name_len, Hd.value_off, Hd.value_len, rc.z, rc.w, s_enc, A.lw);
             } else {
@@ -1019,7 +1038,7 @@ __global__ __launch_bounds__(256) void qse_emit_kernel(QseArgs A) {
                           code_bits(C.in + R.dfid_off, R.dfid_len), s_enc, A.lw);
             s2.finish();
         }
-        if ((p3.z & 3u) != kInsNone) {  // the server name's insert
+        if ((p3.z & kInsMask) != kInsNone) {  // the server name's insert or duplication
             RegSink s3;
             s3.init(C.enc_out + ((uint64_t)p3.y << 32 | p3.x));
             qs_emit_insert(s3, src, src, p3.z, 0u, 0u, C.server_off, C.server_len, 0u, sr.w, s_enc, A.lw);
@@ -1103,10 +1122,12 @@ hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream) {
     const uint32_t ge = (uint32_t)std::min<uint64_t>((2ull * nhdr + nres + nconn + 255u) / 256u, 16384ull);
     HHUFF_LAUNCH(e, qse_prep_kernel, gp, 256, stream, A);
     if (e == hipSuccess) e = launch_long_bits(true, call.in, call.hdr, nhdr, call.server_off, call.server_len, A.rec, A.lw, stream);
-    if (call.flags & HHUFF_QENC_EVICT) {
-        HHUFF_LAUNCH(e, qse_walk_kernel<true>, (nconn + 63u) / 64u, 64, stream, A);
+    if (call.flags & HHUFF_QENC_DUP) {  // (only with HHUFF_QENC_EVICT: the C entry refuses it alone)
+        HHUFF_LAUNCH(e, (qse_walk_kernel<true, true>), (nconn + 63u) / 64u, 64, stream, A);
+    } else if (call.flags & HHUFF_QENC_EVICT) {
+        HHUFF_LAUNCH(e, (qse_walk_kernel<true, false>), (nconn + 63u) / 64u, 64, stream, A);
     } else {
-        HHUFF_LAUNCH(e, qse_walk_kernel<false>, (nconn + 63u) / 64u, 64, stream, A);
+        HHUFF_LAUNCH(e, (qse_walk_kernel<false, false>), (nconn + 63u) / 64u, 64, stream, A);
     }
     HHUFF_LAUNCH(e, qse_emit_kernel, ge, 256, stream, A);
     if (e == hipSuccess) e = launch_long_payload(call.in, A.lw, stream);

@@ -1,6 +1,6 @@
 // The evicting encoder table of hhuff_qpack_flatten_sessions with HHUFF_QENC_EVICT (include/hhuff.h (2g')):
 // the operations on a connection's entry ring and string area, for the device (hhuff_qpenc.hip) and for the
-// host (tools/qtable_host.cpp replays random insert / ack / cancel sequences against list bookkeeping under
+// host (tools/qtable_host.cpp replays random insert / duplicate / ack / cancel sequences against list bookkeeping under
 // AddressSanitizer and UndefinedBehaviorSanitizer).  Entries keep absolute 1-based indices; the live ones are
 // evicted + 1 .. count, entry i in slot (i - 1) mod slots of a ring of header_table_size / 32 slots; their
 // strings lie in insert order as one contiguous run of the string area.
@@ -52,6 +52,15 @@ HHUFF_QT_HD uint32_t qt_evict_prefix(const QsEntry* ent, uint32_t slots, uint32_
     }
     used_after = u;
     return e;
+}
+
+// HHUFF_QENC_DUP's draining test of the live entry i (evicted < i <= count): headroom = the free bytes and the
+// bytes of the live entries older than i, what inserts can still take before i has to go; i is draining when
+// that is under a quarter of the table.  The strings are one run in insert order, so the older entries' bytes
+// are the distance between the two names and 32 an entry: no walk.
+HHUFF_QT_HD bool qt_draining(const QsEntry* ent, uint32_t slots, uint32_t cap, uint32_t used, uint32_t evicted, uint32_t i) {
+    const uint32_t run = ent[qt_slot(i, slots)].noff - ent[qt_slot(evicted + 1u, slots)].noff;
+    return (cap - used) + run + 32u * (i - evicted - 1u) < cap / 4u;
 }
 
 // String compaction: the live run [noff of entry evicted + 1, str_used) moves to offset 0 and the live entries'

@@ -593,7 +593,8 @@ int hhuff_qpack_flatten_responses(const uint8_t *in, uint64_t in_size, const hhu
  *           stopping at the first pinned one, free enough that used + need <= header_table_size.  Then exactly
  *           the shortest such prefix is evicted and the entry inserted; else nothing is evicted and the field
  *           falls through to the static name reference, dynamic name reference or literal form.  No Duplicate
- *           instruction, no draining heuristic.  A connection stops inserting at count == 2^31 - 1.
+ *           instruction, no draining heuristic (but see point 7).  A connection stops inserting at
+ *           count == 2^31 - 1.
  *        4. Section prefix.  Required Insert Count = (largest_ref mod (2 * (header_table_size / 32))) + 1
  *           (RFC 9204 4.5.1.1; the bytes above while largest_ref < 2 * (header_table_size / 32)); the delta base
  *           is unchanged.
@@ -609,13 +610,44 @@ int hhuff_qpack_flatten_responses(const uint8_t *in, uint64_t in_size, const hhu
  *           all, rflags[r] |= 1, whether or not it would have needed a slot.
  *           hhuff_qpack_session_enc_bound() always fits a connection's encoder-stream region for a step;
  *           "header_table_size + 4 bytes always fit" holds only without the flag.
- *        6. hhuff_qpack_enc_scratch_size() is the same with and without the flag. */
+ *        6. hhuff_qpack_enc_scratch_size() is the same with and without the flag.
+ *        7. HHUFF_QENC_DUP (opt-in, valid only together with HHUFF_QENC_EVICT: alone it is known on the host and
+ *           the call returns HHUFF_RES_EINVAL; without it every byte, status and scratch word is as above).  An
+ *           entry that every section keeps referring to ends up the oldest, is pinned whenever an insert asks
+ *           for room, and the table stops turning over behind it; with the flag such an entry is re-inserted by
+ *           a Duplicate instruction while it can still be evicted.
+ *           Draining.  For a live entry i, older(i) = the sum of name_len + value_len + 32 over the live entries
+ *           evicted+1 .. i-1, and headroom(i) = (header_table_size - used) + older(i): the bytes of inserts the
+ *           table can still take before i has to go.  Entry i is draining iff headroom(i) <
+ *           header_table_size / 4 (integer division).  The quarter is a constant of this contract, like
+ *           max_inflight's meaning, not a tuned number: no entry of a table with room for another quarter is
+ *           draining, and in a full table the oldest quarter by bytes is.
+ *           Rule.  At "an exact dynamic match -> dynamic indexed" of the per-field order: when the section has
+ *           an encoder buffer, the field is likely to repeat (the test an insert uses: HHUFF_HDR_TOKEN |
+ *           HHUFF_HDR_LIKELY_TO_REPEAT, or the server name) and the matched entry i is draining, point 3's room
+ *           test runs with need = name_len + value_len + 32.  Its pins are the inflight sections' smallest
+ *           references and the smallest reference of the section being flattened so far; i itself is NOT a
+ *           pin, so the evicted prefix may include the source (RFC 9204 3.2.2: the decoder resolves the index
+ *           before it evicts).  If the test succeeds, the encoder stream gets Duplicate (000 pattern, 5-bit
+ *           prefix) with the relative index count - i, count taken before the insert; exactly that prefix is
+ *           evicted; a new entry with the field's name and value is inserted; the field is the post-base
+ *           indexed reference to the new entry, as after an insert.  Otherwise nothing changes: the indexed
+ *           reference to i.
+ *           Unchanged.  Lookup is newest first, so later fields and sections find the duplicate, which is not
+ *           draining.  A name-only match still inserts with a dynamic name reference and pins that entry; it is
+ *           never duplicated.  The wrapped Required Insert Count, the transactions of point 5, both bound
+ *           helpers (a Duplicate is at most 3 bytes, under the 20 + name_len + value_len counted for the same
+ *           field) and hhuff_qpack_enc_scratch_size() are as above.
+ *           Mode.  A session is duplicating for its whole life: a call with HHUFF_QENC_CONTINUE whose
+ *           HHUFF_QENC_DUP bit differs from the one the scratch was started with is refused per connection
+ *           exactly as the HHUFF_QENC_EVICT mismatch is. */
 #define HHUFF_HDR_LIKELY_TO_REPEAT 4u    /* h2o_token_t.flags.likely_to_repeat of the header's token (caller-supplied,
                                             like HHUFF_HDR_TOKEN; meaningful only with HHUFF_HDR_TOKEN) */
 #define HHUFF_QRES_NO_ENCODER_STREAM 32u /* this response is flattened with encoder_buf == NULL */
 #define HHUFF_QENC_CONTINUE 1u
 #define HHUFF_QENC_SET_CAPACITY 2u       /* 0x20 | 5-bit-prefix int header_table_size */
 #define HHUFF_QENC_EVICT 4u              /* the table evicts entries no section still needs (contract above) */
+#define HHUFF_QENC_DUP 8u                /* with HHUFF_QENC_EVICT only: draining entries are duplicated (point 7) */
 #define HHUFF_QPK_DECODER_STREAM 0x30202 /* H2O_HTTP3_ERROR_QPACK_DECODER_STREAM */
 /* the longer section prefix and dynamic indices at up to 2,048 entries */
 static inline uint64_t hhuff_qpack_session_response_bound(uint64_t name_value_bytes, uint32_t nhdr, uint32_t server_len,

@@ -349,7 +349,7 @@ def qpenc_line(torch, codec, nconn=65536):
             "responses_per_s": round(nres / (t * 1e-3), 1), "fields_per_s": round(nhdr / (t * 1e-3), 1)}
 
 
-def qsess_line(torch, codec, nconn=65536, evict=False):
+def qsess_line(torch, codec, nconn=65536, evict=False, dup=False):
     """QPACK encoder sessions (hhuff_qpack_flatten_sessions): hpenc_line's 4,096 synthetic connections cut into two
     steps (hpenc_synth.to_qpack_sessions), tiled to nconn.  fresh: the first step on new sessions, with Set
     Dynamic Table Capacity.  continued: the second step with HHUFF_QENC_CONTINUE and no decoder input, every call
@@ -360,10 +360,13 @@ def qsess_line(torch, codec, nconn=65536, evict=False):
     connection's strings, so it turns over in every call.  Every call's decoder stream cancels all of the
     connection's streams (never an error, unlike an acknowledgment of a section that did not become inflight):
     the sections of the call before release their pins, and the inflight lists stay short.  The server name is
-    left out: an entry that every section refers to first becomes the oldest and stays (no Duplicate
-    instruction), and then nothing turns over; and the calls alternate between the batch and a copy whose
+    left out: an entry that every section refers to first becomes the oldest and stays (HHUFF_QENC_EVICT alone
+    sends no Duplicate instruction), and then nothing turns over; and the calls alternate between the batch and a copy whose
     likely-to-repeat values have every digit turned on by one, so that a call's values are not the ones the call
-    before left in the table."""
+    before left in the table.
+    dup (qsessdup): qsessev's batch with the server name kept and HHUFF_QENC_DUP beside HHUFF_QENC_EVICT: the entry
+    every section refers to is duplicated when it drains, and the table goes on turning over behind it.  Another
+    batch than qsessev's (a field more per response), so the two lines are not an A/B."""
     from h2o_amd import hpenc_synth as HE
 
     k = max(1, nconn // 4096)
@@ -401,14 +404,15 @@ def qsess_line(torch, codec, nconn=65536, evict=False):
         hdr2 = steps[0]["hdr"].copy()
         hdr2["value_off"] += np.where((hdr2["flags"] & ltr) == ltr, data.size, 0).astype(hdr2["value_off"].dtype)
         data = np.concatenate([data, turned])
-        kw.update(evict=True, server_len=0, in_size=int(data.size), dec_off=dev(np.tile(offs, k).astype(np.uint32).view(np.int32)),
+        kw.update(evict=True, dup=dup, server_len=kw["server_len"] if dup else 0, in_size=int(data.size),
+                  dec_off=dev(np.tile(offs, k).astype(np.uint32).view(np.int32)),
                   dec_len=dev(np.tile(lens, k).astype(np.uint32).view(np.int32)))
     d, hd = dev(data), dev(steps[0]["hdr"].view(np.uint8))
     hds = [hd, dev(hdr2.view(np.uint8))] if evict else [hd]
     kw["scratch"] = torch.empty(codec.qpack_enc_scratch_size(nc, H, 128), dtype=torch.uint8, device="cuda")
     kw["enc_out_off"] = torch.arange(nc + 1, dtype=torch.int64, device="cuda") * room
     kw["enc_out"] = torch.empty(nc * room, dtype=torch.uint8, device="cuda")
-    line = {"config": "qsessev" if evict else "qsess", "connections": nc, "fields": nhdr}
+    line = {"config": "qsessdup" if dup else "qsessev" if evict else "qsess", "connections": nc, "fields": nhdr}
     if evict:
         line["header_table_size"] = H
     for name, q, cont in (("fresh", steps[0], False), ("continued", steps[1], True)):
@@ -506,6 +510,10 @@ def main():
         if cfg.startswith("qsessev"):
             n = int(cfg[7:]) if len(cfg) > 7 else 65536
             print(json.dumps(qsess_line(torch, codec, n, evict=True)), flush=True)
+            continue
+        if cfg.startswith("qsessdup"):
+            n = int(cfg[8:]) if len(cfg) > 8 else 65536
+            print(json.dumps(qsess_line(torch, codec, n, evict=True, dup=True)), flush=True)
             continue
         if cfg.startswith("qpenc") or cfg.startswith("qsess"):
             n = int(cfg[5:]) if len(cfg) > 5 else 65536

@@ -1,5 +1,5 @@
 // The evicting encoder table's operations (h2o_amd/csrc/hhuff_qtable.h: evict-prefix, ring slot, string
-// compaction, lookup bounds) on the host, against list bookkeeping, for AddressSanitizer and
+// compaction, lookup bounds, the draining test) on the host, against list bookkeeping, for AddressSanitizer and
 // UndefinedBehaviorSanitizer.  The ring and the string area are heap blocks of exactly the sizes the device
 // gives them (header_table_size / 32 entries, header_table_size bytes), so a step outside them is reported.
 //
@@ -7,8 +7,11 @@
 //       tools/qtable_host.cpp -o build/qtable_host && build/qtable_host 4000
 //
 // Every sequence: a table size of 64 .. 512, then random sections (references to live entries, inserts with and
-// without a name-reference pin), acknowledgments and cancellations that release the sections' pins.  After
-// every operation the ring is compared with the list: indices, lengths, every string byte, `used`.
+// without a name-reference pin, duplications of draining entries -- HHUFF_QENC_DUP: the matched entry is no pin,
+// so the prefix that goes may hold it, and the new entry's strings come from a copy of the field, as the device
+// takes them from its input), acknowledgments and cancellations that release the sections' pins.  After every
+// operation the ring is compared with the list: indices, lengths, every string byte, `used`.  The run fails
+// unless it saw a duplication that evicted its own source and one whose compaction wrote over the source.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -59,6 +62,16 @@ void compare(const Table& t) {
 }
 
 uint64_t g_compactions = 0;
+bool g_compacted = false;  // the last insert compacted the string area
+
+// the list's draining test: the free bytes and the bytes of the entries older than i, against a quarter
+bool draining(const Table& t, uint32_t i) {
+    uint64_t headroom = t.cap - t.used;
+    for (uint32_t k = 0; k + 1 < i - t.evicted; ++k) headroom += t.live[k].size() + 32u;
+    const bool want = headroom < t.cap / 4u;
+    CHECK(qt_draining(t.ent.get(), t.slots, t.cap, t.used, t.evicted, i) == want);
+    return want;
+}
 
 // -> whether the entry went in; pin = the smallest pinned index (~0u: none)
 bool insert(Table& t, const std::string& name, const std::string& value, uint32_t pin) {
@@ -86,7 +99,8 @@ bool insert(Table& t, const std::string& name, const std::string& value, uint32_
     const uint32_t len = (uint32_t)(name.size() + value.size());
     const uint32_t tail = t.str_used;
     t.str_used = qt_place(t.str.get(), t.cap, t.ent.get(), t.slots, t.evicted, t.count, t.str_used, len);
-    g_compactions += t.str_used != tail ? 1u : 0u;
+    g_compacted = t.str_used != tail;
+    g_compactions += g_compacted ? 1u : 0u;
     CHECK((uint64_t)t.str_used + len <= t.cap);
     memcpy(t.str.get() + t.str_used, name.data(), name.size());
     memcpy(t.str.get() + t.str_used + name.size(), value.data(), value.size());
@@ -106,6 +120,7 @@ int main(int argc, char** argv) {
     std::mt19937 rng(12345);
     auto pick = [&](uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rng() % (hi - lo + 1)); };
     uint64_t inserts = 0, refused = 0, evictions = 0;
+    uint64_t dups = 0, dup_refused = 0, dup_self = 0, dup_over = 0, not_draining = 0;
     for (int s = 0; s < nseq; ++s) {
         Table t(pick(64, 512));
         std::vector<uint32_t> inflight;  // the sections' smallest references
@@ -125,6 +140,33 @@ int main(int argc, char** argv) {
                             (void)t.ent[qt_slot(i, t.slots)].noff;
                             smallest = i < smallest ? i : smallest;
                         }
+                        continue;
+                    }
+                    if (pick(0, 3) == 0 && t.count > t.evicted) {  // an exact match: a duplication when it drains
+                        const uint32_t i = pick(t.evicted + 1, t.count);
+                        if (!draining(t, i)) {
+                            ++not_draining;
+                            smallest = i < smallest ? i : smallest;
+                            continue;
+                        }
+                        const uint32_t k = i - t.evicted - 1, ev0 = t.evicted;
+                        const std::string name = t.live[k].substr(0, t.name_len[k]), value = t.live[k].substr(t.name_len[k]);
+                        const uint32_t src_off = t.ent[qt_slot(i, t.slots)].noff;
+                        if (insert(t, name, value, imin)) {  // i itself is no pin
+                            ++dups;
+                            evictions += t.evicted - ev0;
+                            if (t.evicted >= i) {
+                                ++dup_self;
+                                // the compacted run starts at 0: it covers the source's old place when it reaches it
+                                if (g_compacted && t.str_used > src_off) ++dup_over;
+                            }
+                            smallest = t.count < smallest ? t.count : smallest;
+                        } else {
+                            ++dup_refused;
+                            CHECK(t.evicted == ev0);
+                            smallest = i < smallest ? i : smallest;
+                        }
+                        compare(t);
                         continue;
                     }
                     uint32_t pin = imin;
@@ -153,8 +195,11 @@ int main(int argc, char** argv) {
             compare(t);
         }
     }
-    printf("ok: %d sequences, %llu inserts (%llu entries evicted, %llu compactions), %llu refused\n", nseq,
-           (unsigned long long)inserts, (unsigned long long)evictions, (unsigned long long)g_compactions,
-           (unsigned long long)refused);
+    CHECK(dup_self > 0 && dup_over > 0);
+    printf("ok: %d sequences, %llu inserts (%llu entries evicted, %llu compactions), %llu refused; %llu duplications "
+           "(%llu evicted their source, %llu of those compacted over it), %llu refused, %llu matches not draining\n",
+           nseq, (unsigned long long)inserts, (unsigned long long)evictions, (unsigned long long)g_compactions,
+           (unsigned long long)refused, (unsigned long long)dups, (unsigned long long)dup_self,
+           (unsigned long long)dup_over, (unsigned long long)dup_refused, (unsigned long long)not_draining);
     return 0;
 }
