@@ -764,13 +764,17 @@ __device__ __forceinline__ void place_bits(O obase, uint32_t tb, uint64_t c, uin
     if (sh + n > 64u) or_word(obase, a + 2u, (uint32_t)t << (32u - sh));  // sh > 0 here
 }
 
-template <class O>
+// DEFER_LONG: a dword with a code longer than 16 bits is not placed on the spot (two 64-bit placements that the
+// whole wave issues for one lane's sake) but noted in `pend`; the bit count and the verdict are the same, and the
+// caller places the noted strings that were kept in a walk of their own (encode_chunk_v2).
+template <class O, bool DEFER_LONG = false>
 struct EncV2 {
     const uint2* enc;
     O obase;  // the MSB-first output stage: LDS byte address or word pointer (see or_word)
     uint32_t tb;     // next stage bit
     uint32_t tlim;   // stage bit at which the string fails (~0: no limit)
     bool live, fail;
+    uint32_t pend;   // DEFER_LONG: non-zero once a dword of this lane was left for the second walk
     // four table entries of one input dword; `on`: this lane has these bytes
     __device__ __forceinline__ void put4(uint2 e0, uint2 e1, uint2 e2, uint2 e3, bool on) {
         const uint32_t n01 = e0.y + e1.y, n23 = e2.y + e3.y, n = n01 + n23;
@@ -779,7 +783,9 @@ struct EncV2 {
         fail = fail || over;
         live = live && !over;
         const bool put = on && live;
-        if (__any(put && lng)) {  // a code longer than 16 bits: two placements of 64-bit pairs
+        if constexpr (DEFER_LONG) {
+            pend |= put && lng ? 1u : 0u;
+        } else if (__any(put && lng)) {  // a code longer than 16 bits: two placements of 64-bit pairs
             if (put && lng) {
                 place_bits(obase, tb, (uint64_t)e0.x << e1.y | e1.x, n01);
                 place_bits(obase, tb + n01, (uint64_t)e2.x << e3.y | e3.x, n23);
@@ -802,7 +808,9 @@ struct EncV2 {
         // verdict is tb >= tlim after the loop; -4 % c4 encode against masks carried from dword to dword)
         const uint32_t nm = n & onm;
         const uint32_t putm = onm & (uint32_t)((int32_t)(tb + nm - tlim) >> 31);
-        if (__builtin_amdgcn_ballot_w64((putm & lngm) != 0u) != 0) {
+        if constexpr (DEFER_LONG) {
+            pend |= putm & lngm;
+        } else if (__builtin_amdgcn_ballot_w64((putm & lngm) != 0u) != 0) {
             if (putm & lngm) {
                 place_bits(obase, tb, (uint64_t)e0.x << e1.y | e1.x, n01);
                 place_bits(obase, tb + n01, (uint64_t)e2.x << e3.y | e3.x, n23);
@@ -836,7 +844,14 @@ struct EncV2 {
 // U: whole dwords a trip of the bulk loop (1 or 2; the loop's ballots keep the compiler from unrolling it)
 // T257: `enc` has 257 entries (entry 256 zero) instead of 512 (256..511 zero): the head and tail words are
 // masked, so a byte outside the string looks up entry 256 (as chunk_code_bits_nb does)
-template <int U = 1, bool T257 = false, class O>
+// DEFER_LONG: for callers that do not know the verdict before they place (the sorted and the staged encoders).
+// Dwords with a code longer than 16 bits are left out of the first walk (EncV2); the lanes whose string had one
+// and was kept then walk their whole string again with the plain routine, the others switched off.  The stage is
+// zeroed and only ever OR-ed into, so placing the same bits twice changes nothing and the second walk needs no
+// clearing: the stage ends up exactly as the plain routine leaves it.  A string that fails is not walked again
+// (its slot is unspecified), and that is what nearly every string with such bytes does: random bytes pass
+// 8 len - 7 bits after four or five dwords, each of which cost the wave a detour before.
+template <int U = 1, bool T257 = false, bool DEFER_LONG = false, class O>
 __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint32_t last, uint32_t start, uint32_t len,
                                                     bool active, O obase, uint32_t startbit,
                                                     const uint2* __restrict__ enc, uint32_t limit, bool pad) {
@@ -848,7 +863,8 @@ __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint3
     const uint32_t mfirst = 0xFFFFFFFFu << (8u * (start & 3u));
     const uint32_t mlast = (uint32_t)(0xFFFFFFFFull >> ((32u - 8u * (end & 3u)) & 31u));
     // tlim < 2^31 keeps tb + n - tlim a signed quantity (stage bits are < 2^20)
-    EncV2<O> E{enc, obase, startbit, limit >= 0x40000000u ? 0x7FFFFFFFu : startbit + limit, active, false};
+    EncV2<O, DEFER_LONG> E{
+        enc, obase, startbit, limit >= 0x40000000u ? 0x7FFFFFFFu : startbit + limit, active, false, 0u};
     auto masked = [&](uint32_t j, bool on, uint32_t w) {  // one dword with byte masks (head / tail); w: its word
         uint32_t vm = j == 0 ? mfirst : 0xFFFFFFFFu;
         vm &= (j + 1 == ndw) ? mlast : 0xFFFFFFFFu;
@@ -889,6 +905,11 @@ __device__ __forceinline__ uint32_t encode_chunk_v2(const uint32_t* stage, uint3
     E.fail = E.fail || (E.live && E.tb >= E.tlim);
     E.live = E.live && !E.fail;
     masked(jl, active && (end & 3u) != 0 && jl >= jf, stage[min(a0 + 4u * jl, last) >> 2]);  // tail
+    if constexpr (DEFER_LONG) {  // the second walk (it pads too: the same bits again)
+        const bool need = E.pend != 0u && !E.fail && active;
+        if (__builtin_amdgcn_ballot_w64(need) != 0)
+            encode_chunk_v2<U, T257, false>(stage, last, start, len, need, obase, startbit, enc, limit, pad);
+    }
     if (E.fail || !active) return kFailLen;
     const uint32_t tbits = E.tb - startbit;
     if (pad) {  // fill the last byte with ones (EOS prefix, hpack.c:795-798); strings start on a byte, so the

@@ -1655,8 +1655,9 @@ __global__ __launch_bounds__(WAVES * 64) void encode_staged_kernel(EncArgs A) {
                 const bool act = t.valid && t.len != 0 && t.len <= kMaxStrLen;
                 const uint32_t rel = t.len ? t.s - cur.a0 : 0u;
                 const uint32_t last = cur.span ? cur.span - 4u : 0u;
-                const uint32_t tb = encode_chunk_v2<HHUFF_ENC_OTHER_U>(stage, last, rel, t.len, act, lds_addr(obuf32), 8u * cur.op0, s_enc,
-                                                    act ? 8 * t.len - 7 : 0xFFFFFFFFu, true);
+                // (DEFER_LONG: the verdict is not known before the placement)
+                const uint32_t tb = encode_chunk_v2<HHUFF_ENC_OTHER_U, false, true>(
+                    stage, last, rel, t.len, act, lds_addr(obuf32), 8u * cur.op0, s_enc, act ? 8 * t.len - 7 : 0xFFFFFFFFu, true);
                 const uint32_t r = tb == kFailLen ? kFailLen : (tb + 7) >> 3;
                 if (act) ol = r;
             }
@@ -1914,8 +1915,9 @@ __global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
             const uint2 sj = s_str[j];
             const bool vj = cb + j < A.n;
             const bool act = vj && sj.y != 0 && sj.y <= kMaxStrLen;
-            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U>(s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x, s_enc,
-                                                act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
+            // (DEFER_LONG: the second walk of kept strings with long codes ends before barrier 3 below)
+            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, false, true>(
+                s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x, s_enc, act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
             // the encoded length goes back to the string's own record (read by its own thread only), so the
             // lengths and statuses are stored in string order, coalesced
             s_str[j].x = act && tb != kFailLen ? (tb + 7) >> 3 : kFailLen;
@@ -2201,8 +2203,9 @@ void encode_sorted_kernel(EncArgs A) {
             const uint2 sj = make_uint2(rj & 0x3FFFu, rj >> 14);
             const bool vj = cb + j < A.n;
             const bool act = vj && sj.y != 0 && sj.y <= kMaxStrLen;
-            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, true>(s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x,
-                                                                          s_enc, act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
+            // (DEFER_LONG: the second walk of kept strings with long codes ends before barrier 3 below)
+            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, true, true>(
+                s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x, s_enc, act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
             // the encoded length goes back to the string's own thread (shorter than the string: 16 bits hold
             // it), so the lengths and statuses are stored in string order, coalesced
             s_olen[j] = (uint16_t)(act && tb != kFailLen ? (tb + 7) >> 3 : kSortFail);

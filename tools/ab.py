@@ -42,6 +42,12 @@ def run(names, cfg="c4", rounds=5, steps=10):
 
     # ablation configs (not product configs): fixed-length strings isolate lane imbalance
     synth.CONFIGS.setdefault("c4u", dict(n=1 << 24, lengths=("uniform", 48, 48), alphabet="header"))
+    # c4 with no adversarial strings (c4 less c4na: what the 1 % of random-byte strings cost), and the same with
+    # one byte of a 20-bit code (0x80) in the middle of every 64th string, which still compresses: the hostile
+    # batch for an encoder that walks such a string twice
+    c4 = synth.CONFIGS["c4"]
+    synth.CONFIGS.setdefault("c4na", dict(c4, adversarial_frac=0.0))
+    synth.CONFIGS.setdefault("c4rare", dict(c4, adversarial_frac=0.0, rare_every=64))
     synth.CONFIGS.setdefault("c3desc", dict(n=1 << 20, lengths=("zipf_desc", 8, 512), alphabet="header"))
     # c3's two halves at their c3 counts (the zipf's conditional lengths): what a length partition could reach
     synth.CONFIGS.setdefault("c3lo", dict(n=643000, lengths=("zipf", 8, 96), alphabet="header"))
@@ -63,7 +69,11 @@ def run(names, cfg="c4", rounds=5, steps=10):
         L.hhuff_flatten_batch.argtypes = [vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp,
                                           vp, vp]
         libs[nm] = L
-    b = synth.make_batch_torch(cfg, seed=5)
+    spec = synth.CONFIGS[cfg]
+    b = synth.make_batch_torch(cfg, seed=5, adversarial_frac=spec.get("adversarial_frac", 0.01))
+    if spec.get("rare_every"):
+        o = b["off"][:-1:spec["rare_every"]], b["off"][1::spec["rare_every"]]
+        b["data"][(o[0] + o[1]) // 2] = 0x80
     n, P = b["n"], int(b["total"])
     off32 = b["off"].to(torch.int32)
     lens = b["off"][1:] - b["off"][:-1]
