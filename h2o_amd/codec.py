@@ -486,9 +486,10 @@ HPE_HEADER_DTYPE = np.dtype([("name_off", "<u4"), ("name_len", "<u4"), ("value_o
                              ("flags", "<u4")])
 HPE_RESPONSE_DTYPE = np.dtype([("content_length", "<u8"), ("stream_id", "<u4"), ("status", "<u4"),
                                ("hdr_first", "<u4"), ("nhdr", "<u4"), ("header_table_size", "<u4"),
-                               ("max_frame_size", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+                               ("max_frame_size", "<u4"), ("flags", "<u4"), ("parent_stream_id", "<u4")])
 HDR_DONT_COMPRESS, HDR_TOKEN = 1, 2
 RES_END_STREAM, RES_SERVER, RES_TRAILERS, RES_REQUEST = 1, 2, 4, 8
+RES_PUSH_PROMISE = 16  # h2o_hpack_flatten_push_promise: stream_id is the promised stream, parent_stream_id the frames'
 ENC_CONTINUE = 1
 RES_SPACE, RES_SKIPPED, RES_EINVAL = -300, -301, -303
 

@@ -2,7 +2,8 @@
 // what both use in hhuff_enc.h.
 //
 // h2o_hpack_flatten_response (lib/http2/hpack.c:1137-1177), h2o_hpack_flatten_trailers
-// (:1179-1196) and, on the client side, h2o_hpack_flatten_request (:1044-1096) for many connections, each with its encoder dynamic table (do_encode_header :858-937,
+// (:1179-1196), h2o_hpack_flatten_push_promise (:1098-1135) and, on the client side, h2o_hpack_flatten_request
+// (:1044-1096) for many connections, each with its encoder dynamic table (do_encode_header :858-937,
 // header_table_add :277-317 with at most 32 entries, header_table_adjust_size :839-856).
 // What a field becomes depends on the table, and the table on every earlier field of the connection, so
 // the table work is sequential per connection -- but it needs no output bytes: only lengths and equality.
@@ -119,6 +120,22 @@ __device__ __forceinline__ uint32_t request_fast(const uint8_t* n, uint32_t nl, 
         b = 0x90u, own = 0u;
     }
     return b ? (b << kInfoFastShift | own) : 0u;
+}
+
+// What a record's kind decides about its frames: the first frame's type and its flags besides END_HEADERS, the
+// stream id of every frame header of the block, and the payload bytes ahead of the size update.  HEADERS
+// (:1094, :1174, :1194) go out on the record's own stream; a promise (h2o_hpack_flatten_push_promise,
+// :1098-1135) is a PUSH_PROMISE without END_STREAM on the parent stream whose payload starts with the
+// promised stream id (:1116).  The walk, the emit head and the frames kernel all read it here.
+struct FrameRule {
+    uint32_t type, flags, sid, lead;
+    bool own;  // the header range starts with `status` own fields, no :status / server / content-length
+};
+__device__ __forceinline__ FrameRule frame_rule(const hhuff_hpack_response_t& R) {
+    if (R.flags & HHUFF_RES_PUSH_PROMISE) return FrameRule{5u, 0u, R.parent_stream_id, 4u, true};
+    const bool trailers = (R.flags & HHUFF_RES_TRAILERS) != 0;
+    const uint32_t es = (trailers || (R.flags & HHUFF_RES_END_STREAM)) ? 1u : 0u;
+    return FrameRule{1u, es, R.stream_id, 0u, !trailers && (R.flags & HHUFF_RES_REQUEST)};
 }
 }  // namespace
 
@@ -401,8 +418,9 @@ __global__ __launch_bounds__(64) void hpe_table_kernel(HpeArgs A) {
         const hhuff_hpack_response_t Rn = A.res[rn];
         const uint64_t base_n = limit, limit_n = A.out_off[rn + 1];
         const bool trailers = (R.flags & HHUFF_RES_TRAILERS) != 0;
-        const bool request = !trailers && (R.flags & HHUFF_RES_REQUEST);  // h2o_hpack_flatten_request
-        const bool head = !trailers && !request;                          // :status, server, content-length
+        const FrameRule F = frame_rule(R);
+        const bool request = F.own;               // h2o_hpack_flatten_request / _push_promise
+        const bool head = !trailers && !request;  // :status, server, content-length
         const bool server = head && (R.flags & HHUFF_RES_SERVER) && A.server_len != 0;
         const uint32_t h0 = R.hdr_first, h1 = R.hdr_first + R.nhdr;
         const uint32_t own_end = request ? h0 + R.status : h0;  // a request's own fields: method .. expect
@@ -411,12 +429,14 @@ __global__ __launch_bounds__(64) void hpe_table_kernel(HpeArgs A) {
             st = HHUFF_RES_SKIPPED;
         } else if ((uint64_t)R.hdr_first + R.nhdr > A.nhdr || limit < base ||  // header range / region malformed
                    (head && (R.status < 100 || R.status > 999)) || (request && R.status > R.nhdr) ||
+                   ((R.flags & HHUFF_RES_PUSH_PROMISE) && (R.flags & (HHUFF_RES_TRAILERS | HHUFF_RES_REQUEST))) ||
                    R.max_frame_size < 16384u ||
                    R.max_frame_size > 0xFFFFFFu || (server && (srv_info & kInfoBad))) {
             st = HHUFF_RES_EINVAL;
         }
         uint32_t pos = 0, su = ~0u, scode = 0, spos = 0, cll = 0;
         if (st == 0) {
+            pos = F.lead;                       // a promise's stream id comes before the size update (:1116-1117)
             if (R.header_table_size < t.cap) {  // header_table_adjust_size (:839-856)
                 t.cap = R.header_table_size;
                 while (t.num != 0 && t.size > t.cap) t.evict_one();
@@ -530,8 +550,8 @@ __device__ __forceinline__ void put_frame_header(uint8_t* d, uint32_t len, uint3
 }
 }  // namespace
 
-// 3. emit: items 0 .. nhdr-1 are fields, nhdr .. nhdr+nres-1 response heads (frame header, table size
-//    update, :status, server, and the content-length at the end)
+// 3. emit: items 0 .. nhdr-1 are fields, nhdr .. nhdr+nres-1 response heads (frame header, a promise's
+//    stream id, table size update, :status, server, and the content-length at the end)
 __global__ __launch_bounds__(256) void hpe_emit_kernel(HpeArgs A) {
     __shared__ uint2 s_enc[256];
     s_enc[threadIdx.x] = make_uint2(e_enc_code[threadIdx.x], e_enc_nbits[threadIdx.x]);
@@ -552,13 +572,13 @@ __global__ __launch_bounds__(256) void hpe_emit_kernel(HpeArgs A) {
         if (p0.w == 0) continue;  // failed
         const hhuff_hpack_response_t R = A.res[r];
         uint8_t* base = A.out + ((uint64_t)p0.y << 32 | p0.x);
-        const bool trailers = (R.flags & HHUFF_RES_TRAILERS) != 0;
-        const uint32_t es = (trailers || (R.flags & HHUFF_RES_END_STREAM)) ? 1u : 0u;
-        if (p0.z <= R.max_frame_size) put_frame_header(base, p0.z, 1u, 4u | es, R.stream_id);  // else hpe_frames_kernel
+        const FrameRule F = frame_rule(R);
+        if (p0.z <= R.max_frame_size) put_frame_header(base, p0.z, F.type, 4u | F.flags, F.sid);  // else hpe_frames_kernel
         RegSink sink;
         sink.init(base + 9);
+        if (F.lead) sink.put4(__builtin_bswap32(R.stream_id));  // the promised stream id (h2o_http2_encode32u, :1116)
         if (p1.x != ~0u) sink_int(sink, 0x20u, p1.x, 5);  // Dynamic Table Size Update (:852-853)
-        if (!trailers && !(R.flags & HHUFF_RES_REQUEST)) {
+        if (!(R.flags & HHUFF_RES_TRAILERS) && !F.own) {
             const uint32_t s = R.status;  // encode_status (:437-466)
             const uint32_t c = s == 200 ? 8 : s == 204 ? 9 : s == 206 ? 10 : s == 304 ? 11 : s == 400 ? 12 : s == 404 ? 13 : s == 500 ? 14 : 0;
             if (c) {
@@ -598,6 +618,7 @@ __global__ __launch_bounds__(256) void hpe_frames_kernel(HpeArgs A) {
         const uint4 p0 = A.plan[2 * r];
         const hhuff_hpack_response_t R = A.res[r];
         uint8_t* base = A.out + ((uint64_t)p0.y << 32 | p0.x);
+        const FrameRule F = frame_rule(R);
         const uint32_t P = p0.z, M = R.max_frame_size;
         const uint32_t k = (P + M - 1u) / M;
         for (uint32_t j = k - 1; j >= 1; --j) {
@@ -613,15 +634,11 @@ __global__ __launch_bounds__(256) void hpe_frames_kernel(HpeArgs A) {
             }
             if (threadIdx.x == 0) {
                 const bool last = j == k - 1;
-                put_frame_header(base + (uint64_t)j * (M + 9u), last ? (uint32_t)(hi - lo) : M, 9u, last ? 4u : 0u,
-                                 R.stream_id);
+                put_frame_header(base + (uint64_t)j * (M + 9u), last ? (uint32_t)(hi - lo) : M, 9u, last ? 4u : 0u, F.sid);
             }
             __syncthreads();
         }
-        if (threadIdx.x == 0) {
-            const uint32_t es = ((R.flags & HHUFF_RES_TRAILERS) || (R.flags & HHUFF_RES_END_STREAM)) ? 1u : 0u;
-            put_frame_header(base, M, 1u, es, R.stream_id);
-        }
+        if (threadIdx.x == 0) put_frame_header(base, M, F.type, F.flags, F.sid);
         __syncthreads();
     }
 }

@@ -14,12 +14,14 @@ A batch (the include/hhuff.h hhuff_hpack_flatten_responses layout): `data` (ever
 `hdr` (HPE_HEADER_DTYPE records), `res` (HPE_RESPONSE_DTYPE), `conn_first` [nconn+1], `server_off`,
 `server_len`, `out_off` [nres+1] (hhuff_hpack_response_bound per response, 16-byte aligned).
 Several steps of one session continue the same connections (HHUFF_ENC_CONTINUE).
+make_request_session: the client's requests (h2o_hpack_flatten_request); make_push_session: a pushing server's
+connections (h2o_hpack_flatten_push_promise records among the responses).
 """
 import numpy as np
 
 from .codec import HPE_HEADER_DTYPE, HPE_RESPONSE_DTYPE, QPE_RESPONSE_DTYPE, HDR_DONT_COMPRESS, HDR_LIKELY_TO_REPEAT, \
-    HDR_TOKEN, QRES_DATAGRAM, QRES_REQUEST, RES_END_STREAM, RES_REQUEST, RES_SERVER, RES_TRAILERS, hpack_response_bound, \
-    qpack_response_bound, qpack_session_response_bound
+    HDR_TOKEN, QRES_DATAGRAM, QRES_REQUEST, RES_END_STREAM, RES_PUSH_PROMISE, RES_REQUEST, RES_SERVER, RES_TRAILERS, \
+    hpack_response_bound, qpack_response_bound, qpack_session_response_bound
 
 SERVER = b"h2o/2.3.0-dev"
 _CTYPES = [b"text/html; charset=utf-8", b"text/css", b"application/javascript", b"image/png", b"image/jpeg",
@@ -295,6 +297,109 @@ def make_request_session(nconn, steps=1, req_per_conn=(1, 8), seed=0, small_tabl
     return out
 
 
+# ---- server push: h2o_hpack_flatten_push_promise (lib/http2/hpack.c:1098-1135) as push_path
+# (lib/http2/connection.c:1875-1964) produces the calls ----
+# the request headers a pushed request inherits: the tokens with copy_for_push_request (lib/common/token_table.h)
+_PUSH_TOKENS = {b"accept", b"accept-charset", b"accept-encoding", b"accept-language", b"user-agent"}
+_CHARSETS = [b"utf-8", b"utf-8, iso-8859-1;q=0.5"]
+
+
+def _push_client(rng):
+    """what a connection's pushed requests share: push_path copies scheme and authority from the parent request"""
+    cl = _client(rng)
+    u = rng.random()
+    cl["scheme"] = b"https" if u < 0.89 else b"http" if u < 0.99 else [b"masque", b"ftp"][int(rng.integers(0, 2))]
+    cl["charset"] = _CHARSETS[int(rng.integers(0, 2))] if rng.random() < 0.2 else None
+    cl["assets"] = [b"/%s/%s.%s" % (_rand(rng, _B64[26:52], int(rng.integers(2, 8))), _rand(rng, _B64, int(rng.integers(1, 24))),
+                                    [b"css", b"js", b"png", b"woff2"][int(rng.integers(0, 4))]) for _ in range(3)]
+    return cl
+
+
+def _promise(rng, cl, big_frac):
+    """-> (own fields, headers) of one h2o_hpack_flatten_push_promise call"""
+    u = rng.random()
+    path = b"/" if u < 0.08 else b"/index.html" if u < 0.16 else cl["assets"][int(rng.integers(0, 3))] if u < 0.7 else \
+        b"/static/%s" % _rand(rng, _B64, int(rng.integers(1, 40)))
+    own = [(b":method", b"GET"), (b":scheme", cl["scheme"]), (b":authority", cl["host"]), (b":path", path)]
+    hs = [(b"accept", _ACCEPTS[int(rng.integers(0, len(_ACCEPTS)))] if rng.random() < 0.3 else _ACCEPTS[0])]
+    if cl["charset"] is not None:
+        hs.append((b"accept-charset", cl["charset"]))
+    if cl["ae"] is not None:
+        hs.append((b"accept-encoding", cl["ae"]))
+    hs.append((b"accept-language", cl["lang"]))
+    ua = cl["ua"]
+    if rng.random() < big_frac:  # longer than max_frame_size: CONTINUATION frames
+        ua = b"Mozilla/5.0 (" + _rand(rng, _B64, int(rng.integers(24000, 50000))) + b")"
+    hs.append((b"user-agent", ua))
+    return own, hs
+
+
+def make_push_session(nconn, steps=1, seed=0, parents_per_conn=(1, 4), small_table_frac=0.05, big_frac=0.004,
+                      notoken_frac=0.01, dont_compress_frac=0.01, frame_frac=0.05, push_only=False):
+    """Server connections that push (HHUFF_RES_PUSH_PROMISE records: `status` = 4 own fields, stream_id = the
+    promised stream, parent_stream_id = the stream whose response triggered the push), in wire order with the
+    connection's responses: a parent response on an odd stream is preceded by 0-4 promises (promised ids even,
+    rising by 2 per connection), and the pushed streams' own responses follow later on the even ids.
+    push_only=True leaves the responses out (only promises: every block of the session is a request).  Same
+    batch layout as make_session; its own generator, so make_session / make_request_session are unaffected."""
+    rng = np.random.default_rng(seed)
+    sites = [_site(rng) for _ in range(nconn)]
+    clients = [_push_client(rng) for _ in range(nconn)]
+    caps = [4096 if rng.random() >= small_table_frac else int(rng.choice([0, 64, 256, 1024, 2048])) for _ in range(nconn)]
+    mfs = [16384 if rng.random() >= frame_frac else int(rng.choice([1 << 15, 1 << 20, (1 << 24) - 1])) for _ in range(nconn)]
+    parent = [1] * nconn    # the next client-initiated stream
+    promised = [2] * nconn  # the next server-initiated stream
+    pending = [[] for _ in range(nconn)]  # promised streams whose response is still to come
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    out = []
+    for _ in range(steps):
+        B = _Batch()
+        server_off = B.s(SERVER)
+        conn_first = [0]
+
+        def response(c, sid, k):
+            st, hs, cl, end = _response(rng, sites[c], B, k, 0.0)
+            first = len(B.hdr)
+            for name, value in hs:
+                f = HDR_TOKEN if name in _TOKENS and rng.random() >= notoken_frac else 0
+                if rng.random() < dont_compress_frac:
+                    f |= HDR_DONT_COMPRESS
+                B.header(name, value, f)
+            fl = (RES_END_STREAM if end else 0) | (RES_SERVER if st != 103 else 0)
+            B.res.append((none if cl is None else cl, sid, st, first, len(B.hdr) - first, caps[c], mfs[c], fl, 0))
+
+        for c in range(nconn):
+            for k in range(int(rng.integers(parents_per_conn[0], parents_per_conn[1] + 1))):
+                if rng.random() < 0.02:  # the peer changes SETTINGS_HEADER_TABLE_SIZE
+                    caps[c] = int(rng.choice([0, 128, 512, 1024, 4096, 65536]))
+                for _p in range(int(rng.integers(0, 5))):
+                    own, hs = _promise(rng, clients[c], big_frac)
+                    first = len(B.hdr)
+                    for name, value in own:
+                        B.header(name, value, HDR_TOKEN)
+                    for name, value in hs:
+                        f = HDR_TOKEN if name in _PUSH_TOKENS and rng.random() >= notoken_frac else 0
+                        if rng.random() < dont_compress_frac:
+                            f |= HDR_DONT_COMPRESS
+                        B.header(name, value, f)
+                    B.res.append((none, promised[c], len(own), first, len(B.hdr) - first, caps[c], mfs[c], RES_PUSH_PROMISE,
+                                  parent[c]))
+                    pending[c].append(promised[c])
+                    promised[c] += 2
+                if not push_only:
+                    response(c, parent[c], k)
+                    while pending[c] and rng.random() < 0.6:  # a pushed stream's own response
+                        response(c, pending[c].pop(0), k)
+                parent[c] += 2
+            conn_first.append(len(B.res))
+        hdr = np.array(B.hdr, dtype=HPE_HEADER_DTYPE) if B.hdr else np.zeros(0, HPE_HEADER_DTYPE)
+        res = np.array(B.res, dtype=HPE_RESPONSE_DTYPE) if B.res else np.zeros(0, HPE_RESPONSE_DTYPE)
+        data = np.frombuffer(b"".join(B.chunks), np.uint8).copy()
+        out.append(dict(data=data, hdr=hdr, res=res, conn_first=np.array(conn_first, np.uint32), server_off=server_off,
+                        server_len=len(SERVER), out_off=out_offsets(hdr, res, len(SERVER))))
+    return out
+
+
 def out_offsets(hdr, res, server_len):
     """[nres + 1] u64 region starts: hhuff_hpack_response_bound per response, 16-byte aligned"""
     nv = (hdr["name_len"].astype(np.int64) + hdr["value_len"]) if hdr.size else np.zeros(0, np.int64)
@@ -311,7 +416,7 @@ def out_offsets(hdr, res, server_len):
 def build_batch(conns, server=SERVER):
     """An explicit batch: conns = [[response, ...] per connection], response = dict(status=, headers=[(name,
     value, flags)], content_length=None, flags=RES_*, header_table_size=4096, max_frame_size=16384,
-    stream_id=1)"""
+    stream_id=1, parent_stream_id=0)"""
     B = _Batch()
     server_off = B.s(server)
     conn_first = [0]
@@ -323,7 +428,7 @@ def build_batch(conns, server=SERVER):
             cl = r.get("content_length")
             B.res.append((np.uint64(0xFFFFFFFFFFFFFFFF) if cl is None else cl, r.get("stream_id", 1), r.get("status", 200),
                           first, len(B.hdr) - first, r.get("header_table_size", 4096), r.get("max_frame_size", 16384),
-                          r.get("flags", 0), 0))
+                          r.get("flags", 0), r.get("parent_stream_id", 0)))
         conn_first.append(len(B.res))
     hdr = np.array(B.hdr, dtype=HPE_HEADER_DTYPE) if B.hdr else np.zeros(0, HPE_HEADER_DTYPE)
     res = np.array(B.res, dtype=HPE_RESPONSE_DTYPE) if B.res else np.zeros(0, HPE_RESPONSE_DTYPE)

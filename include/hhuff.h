@@ -417,15 +417,30 @@ int hhuff_qpack_parse_responses(const uint8_t *in, uint64_t in_size, const uint3
  *                    HHUFF_HDR_TOKEN and no HHUFF_HDR_DONT_COMPRESS; :method GET / POST, :scheme https / http,
  *                    :path / and /index.html among them, and accept-encoding "gzip, deflate" (token) among the
  *                    others, are the one-byte static references h2o writes without its table (:950-985,
- *                    :1083-1086; a scheme named https / http is h2o's H2O_URL_SCHEME_HTTPS / _HTTP)
- *        out         response r's frames (HEADERS, then CONTINUATIONs past max_frame_size, fixup_frame_headers
+ *                    :1083-1086; a scheme named https / http is h2o's H2O_URL_SCHEME_HTTPS / _HTTP);
+ *                    HHUFF_RES_PUSH_PROMISE makes r a promise (h2o_hpack_flatten_push_promise, :1098-1135, as
+ *                    h2o_http2_stream_send_push_promise calls it): stream_id is the promised stream, written as
+ *                    given in the payload's first 4 bytes (big-endian, before the Dynamic Table Size Update),
+ *                    parent_stream_id (read only under this flag) goes into every frame header of the block; the
+ *                    first frame is a PUSH_PROMISE (type 5; END_HEADERS or no flag, never END_STREAM); `status`
+ *                    counts the own fields that lead the header range as for HHUFF_RES_REQUEST (h2o's call has 4:
+ *                    :method, :scheme, :authority, :path) with the same one-byte references by place;
+ *                    HHUFF_RES_SERVER, HHUFF_RES_END_STREAM and content_length are ignored; the flag together
+ *                    with HHUFF_RES_TRAILERS or HHUFF_RES_REQUEST is refused (HHUFF_RES_EINVAL).  Promises,
+ *                    responses and trailers of a connection mix freely in conn_first order -- the order they go
+ *                    on the wire -- and share the table
+ *        out         response r's frames (HEADERS or PUSH_PROMISE, then CONTINUATIONs past max_frame_size -- for
+ *                    a promise counted over a payload that includes the 4 id bytes --, fixup_frame_headers
  *                    :1012-1042) at out + out_off[r]; region [out_off[r], out_off[r+1]) (u64, nres + 1 entries);
  *                    hhuff_hpack_response_bound() is enough for any table state
  *      Per response: out_len[r] = bytes written (frame headers included), headers_size[r] = the payload bytes
- *      (h2o_hpack_flatten_response's return value), rstatus[r] = 0, HHUFF_RES_SPACE (the frames do not fit
- *      the region), HHUFF_RES_EINVAL (status outside 100..999 -- past nhdr for a request --, max_frame_size outside 16384..2^24-1, a string
- *      past in_size) or HHUFF_RES_SKIPPED (an earlier response of the connection failed: its table is no
- *      longer the peer's, h2o would have dropped the connection).  A failed response writes nothing.
+ *      (h2o_hpack_flatten_response's return value; a promise's 4 id bytes included), rstatus[r] = 0,
+ *      HHUFF_RES_SPACE (the frames do not fit the region), HHUFF_RES_EINVAL (status outside 100..999 -- past
+ *      nhdr for a request or a promise --, max_frame_size outside 16384..2^24-1, a string past in_size, a promise
+ *      flagged as trailers or request too) or HHUFF_RES_SKIPPED (an earlier response of the connection failed:
+ *      its table is no longer the peer's, h2o would have dropped the connection).  A failed response writes
+ *      nothing and leaves the table as it was, but for the capacity change of its size update where a later
+ *      step refused it.
  *      Device arrays; scratch = hhuff_hpack_enc_scratch_size(nconn) bytes (16-byte aligned) holding the
  *      tables: HHUFF_ENC_CONTINUE carries them (and the failed state) over from the previous call; without it
  *      every connection starts with an empty table.  nhdr = headers in hdr, nres = conn_first[nconn] (host
@@ -439,24 +454,27 @@ typedef struct hhuff_hpack_header {
 #define HHUFF_HDR_TOKEN 2u
 typedef struct hhuff_hpack_response {
     uint64_t content_length;    /* res.content_length: SIZE_MAX (all ones) sends none */
-    uint32_t stream_id, status; /* status: res.status (ignored for trailers; own fields of a request) */
+    uint32_t stream_id, status; /* status: res.status (ignored for trailers; own fields of a request / promise) */
     uint32_t hdr_first, nhdr;
     uint32_t header_table_size; /* conn->peer_settings.header_table_size (header_table_adjust_size, :839-856) */
     uint32_t max_frame_size;    /* conn->peer_settings.max_frame_size */
     uint32_t flags;             /* HHUFF_RES_* */
-    uint32_t reserved;          /* 0 */
+    uint32_t parent_stream_id;  /* HHUFF_RES_PUSH_PROMISE: the stream of the frame headers; not read otherwise */
 } hhuff_hpack_response_t;       /* 40 bytes */
 #define HHUFF_RES_END_STREAM 1u /* is_end_stream */
 #define HHUFF_RES_SERVER 2u     /* server_name != NULL */
 #define HHUFF_RES_TRAILERS 4u   /* h2o_hpack_flatten_trailers */
 #define HHUFF_RES_REQUEST 8u    /* h2o_hpack_flatten_request (status = the number of its own fields) */
+#define HHUFF_RES_PUSH_PROMISE 16u /* h2o_hpack_flatten_push_promise (stream_id = the promised stream) */
 #define HHUFF_ENC_CONTINUE 1u
 #define HHUFF_RES_SPACE (-300)
 #define HHUFF_RES_SKIPPED (-301)
 #define HHUFF_RES_EINVAL (-303)
 /* A region size that holds response r whatever its connection's table: name_value_bytes = the sum of its
  * headers' name_len + value_len, server_len = 0 without HHUFF_RES_SERVER.  (h2o's own reservation,
- * hpack.c:1141-1152 with calc_capacity :998-1001, plus the CONTINUATION frame headers.) */
+ * hpack.c:1141-1152 with calc_capacity :998-1001, plus the CONTINUATION frame headers.)  A promise fits with
+ * server_len = 0: its worst payload is name_value_bytes + 21 nhdr + 4 (the promised id) + 5 (the size update),
+ * and the bound allows + 33. */
 static inline uint64_t hhuff_hpack_response_bound(uint64_t name_value_bytes, uint32_t nhdr, uint32_t server_len,
                                                   uint32_t max_frame_size)
 {
