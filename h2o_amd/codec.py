@@ -33,6 +33,15 @@ class HhuffError(RuntimeError):
     pass
 
 
+class _ConnSlotsStruct(ctypes.Structure):  # include/hhuff.h hhuff_conn_slots_t
+    _fields_ = [("slot", _vp), ("flags", _vp), ("nslots", ctypes.c_uint32)]
+
+
+SLOTS_SYMBOLS = ("hhuff_hpack_decode_blocks_slots", "hhuff_hpack_parse_requests_slots", "hhuff_hpack_parse_responses_slots",
+                 "hhuff_qpack_decode_slots", "hhuff_qpack_parse_requests_slots", "hhuff_qpack_parse_responses_slots",
+                 "hhuff_hpack_flatten_responses_slots", "hhuff_qpack_flatten_sessions_slots")
+
+
 def lib():
     """Load libhhuff.so (fails loudly when the HIP extension is not built)."""
     global _lib
@@ -124,6 +133,12 @@ def lib():
                                                     ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64,
                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32] + [_vp] * 12 +
                                                    [ctypes.c_uint64, ctypes.c_uint, _vp])
+        # include/hhuff.h (2h): every stateful entry point again with a hhuff_conn_slots_t first
+        for name in SLOTS_SYMBOLS:
+            base = getattr(L, name[:-len("_slots")])
+            f = getattr(L, name)
+            f.restype = ctypes.c_int
+            f.argtypes = [ctypes.POINTER(_ConnSlotsStruct)] + list(base.argtypes)
         L.hhuff_version.restype = ctypes.c_char_p
         L.hhuff_last_error_string.restype = ctypes.c_char_p
         L.hhuff_grid_size.restype = ctypes.c_int
@@ -173,7 +188,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_qpack_flatten_sessions", "hhuff_set_decode_kernel",
             "hhuff_decode_batch_host_packed", "hhuff_encode_batch_host_packed", "hhuff_set_edge_defer_min",
             "hhuff_decode_batch_multi", "hhuff_encode_batch_multi", "hhuff_shard_bounds",
-            "hhuff_debug_encode_blocks_per_cu")
+            "hhuff_debug_encode_blocks_per_cu") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -219,6 +234,28 @@ def _stream(stream):
 
     s = torch.cuda.current_stream() if stream is None else stream
     return s.cuda_stream
+
+
+CONN_RESET = 1
+BLK_EINVAL = QPK_EINVAL = -303
+
+
+class ConnSlots:
+    """include/hhuff.h hhuff_conn_slots_t for the stateful calls' slots= argument: `slot` an int32 device tensor
+    (u32 bits) with the scratch slot of each listed connection (None: slot c = c), `flags` a uint8 device tensor of
+    CONN_RESET bits (None: all 0), `nslots` the slots the scratch holds."""
+
+    def __init__(self, slot, flags, nslots):
+        self.slot, self.flags, self.nslots = slot, flags, int(nslots)
+
+
+def _stateful(name, slots, args):
+    """call the stateful entry point `name`, or its _slots variant with `slots` (ConnSlots or None) in front"""
+    if slots is None:
+        _check(getattr(lib(), name)(*args), name)
+        return
+    st = _ConnSlotsStruct(_dp(slots.slot), _dp(slots.flags), slots.nslots)
+    _check(getattr(lib(), name + "_slots")(ctypes.byref(st), *args), name + "_slots")
 
 
 def decode_slot_size(in_size: int) -> int:
@@ -378,14 +415,16 @@ QRES_BYTES = 40
 
 
 def hpack_decode_blocks(data, blk_off, conn_first, table_size=4096, arena_off=None, in_size=None, stream=None,
-                        scratch=None, cont=False, requests=False, responses=False, trailers=None):
+                        scratch=None, cont=False, requests=False, responses=False, trailers=None, slots=None):
     """HPACK header blocks (include/hhuff.h hhuff_hpack_decode_blocks) on device tensors: blk_off / conn_first
     int32 tensors (u32 bits), arena_off int64.  Returns a dict of device tensors: arena, name_off, name_len,
     value_off, value_len, fflags (per field slot), nfields, bstatus (per block).  requests=True runs
     hhuff_hpack_parse_requests (h2o_hpack_parse_request per block) and adds req: int32 [nblk, 12], the
     hhuff_request_t words (REQUEST_FIELDS; content_length is words 0-1).  responses=True runs
     hhuff_hpack_parse_responses (h2o_hpack_parse_response per block; trailers: uint8 tensor, nonzero for a
-    trailers block, or None) and adds res: int32 [nblk, 4], the hhuff_response_t words (RESPONSE_FIELDS)."""
+    trailers block, or None) and adds res: int32 [nblk, 4], the hhuff_response_t words (RESPONSE_FIELDS).
+    slots (ConnSlots): the _slots variants -- the scratch holds slots.nslots slabs and the listed connections use
+    the ones slots.slot names."""
     import torch
 
     dev = data.device
@@ -403,7 +442,7 @@ def hpack_decode_blocks(data, blk_off, conn_first, table_size=4096, arena_off=No
              fflags=torch.empty(nslots, dtype=torch.uint8, device=dev),
              nfields=torch.empty(max(1, nblk), dtype=torch.int32, device=dev),
              bstatus=torch.empty(max(1, nblk), dtype=torch.int32, device=dev))
-    ss = int(lib().hhuff_hpack_scratch_size(nconn, table_size))
+    ss = int(lib().hhuff_hpack_scratch_size(nconn if slots is None else slots.nslots, table_size))
     if scratch is None:  # pass the previous call's r["scratch"] back with cont=True to carry the tables over
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
     args = [_dp(data), in_size, _dp(blk_off), _dp(conn_first), nconn, table_size, _dp(r["arena"]), _dp(arena_off),
@@ -412,13 +451,13 @@ def hpack_decode_blocks(data, blk_off, conn_first, table_size=4096, arena_off=No
     tail = [_dp(scratch), scratch.numel(), BLK_CONTINUE if cont else 0, _stream(stream)]
     if responses:
         r["res"] = torch.empty((max(1, nblk), 4), dtype=torch.int32, device=dev)
-        _check(lib().hhuff_hpack_parse_responses(*args[:6], None if trailers is None else _dp(trailers), *args[6:],
-                                                 _dp(r["res"]), *tail), "hhuff_hpack_parse_responses")
+        _stateful("hhuff_hpack_parse_responses", slots,
+                  [*args[:6], None if trailers is None else _dp(trailers), *args[6:], _dp(r["res"]), *tail])
     elif requests:
         r["req"] = torch.empty((max(1, nblk), 12), dtype=torch.int32, device=dev)
-        _check(lib().hhuff_hpack_parse_requests(*args, _dp(r["req"]), *tail), "hhuff_hpack_parse_requests")
+        _stateful("hhuff_hpack_parse_requests", slots, [*args, _dp(r["req"]), *tail])
     else:
-        _check(lib().hhuff_hpack_decode_blocks(*args, *tail), "hhuff_hpack_decode_blocks")
+        _stateful("hhuff_hpack_decode_blocks", slots, [*args, *tail])
     r["scratch"] = scratch  # keep alive until the stream has run the launch
     return r
 
@@ -431,7 +470,7 @@ QREQ_BYTES = 72  # sizeof(hhuff_qpack_request_t)
 
 def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table_size=4096, max_blocked=100,
                  num_blocked=None, arena_off=None, in_size=None, stream=None, scratch=None, cont=False, arena=None,
-                 stream_id=None, responses=False):
+                 stream_id=None, responses=False, slots=None):
     """QPACK decoder step (include/hhuff.h hhuff_qpack_decode) on device tensors: enc_off / enc_len (per
     connection), sec_off / conn_first / num_blocked int32 tensors (u32 bits), arena_off int64; nsec =
     conn_first[-1] as a host int.  Returns a dict of device tensors: arena, name_off, name_len, value_off,
@@ -441,7 +480,7 @@ def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table
     hhuff_qpack_parse_requests (h2o_qpack_parse_request per section), plus "req": uint8 [nsec, 72] records
     (hhuff_qpack_request_t).  responses=True (with stream_id): the HTTP/3 client's step,
     hhuff_qpack_parse_responses (h2o_qpack_parse_response per section), plus "res": uint8 [nsec, 40] records
-    (hhuff_qpack_response_head_t)."""
+    (hhuff_qpack_response_head_t).  slots (ConnSlots): the _slots variants (see hpack_decode_blocks)."""
     import torch
 
     dev = data.device
@@ -458,7 +497,7 @@ def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table
              fflags=torch.empty(nslots, dtype=torch.uint8, device=dev), nfields=i32(nsec), sstatus=i32(nsec),
              req_insert_count=torch.empty(max(1, nsec), dtype=torch.int64, device=dev), enc_status=i32(nconn),
              enc_consumed=i32(nconn), insert_count=torch.empty(max(1, nconn), dtype=torch.int64, device=dev))
-    ss = int(lib().hhuff_qpack_scratch_size(nconn, header_table_size))
+    ss = int(lib().hhuff_qpack_scratch_size(nconn if slots is None else slots.nslots, header_table_size))
     if scratch is None:
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
     args = [_dp(data), in_size, _dp(enc_off), _dp(enc_len), _dp(sec_off), _dp(conn_first), nconn, nsec,
@@ -468,15 +507,13 @@ def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table
             _dp(r["enc_consumed"]), _dp(r["insert_count"])]
     tail = [_dp(scratch), scratch.numel(), QPK_CONTINUE if cont else 0, _stream(stream)]
     if stream_id is None:
-        _check(lib().hhuff_qpack_decode(*(args + tail)), "hhuff_qpack_decode")
+        _stateful("hhuff_qpack_decode", slots, args + tail)
     elif responses:
         r["res"] = torch.empty((max(1, nsec), QRES_BYTES), dtype=torch.uint8, device=dev)
-        _check(lib().hhuff_qpack_parse_responses(*(args + [_dp(stream_id), _dp(r["res"])] + tail)),
-               "hhuff_qpack_parse_responses")
+        _stateful("hhuff_qpack_parse_responses", slots, args + [_dp(stream_id), _dp(r["res"])] + tail)
     else:
         r["req"] = torch.empty((max(1, nsec), QREQ_BYTES), dtype=torch.uint8, device=dev)
-        _check(lib().hhuff_qpack_parse_requests(*(args + [_dp(stream_id), _dp(r["req"])] + tail)),
-               "hhuff_qpack_parse_requests")
+        _stateful("hhuff_qpack_parse_requests", slots, args + [_dp(stream_id), _dp(r["req"])] + tail)
     r["scratch"] = scratch
     return r
 
@@ -562,7 +599,7 @@ def qpack_enc_scratch_size(nconn, header_table_size=4096, max_inflight=64):
 def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off, dec_off=None, dec_len=None,
                            header_table_size=4096, max_blocked=100, max_inflight=64, server_off=0, server_len=0,
                            enc_out_off=None, in_size=None, out=None, enc_out=None, scratch=None, cont=False,
-                           set_capacity=False, stream=None, evict=False, dup=False):
+                           set_capacity=False, stream=None, evict=False, dup=False, slots=None):
     """One step of many QPACK encoder sessions (include/hhuff.h hhuff_qpack_flatten_sessions) on device tensors:
     hdr = uint8 tensor of HPE_HEADER_DTYPE records, res = uint8 tensor of QPE_RESPONSE_DTYPE records, conn_first
     int32 (u32 bits) [nconn + 1], stream_id int64 per response, out_off int64 [nres + 1], dec_off / dec_len int32
@@ -573,7 +610,8 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
     for the connections' next step).  evict=True: HHUFF_QENC_EVICT, on every step of a session or on none; give
     enc_out_off then (qpack_session_enc_bound), since header_table_size + 4 bytes need not hold a step's inserts.
     dup=True: HHUFF_QENC_DUP, with evict=True only and likewise on every step or on none: entries about to be pinned
-    as the oldest are re-inserted by a Duplicate instruction."""
+    as the oldest are re-inserted by a Duplicate instruction.  slots (ConnSlots): hhuff_qpack_flatten_sessions_slots
+    (see hpack_decode_blocks); a connection with CONN_RESET is a new encoder in its slot."""
     import torch
 
     dev = data.device
@@ -590,28 +628,29 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
     r = dict(out=out, out_len=i32(nres), header_len=i32(nres), rstatus=i32(nres),
              rflags=torch.empty(max(1, nres), dtype=torch.uint8, device=dev), enc_out=enc_out, enc_out_off=enc_out_off,
              enc_out_len=i32(nconn), dec_status=i32(nconn), dec_consumed=i32(nconn))
-    ss = qpack_enc_scratch_size(nconn, header_table_size, max_inflight)
+    ss = qpack_enc_scratch_size(nconn if slots is None else slots.nslots, header_table_size, max_inflight)
     if scratch is None:
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
     flags = (QENC_CONTINUE if cont else 0) | (QENC_SET_CAPACITY if set_capacity else 0) | (QENC_EVICT if evict else 0) | \
         (QENC_DUP if dup else 0)
-    _check(lib().hhuff_qpack_flatten_sessions(
+    _stateful("hhuff_qpack_flatten_sessions", slots, [
         _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), _dp(conn_first), nconn, nres, _dp(stream_id),
         _dp(dec_off), _dp(dec_len), header_table_size, max_blocked, max_inflight, server_off, server_len, _dp(out),
         _dp(out_off), _dp(r["out_len"]), _dp(r["header_len"]), _dp(r["rstatus"]), _dp(r["rflags"]), _dp(enc_out),
         _dp(enc_out_off), _dp(r["enc_out_len"]), _dp(r["dec_status"]), _dp(r["dec_consumed"]), _dp(scratch),
-        scratch.numel(), flags, _stream(stream)), "hhuff_qpack_flatten_sessions")
+        scratch.numel(), flags, _stream(stream)])
     r["scratch"] = scratch
     return r
 
 
 def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_off=0, server_len=0, in_size=None,
-                            out=None, scratch=None, cont=False, stream=None):
+                            out=None, scratch=None, cont=False, stream=None, slots=None):
     """HTTP/2 response header blocks (include/hhuff.h hhuff_hpack_flatten_responses) on device tensors:
     hdr = uint8 tensor of HPE_HEADER_DTYPE records (20 B each), res = uint8 tensor of HPE_RESPONSE_DTYPE
     records (40 B), conn_first int32 (u32 bits), out_off int64 [nres + 1]; nres = conn_first[-1] as a host int.
     Returns a dict of device tensors: out, out_len, headers_size, rstatus, and the scratch holding the encoder
-    tables (pass it back with cont=True for the connections' next responses)."""
+    tables (pass it back with cont=True for the connections' next responses).  slots (ConnSlots):
+    hhuff_hpack_flatten_responses_slots (see hpack_decode_blocks)."""
     import torch
 
     dev = data.device
@@ -622,13 +661,13 @@ def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_of
         out = torch.empty(max(1, int(out_off[-1].item())), dtype=torch.uint8, device=dev)
     i32 = lambda n: torch.empty(max(1, n), dtype=torch.int32, device=dev)  # noqa: E731
     r = dict(out=out, out_len=i32(nres), headers_size=i32(nres), rstatus=i32(nres))
-    ss = int(lib().hhuff_hpack_enc_scratch_size(nconn))
+    ss = int(lib().hhuff_hpack_enc_scratch_size(nconn if slots is None else slots.nslots))
     if scratch is None:
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
-    _check(lib().hhuff_hpack_flatten_responses(
+    _stateful("hhuff_hpack_flatten_responses", slots, [
         _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), _dp(conn_first), nconn, nres, server_off,
         server_len, _dp(out), _dp(out_off), _dp(r["out_len"]), _dp(r["headers_size"]), _dp(r["rstatus"]),
-        _dp(scratch), scratch.numel(), ENC_CONTINUE if cont else 0, _stream(stream)), "hhuff_hpack_flatten_responses")
+        _dp(scratch), scratch.numel(), ENC_CONTINUE if cont else 0, _stream(stream)])
     r["scratch"] = scratch
     return r
 

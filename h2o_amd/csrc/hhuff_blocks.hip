@@ -19,10 +19,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "hhuff_device.h"
 #include "hhuff.h"
 #include "hhuff_launch.h"
 #include "hhuff_request.h"
+#include "hhuff_slots.h"
 
 namespace hhuff {
 namespace {
@@ -77,6 +80,7 @@ struct BlkArgs {
     uint64_t* fsrc_v;
     hhuff_response_t* res;   // response mode (hhuff_hpack_parse_responses): h2o_hpack_parse_response per block
     const uint8_t* trailers;  // response mode: per block, nonzero = trailers (status == NULL); NULL = none
+    const uint32_t* cmap;     // connection slots (hhuff_slots.h); NULL: connection c in slot c
 };
 constexpr int kWalkPlain = 0, kWalkReq = 1, kWalkResp = 2;  // hpack_walk_kernel modes
 
@@ -385,7 +389,7 @@ __device__ int32_t blk_field(const BlkArgs& A, const Win& W, DynTable& t, uint64
     return soft ? kErrInvalidChar : 0;
 }
 
-template <int MODE>
+template <int MODE, bool SLOTS>
 __global__ __launch_bounds__(kBlkThreads) void hpack_walk_kernel(BlkArgs A) {
     constexpr bool REQ = MODE == kWalkReq, RESP = MODE == kWalkResp;
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];  // literals decoded in place
@@ -409,11 +413,29 @@ __global__ __launch_bounds__(kBlkThreads) void hpack_walk_kernel(BlkArgs A) {
     const uint32_t E = tbl_entries(A.table_size);
     const Win W{A.in, A.in_size};
     for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < A.nconn; c += (uint64_t)gridDim.x * blockDim.x) {
-        uint8_t* scr = A.scratch + c * A.conn_scratch;
+        const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
+        if (cs.refused) {  // no slab of its own: its blocks are refused, nothing else is touched
+            for (uint32_t b = A.conn_first[c]; b < A.conn_first[c + 1]; ++b) {
+                A.nfields[b] = 0;
+                A.bstatus[b] = HHUFF_BLK_EINVAL;
+                if (REQ) {
+                    ReqState rq;
+                    rq.reset();
+                    req_store(A.req + b, rq);
+                }
+                if (RESP) {
+                    RespState rs;
+                    rs.reset(A.trailers != nullptr && A.trailers[b] != 0);
+                    resp_store(A.res + b, rs);
+                }
+            }
+            continue;
+        }
+        uint8_t* scr = A.scratch + cs.slot * A.conn_scratch;
         TableState* ts = reinterpret_cast<TableState*>(scr);
         DynTable t{reinterpret_cast<Entry*>(scr + sizeof(TableState)), E, 0u, 0u, 0ull, A.table_size, A.table_size};
         TableState s0{0u, 0u, 0u, 0u, 0ull, A.table_size};
-        if (A.flags & HHUFF_BLK_CONTINUE) s0 = *ts;
+        if ((A.flags & HHUFF_BLK_CONTINUE) && !cs.reset) s0 = *ts;
         t.start = s0.start;
         t.num = s0.num;
         t.size = s0.size;
@@ -511,12 +533,15 @@ __global__ __launch_bounds__(256) void blk_copy_kernel(BlkArgs A) {
 // Table pass: one wave per connection writes its live entries' bytes, newest first, into the ring the
 // entries do not use now, and points the entries there: the next call (HHUFF_BLK_CONTINUE) reads only
 // scratch.  Live bytes never exceed table_size (each entry costs its bytes + 32 of the capacity).
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void blk_table_kernel(BlkArgs A) {
     const int lane = threadIdx.x & 63;
     const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (c >= A.nconn) return;
+    const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
+    if (cs.refused) return;
     const uint32_t E = tbl_entries(A.table_size);
-    const uint64_t base = c * A.conn_scratch;
+    const uint64_t base = cs.slot * A.conn_scratch;
     TableState* ts = reinterpret_cast<TableState*>(A.scratch + base);
     Entry* ent = reinterpret_cast<Entry*>(A.scratch + base + sizeof(TableState));
     const TableState s = *ts;
@@ -714,11 +739,11 @@ hipError_t launch_hpack_blocks(const uint8_t* in, uint64_t in_size, const uint32
                                uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
                                uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_request_t* req,
                                hhuff_response_t* res, const uint8_t* trailers, uint8_t* scratch, uint32_t flags,
-                               hipStream_t stream) {
+                               hipStream_t stream, const uint32_t* cmap) {
     if (nconn == 0) return hipSuccess;
     BlkArgs A{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
               value_len, fflags, nfields, bstatus, scratch, hpack_conn_scratch(table_size), flags, req,
-              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, res, trailers};
+              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, res, trailers, cmap};
     // workspace (the library's stream-ordered pool): field sources for every slot (block byte);
     // with the literal pre-pass (inputs below 4 GiB: u32 positions) its bitmaps, word prefixes, chunk sums,
     // the literal list and results, and the decoded bytes
@@ -781,14 +806,21 @@ hipError_t launch_hpack_blocks(const uint8_t* in, uint64_t in_size, const uint32
     }
     if (e == hipSuccess) {
         const uint32_t blocks = min((nconn + kBlkThreads - 1u) / kBlkThreads, 65535u);
-        if (req)
-            hipLaunchKernelGGL(hpack_walk_kernel<kWalkReq>, dim3(blocks), dim3(kBlkThreads), 0, stream, A);
-        else if (res)
-            hipLaunchKernelGGL(hpack_walk_kernel<kWalkResp>, dim3(blocks), dim3(kBlkThreads), 0, stream, A);
+        auto walk = [&](auto slots) {  // the kernels' instantiation with or without connection slots
+            constexpr bool S = decltype(slots)::value;
+            if (req)
+                hipLaunchKernelGGL((hpack_walk_kernel<kWalkReq, S>), dim3(blocks), dim3(kBlkThreads), 0, stream, A);
+            else if (res)
+                hipLaunchKernelGGL((hpack_walk_kernel<kWalkResp, S>), dim3(blocks), dim3(kBlkThreads), 0, stream, A);
+            else
+                hipLaunchKernelGGL((hpack_walk_kernel<kWalkPlain, S>), dim3(blocks), dim3(kBlkThreads), 0, stream, A);
+            hipLaunchKernelGGL(blk_copy_kernel, dim3(4096), dim3(256), 0, stream, A);
+            hipLaunchKernelGGL(blk_table_kernel<S>, dim3((uint32_t)(((uint64_t)nconn + 3) / 4)), dim3(256), 0, stream, A);
+        };
+        if (cmap)
+            walk(std::true_type{});
         else
-            hipLaunchKernelGGL(hpack_walk_kernel<kWalkPlain>, dim3(blocks), dim3(kBlkThreads), 0, stream, A);
-        hipLaunchKernelGGL(blk_copy_kernel, dim3(4096), dim3(256), 0, stream, A);
-        hipLaunchKernelGGL(blk_table_kernel, dim3((uint32_t)(((uint64_t)nconn + 3) / 4)), dim3(256), 0, stream, A);
+            walk(std::false_type{});
         e = hipGetLastError();
     }
     const hipError_t f = hipFreeAsync(work, stream);

@@ -20,6 +20,7 @@
 
 #include "hhuff.h"
 #include "hhuff_launch.h"
+#include "hhuff_slots.h"
 
 #define HHUFF_API extern "C" __attribute__((visibility("default")))
 
@@ -204,30 +205,65 @@ HHUFF_API int hhuff_decode_literals(const uint8_t* in, uint64_t in_size, const u
     return f == hipSuccess ? HHUFF_OK : hip_fail(f, "hipFreeAsync");
 }
 
+namespace {
+// A stateful call's connection map (include/hhuff.h (2h)): made on the call's stream before its kernels,
+// released behind them.  Without slots it holds nothing and launches nothing.
+struct ConnMap {
+    uint32_t* cmap = nullptr;
+    hipStream_t stream;
+    explicit ConnMap(hipStream_t s) : stream(s) {}
+    hipError_t make(const hhuff_conn_slots_t* slots, uint32_t nconn) {
+        return hhuff::conn_map_make(slots, nconn, stream, &cmap);
+    }
+    ~ConnMap() {
+        if (cmap) (void)hipFreeAsync(cmap, stream);
+    }
+};
+}  // namespace
+
 HHUFF_API uint64_t hhuff_hpack_scratch_size(uint32_t nconn, uint32_t table_size) {
     return (uint64_t)nconn * hhuff::hpack_conn_scratch(table_size);
 }
 
 namespace {
-int hpack_blocks(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off, const uint32_t* conn_first, uint32_t nconn,
+int hpack_blocks(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                 const uint32_t* blk_off, const uint32_t* conn_first, uint32_t nconn,
                  uint32_t table_size, uint8_t* arena, const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
                  uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* bstatus,
                  hhuff_request_t* req, hhuff_response_t* res, const uint8_t* trailers, void* scratch,
                  uint64_t scratch_size, unsigned flags, void* stream) {
+    if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size, hhuff::hpack_conn_scratch(table_size)))
+        return arg_fail(bad);
     if (nconn == 0) return HHUFF_OK;
     if (!in || !blk_off || !conn_first || !arena || !arena_off || !name_off || !name_len || !value_off || !value_len ||
         !fflags || !nfields || !bstatus || !scratch)
         return arg_fail("NULL array");
-    if (scratch_size < hhuff_hpack_scratch_size(nconn, table_size)) return arg_fail("scratch smaller than hhuff_hpack_scratch_size");
+    if (!slots && scratch_size < hhuff_hpack_scratch_size(nconn, table_size))
+        return arg_fail("scratch smaller than hhuff_hpack_scratch_size");
     if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
     if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
     if (((uintptr_t)res & 3u) != 0) return arg_fail("res must be 4-byte aligned");
-    hipError_t e = hhuff::launch_hpack_blocks(in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off,
-                                              name_len, value_off, value_len, fflags, nfields, bstatus, req, res, trailers,
-                                              (uint8_t*)scratch, flags, (hipStream_t)stream);
+    ConnMap map((hipStream_t)stream);
+    hipError_t e = map.make(slots, nconn);
+    if (e != hipSuccess) return hip_fail(e, "connection slots");
+    e = hhuff::launch_hpack_blocks(in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
+                                   value_off, value_len, fflags, nfields, bstatus, req, res, trailers, (uint8_t*)scratch,
+                                   flags, (hipStream_t)stream, map.cmap);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "hpack block launch");
 }
 }  // namespace
+
+HHUFF_API int hhuff_hpack_decode_blocks_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                              const uint32_t* blk_off,
+                                        const uint32_t* conn_first, uint32_t nconn, uint32_t table_size, uint8_t* arena,
+                                        const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
+                                        uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+                                        int32_t* bstatus, void* scratch, uint64_t scratch_size, unsigned flags,
+                                        void* stream) {
+    return hpack_blocks(slots, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
+                        value_off, value_len, fflags, nfields, bstatus, nullptr, nullptr, nullptr, scratch, scratch_size,
+                        flags, stream);
+}
 
 HHUFF_API int hhuff_hpack_decode_blocks(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off,
                                         const uint32_t* conn_first, uint32_t nconn, uint32_t table_size, uint8_t* arena,
@@ -235,8 +271,21 @@ HHUFF_API int hhuff_hpack_decode_blocks(const uint8_t* in, uint64_t in_size, con
                                         uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
                                         int32_t* bstatus, void* scratch, uint64_t scratch_size, unsigned flags,
                                         void* stream) {
-    return hpack_blocks(in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                        value_off, value_len, fflags, nfields, bstatus, nullptr, nullptr, nullptr, scratch, scratch_size,
+    return hhuff_hpack_decode_blocks_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, arena,
+        arena_off, name_off, name_len, value_off, value_len, fflags, nfields, bstatus, scratch, scratch_size, flags,
+        stream);
+}
+
+HHUFF_API int hhuff_hpack_parse_requests_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                               const uint32_t* blk_off,
+                                         const uint32_t* conn_first, uint32_t nconn, uint32_t table_size, uint8_t* arena,
+                                         const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
+                                         uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+                                         int32_t* bstatus, hhuff_request_t* req, void* scratch, uint64_t scratch_size,
+                                         unsigned flags, void* stream) {
+    if (nconn != 0 && !req) return arg_fail("NULL array");
+    return hpack_blocks(slots, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
+                        value_off, value_len, fflags, nfields, bstatus, req, nullptr, nullptr, scratch, scratch_size,
                         flags, stream);
 }
 
@@ -246,9 +295,21 @@ HHUFF_API int hhuff_hpack_parse_requests(const uint8_t* in, uint64_t in_size, co
                                          uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
                                          int32_t* bstatus, hhuff_request_t* req, void* scratch, uint64_t scratch_size,
                                          unsigned flags, void* stream) {
-    if (nconn != 0 && !req) return arg_fail("NULL array");
-    return hpack_blocks(in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                        value_off, value_len, fflags, nfields, bstatus, req, nullptr, nullptr, scratch, scratch_size,
+    return hhuff_hpack_parse_requests_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, arena,
+        arena_off, name_off, name_len, value_off, value_len, fflags, nfields, bstatus, req, scratch, scratch_size,
+        flags, stream);
+}
+
+HHUFF_API int hhuff_hpack_parse_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                                const uint32_t* blk_off,
+                                          const uint32_t* conn_first, uint32_t nconn, uint32_t table_size,
+                                          const uint8_t* trailers, uint8_t* arena, const uint64_t* arena_off,
+                                          uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
+                                          uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_response_t* res,
+                                          void* scratch, uint64_t scratch_size, unsigned flags, void* stream) {
+    if (nconn != 0 && !res) return arg_fail("NULL array");
+    return hpack_blocks(slots, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
+                        value_off, value_len, fflags, nfields, bstatus, nullptr, res, trailers, scratch, scratch_size,
                         flags, stream);
 }
 
@@ -258,13 +319,41 @@ HHUFF_API int hhuff_hpack_parse_responses(const uint8_t* in, uint64_t in_size, c
                                           uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
                                           uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_response_t* res,
                                           void* scratch, uint64_t scratch_size, unsigned flags, void* stream) {
-    if (nconn != 0 && !res) return arg_fail("NULL array");
-    return hpack_blocks(in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                        value_off, value_len, fflags, nfields, bstatus, nullptr, res, trailers, scratch, scratch_size,
-                        flags, stream);
+    return hhuff_hpack_parse_responses_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, trailers,
+        arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, bstatus, res, scratch,
+        scratch_size, flags, stream);
 }
 
 HHUFF_API uint64_t hhuff_hpack_enc_scratch_size(uint32_t nconn) { return (uint64_t)nconn * hhuff::hpenc_conn_scratch(); }
+
+HHUFF_API int hhuff_hpack_flatten_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                                  const hhuff_hpack_header_t* hdr,
+                                            uint32_t nhdr, const hhuff_hpack_response_t* res, const uint32_t* conn_first,
+                                            uint32_t nconn, uint32_t nres, uint32_t server_off, uint32_t server_len,
+                                            uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                                            uint32_t* headers_size, int32_t* rstatus, void* scratch, uint64_t scratch_size,
+                                            unsigned flags, void* stream) {
+    if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size, hhuff::hpenc_conn_scratch()))
+        return arg_fail(bad);
+    if (nconn == 0) return HHUFF_OK;
+    if (!conn_first || !scratch || (nres && (!res || !out || !out_off || !out_len || !headers_size || !rstatus)) ||
+        (nhdr && (!hdr || !in)))
+        return arg_fail("NULL array");
+    if (in_size >= (1ull << 32)) return arg_fail("in_size must stay below 2^32 (u32 offsets)");
+    if (!slots && scratch_size < hhuff_hpack_enc_scratch_size(nconn))
+        return arg_fail("scratch smaller than hhuff_hpack_enc_scratch_size");
+    if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
+    if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)hdr & 3u) != 0 || ((uintptr_t)out_off & 7u) != 0)
+        return arg_fail("misaligned hdr / res / out_off");
+    hhuff::HpeCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, server_off, server_len,
+                              out, out_off, out_len, headers_size, rstatus, (uint8_t*)scratch, flags, nullptr};
+    ConnMap map((hipStream_t)stream);
+    hipError_t e = map.make(slots, nconn);
+    if (e != hipSuccess) return hip_fail(e, "connection slots");
+    call.cmap = map.cmap;
+    e = hhuff::launch_hpack_flatten(call, (hipStream_t)stream);
+    return e == hipSuccess ? HHUFF_OK : hip_fail(e, "hpack flatten launch");
+}
 
 HHUFF_API int hhuff_hpack_flatten_responses(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr,
                                             uint32_t nhdr, const hhuff_hpack_response_t* res, const uint32_t* conn_first,
@@ -272,19 +361,8 @@ HHUFF_API int hhuff_hpack_flatten_responses(const uint8_t* in, uint64_t in_size,
                                             uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
                                             uint32_t* headers_size, int32_t* rstatus, void* scratch, uint64_t scratch_size,
                                             unsigned flags, void* stream) {
-    if (nconn == 0) return HHUFF_OK;
-    if (!conn_first || !scratch || (nres && (!res || !out || !out_off || !out_len || !headers_size || !rstatus)) ||
-        (nhdr && (!hdr || !in)))
-        return arg_fail("NULL array");
-    if (in_size >= (1ull << 32)) return arg_fail("in_size must stay below 2^32 (u32 offsets)");
-    if (scratch_size < hhuff_hpack_enc_scratch_size(nconn)) return arg_fail("scratch smaller than hhuff_hpack_enc_scratch_size");
-    if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
-    if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)hdr & 3u) != 0 || ((uintptr_t)out_off & 7u) != 0)
-        return arg_fail("misaligned hdr / res / out_off");
-    const hhuff::HpeCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, server_off, server_len,
-                              out, out_off, out_len, headers_size, rstatus, (uint8_t*)scratch, flags};
-    hipError_t e = hhuff::launch_hpack_flatten(call, (hipStream_t)stream);
-    return e == hipSuccess ? HHUFF_OK : hip_fail(e, "hpack flatten launch");
+    return hhuff_hpack_flatten_responses_slots(nullptr, in, in_size, hdr, nhdr, res, conn_first, nconn, nres,
+        server_off, server_len, out, out_off, out_len, headers_size, rstatus, scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API int hhuff_qpack_flatten_responses(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr,
@@ -306,7 +384,8 @@ HHUFF_API uint64_t hhuff_qpack_enc_scratch_size(uint32_t nconn, uint32_t header_
     return (uint64_t)nconn * hhuff::qpenc_conn_scratch(header_table_size, max_inflight);
 }
 
-HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr, uint32_t nhdr,
+HHUFF_API int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                                 const hhuff_hpack_header_t* hdr, uint32_t nhdr,
                                            const hhuff_qpack_response_t* res, const uint32_t* conn_first, uint32_t nconn,
                                            uint32_t nres, const uint64_t* stream_id, const uint32_t* dec_off,
                                            const uint32_t* dec_len, uint32_t header_table_size, uint64_t max_blocked,
@@ -327,24 +406,46 @@ HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, 
         arg_fail("HHUFF_QENC_DUP needs HHUFF_QENC_EVICT");
         return HHUFF_RES_EINVAL;
     }
+    if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size,
+                                                  hhuff::qpenc_conn_scratch(header_table_size, max_inflight)))
+        return arg_fail(bad);
     if (nconn == 0) return HHUFF_OK;
     if (!conn_first || !scratch || !enc_out || !enc_out_off || !enc_out_len || !dec_status || !dec_consumed ||
         (nres && (!res || !stream_id || !out || !out_off || !out_len || !header_len || !rstatus || !rflags)) ||
         (nhdr && !hdr) || ((nhdr || dec_off || server_len) && !in) || ((dec_off == nullptr) != (dec_len == nullptr)))
         return arg_fail("NULL array");
     if (in_size >= (1ull << 32)) return arg_fail("in_size must stay below 2^32 (u32 offsets)");
-    if (scratch_size < hhuff_qpack_enc_scratch_size(nconn, header_table_size, max_inflight))
+    if (!slots && scratch_size < hhuff_qpack_enc_scratch_size(nconn, header_table_size, max_inflight))
         return arg_fail("scratch smaller than hhuff_qpack_enc_scratch_size");
     if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
     if (((uintptr_t)res & 7u) != 0 || ((uintptr_t)hdr & 3u) != 0 || ((uintptr_t)out_off & 7u) != 0 ||
         ((uintptr_t)enc_out_off & 7u) != 0 || ((uintptr_t)stream_id & 7u) != 0)
         return arg_fail("misaligned hdr / res / out_off / enc_out_off / stream_id");
-    const hhuff::QseCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, stream_id, dec_off, dec_len,
+    hhuff::QseCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, stream_id, dec_off, dec_len,
                               header_table_size, max_blocked, max_inflight, server_off, server_len, out, out_off, out_len,
                               header_len, rstatus, rflags, enc_out, enc_out_off, enc_out_len, dec_status, dec_consumed,
-                              (uint8_t*)scratch, flags};
-    hipError_t e = hhuff::launch_qpack_sessions(call, (hipStream_t)stream);
+                              (uint8_t*)scratch, flags, nullptr};
+    ConnMap map((hipStream_t)stream);
+    hipError_t e = map.make(slots, nconn);
+    if (e != hipSuccess) return hip_fail(e, "connection slots");
+    call.cmap = map.cmap;
+    e = hhuff::launch_qpack_sessions(call, (hipStream_t)stream);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack sessions launch");
+}
+
+HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr, uint32_t nhdr,
+                                           const hhuff_qpack_response_t* res, const uint32_t* conn_first, uint32_t nconn,
+                                           uint32_t nres, const uint64_t* stream_id, const uint32_t* dec_off,
+                                           const uint32_t* dec_len, uint32_t header_table_size, uint64_t max_blocked,
+                                           uint32_t max_inflight, uint32_t server_off, uint32_t server_len, uint8_t* out,
+                                           const uint64_t* out_off, uint32_t* out_len, uint32_t* header_len,
+                                           int32_t* rstatus, uint8_t* rflags, uint8_t* enc_out, const uint64_t* enc_out_off,
+                                           uint32_t* enc_out_len, int32_t* dec_status, uint32_t* dec_consumed, void* scratch,
+                                           uint64_t scratch_size, unsigned flags, void* stream) {
+    return hhuff_qpack_flatten_sessions_slots(nullptr, in, in_size, hdr, nhdr, res, conn_first, nconn, nres,
+        stream_id, dec_off, dec_len, header_table_size, max_blocked, max_inflight, server_off, server_len, out,
+        out_off, out_len, header_len, rstatus, rflags, enc_out, enc_out_off, enc_out_len, dec_status, dec_consumed,
+        scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API uint64_t hhuff_qpack_scratch_size(uint32_t nconn, uint32_t header_table_size) {
@@ -352,7 +453,8 @@ HHUFF_API uint64_t hhuff_qpack_scratch_size(uint32_t nconn, uint32_t header_tabl
 }
 
 namespace {
-int qpack_step(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, const uint32_t* enc_len,
+int qpack_step(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+               const uint32_t* enc_off, const uint32_t* enc_len,
                const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
                uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked, uint8_t* arena,
                const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
@@ -360,6 +462,9 @@ int qpack_step(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, con
                int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count, const uint64_t* stream_id,
                hhuff_qpack_request_t* req, hhuff_qpack_response_head_t* res, void* scratch, uint64_t scratch_size,
                unsigned flags, void* stream) {
+    if (slots && header_table_size > (1u << 30)) return arg_fail("header_table_size above 2^30");
+    if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size, hhuff::qpack_conn_scratch(header_table_size)))
+        return arg_fail(bad);
     if (nconn == 0) return HHUFF_OK;
     if (!in || !enc_off || !enc_len || !sec_off || !conn_first || !enc_status || !enc_consumed || !insert_count ||
         !scratch)
@@ -370,17 +475,34 @@ int qpack_step(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, con
     if (header_table_size > (1u << 30)) return arg_fail("header_table_size above 2^30");
     // u32 offsets, and the literal workspace is sized for in_size + 2 literals in 32 bits
     if (in_size > (1ull << 32) - 3) return arg_fail("in_size must be at most 2^32 - 3 (u32 offsets)");
-    if (scratch_size < hhuff_qpack_scratch_size(nconn, header_table_size))
+    if (!slots && scratch_size < hhuff_qpack_scratch_size(nconn, header_table_size))
         return arg_fail("scratch smaller than hhuff_qpack_scratch_size");
     if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
-    hipError_t e = hhuff::launch_qpack(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
-                                       header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len,
-                                       value_off, value_len, fflags, nfields, sstatus, req_insert_count, enc_status,
-                                       enc_consumed, insert_count, (uint8_t*)scratch, flags, (hipStream_t)stream,
-                                       stream_id, req, res);
+    ConnMap map((hipStream_t)stream);
+    hipError_t e = map.make(slots, nconn);
+    if (e != hipSuccess) return hip_fail(e, "connection slots");
+    e = hhuff::launch_qpack(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
+                            num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                            req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                            (hipStream_t)stream, stream_id, req, res, map.cmap);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack launch");
 }
 }  // namespace
+
+HHUFF_API int hhuff_qpack_decode_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                       const uint32_t* enc_off, const uint32_t* enc_len,
+                                 const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
+                                 uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked,
+                                 uint8_t* arena, const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
+                                 uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+                                 int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status,
+                                 uint32_t* enc_consumed, uint64_t* insert_count, void* scratch, uint64_t scratch_size,
+                                 unsigned flags, void* stream) {
+    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
+                      num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                      req_insert_count, enc_status, enc_consumed, insert_count, nullptr, nullptr, nullptr, scratch,
+                      scratch_size, flags, stream);
+}
 
 HHUFF_API int hhuff_qpack_decode(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, const uint32_t* enc_len,
                                  const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
@@ -390,9 +512,27 @@ HHUFF_API int hhuff_qpack_decode(const uint8_t* in, uint64_t in_size, const uint
                                  int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status,
                                  uint32_t* enc_consumed, uint64_t* insert_count, void* scratch, uint64_t scratch_size,
                                  unsigned flags, void* stream) {
-    return qpack_step(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
+    return hhuff_qpack_decode_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
+        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len,
+        fflags, nfields, sstatus, req_insert_count, enc_status, enc_consumed, insert_count, scratch, scratch_size,
+        flags, stream);
+}
+
+HHUFF_API int hhuff_qpack_parse_requests_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                               const uint32_t* enc_off,
+                                         const uint32_t* enc_len, const uint32_t* sec_off, const uint32_t* conn_first,
+                                         uint32_t nconn, uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked,
+                                         const uint32_t* num_blocked, uint8_t* arena, const uint64_t* arena_off,
+                                         uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
+                                         uint8_t* fflags, uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
+                                         int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
+                                         const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch,
+                                         uint64_t scratch_size, unsigned flags, void* stream) {
+    if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
+    if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
+    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
                       num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, nullptr, nullptr, nullptr, scratch,
+                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, nullptr, scratch,
                       scratch_size, flags, stream);
 }
 
@@ -405,11 +545,27 @@ HHUFF_API int hhuff_qpack_parse_requests(const uint8_t* in, uint64_t in_size, co
                                          int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                                          const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch,
                                          uint64_t scratch_size, unsigned flags, void* stream) {
-    if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
-    if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
-    return qpack_step(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
+    return hhuff_qpack_parse_requests_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
+        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len,
+        fflags, nfields, sstatus, req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, scratch,
+        scratch_size, flags, stream);
+}
+
+HHUFF_API int hhuff_qpack_parse_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                                const uint32_t* enc_off,
+                                          const uint32_t* enc_len, const uint32_t* sec_off, const uint32_t* conn_first,
+                                          uint32_t nconn, uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked,
+                                          const uint32_t* num_blocked, uint8_t* arena, const uint64_t* arena_off,
+                                          uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
+                                          uint8_t* fflags, uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
+                                          int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
+                                          const uint64_t* stream_id, hhuff_qpack_response_head_t* res, void* scratch,
+                                          uint64_t scratch_size, unsigned flags, void* stream) {
+    if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
+    if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
+    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
                       num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, nullptr, scratch,
+                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, nullptr, res, scratch,
                       scratch_size, flags, stream);
 }
 
@@ -422,12 +578,10 @@ HHUFF_API int hhuff_qpack_parse_responses(const uint8_t* in, uint64_t in_size, c
                                           int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                                           const uint64_t* stream_id, hhuff_qpack_response_head_t* res, void* scratch,
                                           uint64_t scratch_size, unsigned flags, void* stream) {
-    if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
-    if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
-    return qpack_step(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                      num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, nullptr, res, scratch,
-                      scratch_size, flags, stream);
+    return hhuff_qpack_parse_responses_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
+        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len,
+        fflags, nfields, sstatus, req_insert_count, enc_status, enc_consumed, insert_count, stream_id, res, scratch,
+        scratch_size, flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "hhuff_enc.h"
+#include "hhuff_slots.h"
 
 namespace hhuff {
 namespace {
@@ -386,21 +387,24 @@ __device__ uint32_t hpe_field(const HpeArgs& A, EncTable& t, const FieldIn& F, u
 }  // namespace
 
 // 2. the walk: one lane per connection, its responses in order
+template <bool SLOTS>
 __global__ __launch_bounds__(64) void hpe_table_kernel(HpeArgs A) {
     __shared__ uint4 s_meta[kMaxEntries * 64];
     const uint32_t lane = threadIdx.x;
     const uint64_t c = (uint64_t)blockIdx.x * 64u + lane;
     if (c >= A.nconn) return;
-    uint8_t* scr = A.scratch + c * kConnScratch;
+    // a refused connection (hhuff_slots.h) has no slab: scr is never dereferenced, its responses are refused
+    const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
+    uint8_t* scr = A.scratch + cs.slot * kConnScratch;
     EncState* ts = reinterpret_cast<EncState*>(scr);
     EncState s0{0u, 0u, 0u, 0u, 0u, kInitialCap, 0u, 0u};
-    if (A.flags & HHUFF_ENC_CONTINUE) s0 = *ts;
+    if ((A.flags & HHUFF_ENC_CONTINUE) && !cs.reset && !cs.refused) s0 = *ts;
     EncTable t{reinterpret_cast<EncEntry*>(scr + sizeof(EncState)), s_meta + lane, s0.start, s0.num, s0.size, s0.cap};
     for (uint32_t k = 0; k < t.num; ++k) {
         const EncEntry& e = t.ent[t.slot(k)];
         t.meta[t.slot(k) * 64] = make_uint4(e.nl | (e.tok << 31), e.vl, e.nh, e.vh);
     }
-    bool failed = s0.failed != 0;
+    bool failed = s0.failed != 0 || cs.refused;
     const uint4 srv_rc = A.rec[A.nhdr];
     const uint32_t srv_info = A.info[A.nhdr];
     // a malformed conn_first cannot send the walk past the response array
@@ -426,7 +430,7 @@ __global__ __launch_bounds__(64) void hpe_table_kernel(HpeArgs A) {
         const uint32_t own_end = request ? h0 + R.status : h0;  // a request's own fields: method .. expect
         int32_t st = 0;
         if (failed) {
-            st = HHUFF_RES_SKIPPED;
+            st = cs.refused ? HHUFF_RES_EINVAL : HHUFF_RES_SKIPPED;
         } else if ((uint64_t)R.hdr_first + R.nhdr > A.nhdr || limit < base ||  // header range / region malformed
                    (head && (R.status < 100 || R.status > 999)) || (request && R.status > R.nhdr) ||
                    ((R.flags & HHUFF_RES_PUSH_PROMISE) && (R.flags & (HHUFF_RES_TRAILERS | HHUFF_RES_REQUEST))) ||
@@ -503,7 +507,7 @@ __global__ __launch_bounds__(64) void hpe_table_kernel(HpeArgs A) {
         base = base_n;
         limit = limit_n;
     }
-    *ts = EncState{t.start, t.num, s0.ring, failed ? 1u : 0u, t.size, t.cap, 0u, 0u};
+    if (!cs.refused) *ts = EncState{t.start, t.num, s0.ring, failed ? 1u : 0u, t.size, t.cap, 0u, 0u};
 }
 
 namespace {
@@ -645,11 +649,14 @@ __global__ __launch_bounds__(256) void hpe_frames_kernel(HpeArgs A) {
 
 // 5. the table pass: one wave per connection writes its live entries' bytes, newest first, into the ring
 //    they do not use now and points the entries there (as blk_table_kernel does for the decoder)
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void hpe_ring_kernel(HpeArgs A) {
     const int lane = threadIdx.x & 63;
     const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (c >= A.nconn) return;
-    const uint64_t base = c * kConnScratch;
+    const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
+    if (cs.refused) return;
+    const uint64_t base = cs.slot * kConnScratch;
     EncState* ts = reinterpret_cast<EncState*>(A.scratch + base);
     EncEntry* ent = reinterpret_cast<EncEntry*>(A.scratch + base + sizeof(EncState));
     const EncState s = *ts;
@@ -728,11 +735,17 @@ hipError_t launch_hpack_flatten(const HpeCall& call, hipStream_t stream) {
     const uint32_t ge = (uint32_t)std::min<uint64_t>(((uint64_t)nhdr + nres + 255u) / 256u, 16384ull);
     HHUFF_LAUNCH(e, hpe_prep_kernel, gp, 256, stream, A);
     if (e == hipSuccess) e = launch_long_bits(true, A.in, A.hdr, nhdr, A.server_off, A.server_len, A.rec, A.lw, stream);
-    HHUFF_LAUNCH(e, hpe_table_kernel, (nconn + 63u) / 64u, 64, stream, A);
+    if (A.cmap)  // (the instantiations with and without connection slots, hhuff_slots.h)
+        HHUFF_LAUNCH(e, hpe_table_kernel<true>, (nconn + 63u) / 64u, 64, stream, A);
+    else
+        HHUFF_LAUNCH(e, hpe_table_kernel<false>, (nconn + 63u) / 64u, 64, stream, A);
     if ((uint64_t)nhdr + nres != 0) HHUFF_LAUNCH(e, hpe_emit_kernel, ge, 256, stream, A);
     if (e == hipSuccess) e = launch_long_payload(A.in, A.lw, stream);
     if (nres != 0) HHUFF_LAUNCH(e, hpe_frames_kernel, std::min(nres, 512u), 256, stream, A);
-    HHUFF_LAUNCH(e, hpe_ring_kernel, (nconn + 3u) / 4u, 256, stream, A);
+    if (A.cmap)
+        HHUFF_LAUNCH(e, hpe_ring_kernel<true>, (nconn + 3u) / 4u, 256, stream, A);
+    else
+        HHUFF_LAUNCH(e, hpe_ring_kernel<false>, (nconn + 3u) / 4u, 256, stream, A);
     const hipError_t f = hipFreeAsync(ws, stream);
     return e != hipSuccess ? e : f;
 }

@@ -124,6 +124,7 @@ struct HpeCall {
     int32_t* rstatus;
     uint8_t* scratch;
     uint32_t flags;
+    const uint32_t* cmap;  // connection slots (hhuff_slots.h); NULL: connection c in slot c
 };
 uint64_t hpenc_conn_scratch();
 hipError_t launch_hpack_flatten(const HpeCall& call, hipStream_t stream);
@@ -173,19 +174,20 @@ struct QseCall {
     uint32_t* dec_consumed;
     uint8_t* scratch;
     uint32_t flags;
+    const uint32_t* cmap;  // connection slots (hhuff_slots.h); NULL: connection c in slot c
 };
 uint64_t qpenc_conn_scratch(uint32_t header_table_size, uint32_t max_inflight);
 hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream);
 
 // HPACK header blocks (f4): see include/hhuff.h hhuff_hpack_decode_blocks; scratch = nconn x
-// hpack_conn_scratch(table_size) bytes of device memory
+// hpack_conn_scratch(table_size) bytes of device memory (with cmap: one slab per slot)
 uint64_t hpack_conn_scratch(uint32_t table_size);
 hipError_t launch_hpack_blocks(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off, const uint32_t* conn_first,
                                uint32_t nconn, uint32_t table_size, uint8_t* arena, const uint64_t* arena_off,
                                uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
                                uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_request_t* req,
                                hhuff_response_t* res, const uint8_t* trailers, uint8_t* scratch, uint32_t flags,
-                               hipStream_t stream);
+                               hipStream_t stream, const uint32_t* cmap = nullptr);
 // QPACK decoder (f4): see include/hhuff.h hhuff_qpack_decode; scratch = nconn x
 // qpack_conn_scratch(header_table_size) bytes of device memory
 uint64_t qpack_conn_scratch(uint32_t header_table_size);
@@ -196,7 +198,8 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
                         uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus,
                         uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                         uint8_t* scratch, uint32_t flags, hipStream_t stream, const uint64_t* stream_id = nullptr,
-                        hhuff_qpack_request_t* qreq = nullptr, hhuff_qpack_response_head_t* qres = nullptr);
+                        hhuff_qpack_request_t* qreq = nullptr, hhuff_qpack_response_head_t* qres = nullptr,
+                        const uint32_t* cmap = nullptr);
 int grid_size(int device, int which);
 // the staged / stream prices (ps per string, per byte) a mixed-length decode on `device` uses: the fitted
 // defaults, pinned values, or (calibrate != 0: measured now, synchronously) this device's own

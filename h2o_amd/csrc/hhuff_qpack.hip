@@ -29,11 +29,13 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "hhuff_device.h"
 #include "hhuff.h"
 #include "hhuff_launch.h"
 #include "hhuff_request.h"
+#include "hhuff_slots.h"
 
 namespace hhuff {
 namespace {
@@ -92,6 +94,7 @@ struct QpkArgs {
     hhuff_qpack_request_t* qreq;
     // h2o_qpack_parse_response mode (hhuff_qpack_parse_responses): per section its record (and stream_id)
     hhuff_qpack_response_head_t* qres;
+    const uint32_t* cmap;  // connection slots (hhuff_slots.h); NULL: connection c in slot c
 };
 
 // Byte sources of table entries and field strings: kind in the top 3 bits, offset below.  Every source stays
@@ -413,8 +416,8 @@ Exit:
     return ret;
 }
 
-__device__ __forceinline__ QTable q_table(const QpkArgs& A, uint64_t c) {
-    uint8_t* scr = A.scratch + c * A.conn_scratch;
+__device__ __forceinline__ QTable q_table(const QpkArgs& A, uint64_t slot) {  // the table in slab `slot`
+    uint8_t* scr = A.scratch + slot * A.conn_scratch;
     QTable t{reinterpret_cast<QEntry*>(scr + sizeof(QState)), qpk_entries(A.T), {}};
     t.s = *reinterpret_cast<const QState*>(scr);
     return t;
@@ -428,6 +431,7 @@ __device__ __forceinline__ void load_dec_tables(uint32_t* s_lut, uint32_t* s_kin
     __syncthreads();
 }
 
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void qpack_encoder_kernel(QpkArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
     __shared__ uint32_t s_kinfo[32];
@@ -438,14 +442,21 @@ __global__ __launch_bounds__(256) void qpack_encoder_kernel(QpkArgs A) {
     T.kinfo = s_kinfo;
     T.ones = s_ones;
     for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < A.nconn; c += (uint64_t)gridDim.x * blockDim.x) {
-        QState* ps = reinterpret_cast<QState*>(A.scratch + c * A.conn_scratch);
-        if (!(A.flags & HHUFF_QPK_CONTINUE)) {  // h2o_qpack_create_decoder (:240-252)
+        const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
+        if (cs.refused) {  // no slab of its own: nothing of its encoder stream is taken
+            A.enc_status[c] = HHUFF_QPK_EINVAL;
+            A.enc_consumed[c] = 0;
+            A.insert_count[c] = 0;
+            continue;
+        }
+        QState* ps = reinterpret_cast<QState*>(A.scratch + cs.slot * A.conn_scratch);
+        if (!(A.flags & HHUFF_QPK_CONTINUE) || cs.reset) {  // h2o_qpack_create_decoder (:240-252)
             QState s0{};
             s0.base_offset = 1;
             s0.max_size = A.T;
             *ps = s0;
         }
-        QTable t = q_table(A, c);
+        QTable t = q_table(A, cs.slot);
         t.s.dirty = 0;
         int32_t st = 0;
         uint32_t consumed = 0;
@@ -467,11 +478,14 @@ __global__ __launch_bounds__(256) void qpack_encoder_kernel(QpkArgs A) {
 // Table pass: one wave per connection whose table took entries this call writes the live entries' bytes,
 // oldest first, back to back into the ring they do not use now and points the entries there; the field
 // sections (and the next call, HHUFF_QPK_CONTINUE) read only scratch.
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void qpack_table_kernel(QpkArgs A) {
     const int lane = threadIdx.x & 63;
     const uint64_t c = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (c >= A.nconn) return;
-    const uint64_t base = c * A.conn_scratch;
+    const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
+    if (cs.refused) return;
+    const uint64_t base = cs.slot * A.conn_scratch;
     QState* ps = reinterpret_cast<QState*>(A.scratch + base);
     const QState s = *ps;
     if (!s.dirty) return;
@@ -753,7 +767,7 @@ constexpr int kSecPlain = 0, kSecReq = 1, kSecResp = 2;  // qpack_sections_kerne
 // normalised to DECOMPRESSION_FAILED (:852-853), and the record gets the Section Acknowledgment (:856).
 // RESP: h2o_qpack_parse_response (:860-882) as lib/common/http3client.c:542 calls it -- a response head,
 // h2o_hpack_parse_response's rules (a status and a datagram-flow-id out-parameter), the same normalisation
-template <int MODE>
+template <int MODE, bool SLOTS>
 __global__ __launch_bounds__(256) void qpack_sections_kernel(QpkArgs A) {
     constexpr bool REQ = MODE == kSecReq, RESP = MODE == kSecResp;
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
@@ -775,13 +789,20 @@ __global__ __launch_bounds__(256) void qpack_sections_kernel(QpkArgs A) {
             else
                 hi = mid;
         }
-        const QTable t = q_table(A, lo);
+        const ConnSlot cs = conn_slot<SLOTS>(A.cmap, lo);
         A.nfields[k] = 0;
         A.req_insert_count[k] = 0;
         ReqState rq;
         RespState rs;
         if (REQ) rq.reset();
         if (RESP) rs.reset(false);
+        if (cs.refused) {  // its connection has no slab: no table is read
+            A.sstatus[k] = HHUFF_QPK_EINVAL;
+            if (REQ) q_req_store(A.qreq + k, rq, HHUFF_QPK_EINVAL, 0u, 0u);
+            if (RESP) q_res_store(A.qres + k, rs, HHUFF_QPK_EINVAL, 0u, 0u);
+            continue;
+        }
+        const QTable t = q_table(A, cs.slot);
         if (t.s.failed) {
             A.sstatus[k] = HHUFF_QPK_SKIPPED;
             if (REQ) q_req_store(A.qreq + k, rq, HHUFF_QPK_SKIPPED, 0u, 0u);
@@ -965,12 +986,12 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
                         uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus,
                         uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                         uint8_t* scratch, uint32_t flags, hipStream_t stream, const uint64_t* stream_id,
-                        hhuff_qpack_request_t* qreq, hhuff_qpack_response_head_t* qres) {
+                        hhuff_qpack_request_t* qreq, hhuff_qpack_response_head_t* qres, const uint32_t* cmap) {
     if (nconn == 0) return hipSuccess;
     QpkArgs A{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
               max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
               req_insert_count, enc_status, enc_consumed, insert_count, scratch, qpack_conn_scratch(header_table_size),
-              flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream_id, qreq, qres};
+              flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream_id, qreq, qres, cmap};
     // workspace: the literal pre-pass's bitmaps, word prefixes, chunk sums, the literal list with each
     // literal's prefix, the literal kernels' results and decoded bytes (positions are u32: in_size < 2^32,
     // checked by the C ABI), and the field slots' byte sources
@@ -1021,23 +1042,24 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
         A.fsrc_n = reinterpret_cast<uint64_t*>(work + o_fsn);
         A.fsrc_v = reinterpret_cast<uint64_t*>(work + o_fsv);
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(qpack_encoder_kernel, dim3(std::min((nconn + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
-        hipLaunchKernelGGL(qpack_table_kernel, dim3((uint32_t)(((uint64_t)nconn + 3) / 4)), dim3(256), 0, stream, A);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && nsec != 0) {
+    auto step = [&](auto slots) {  // the kernels' instantiation with or without connection slots
+        constexpr bool S = decltype(slots)::value;
+        hipLaunchKernelGGL(qpack_encoder_kernel<S>, dim3(std::min((nconn + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
+        hipLaunchKernelGGL(qpack_table_kernel<S>, dim3((uint32_t)(((uint64_t)nconn + 3) / 4)), dim3(256), 0, stream, A);
+        hipError_t f = hipGetLastError();
+        if (f != hipSuccess || nsec == 0) return f;
+        const dim3 gs(std::min((nsec + 255u) / 256u, 65535u));
         if (qres)
-            hipLaunchKernelGGL(qpack_sections_kernel<kSecResp>, dim3(std::min((nsec + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
+            hipLaunchKernelGGL((qpack_sections_kernel<kSecResp, S>), gs, dim3(256), 0, stream, A);
         else if (qreq)
-            hipLaunchKernelGGL(qpack_sections_kernel<kSecReq>, dim3(std::min((nsec + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
+            hipLaunchKernelGGL((qpack_sections_kernel<kSecReq, S>), gs, dim3(256), 0, stream, A);
         else
-            hipLaunchKernelGGL(qpack_sections_kernel<kSecPlain>, dim3(std::min((nsec + 255u) / 256u, 65535u)), dim3(256), 0,
-                               stream, A);
+            hipLaunchKernelGGL((qpack_sections_kernel<kSecPlain, S>), gs, dim3(256), 0, stream, A);
         hipLaunchKernelGGL(qpack_copy_kernel, dim3(std::min((nsec + 255u) / 256u, 4096u)), dim3(256), 0, stream, A);
         hipLaunchKernelGGL(qpack_blocked_kernel, dim3(std::min((nconn + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
-        e = hipGetLastError();
-    }
+        return hipGetLastError();
+    };
+    if (e == hipSuccess) e = cmap ? step(std::true_type{}) : step(std::false_type{});
     if (work) {
         const hipError_t f = hipFreeAsync(work, stream);
         if (e == hipSuccess) e = f;

@@ -8,9 +8,11 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "hhuff_enc.h"
 #include "hhuff_qtable.h"
+#include "hhuff_slots.h"
 
 namespace hhuff {
 namespace {
@@ -772,22 +774,24 @@ __device__ __forceinline__ uint64_t qs_response_bound(uint64_t name_value_bytes,
 // the walk: one lane per connection -- its decoder stream, then its responses in order.  EV: the session evicts
 // (HHUFF_QENC_EVICT), DUP: it also duplicates draining entries (HHUFF_QENC_DUP, with EV only); <false, false> is
 // the table that only grows.
-template <bool EV, bool DUP>
+template <bool EV, bool DUP, bool SLOTS>
 __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     static_assert(EV || !DUP, "HHUFF_QENC_DUP is a mode of the evicting table");
     const QseCall& C = A.c;
     const uint64_t c = (uint64_t)blockIdx.x * 64u + threadIdx.x;
     if (c >= C.nconn) return;
     const uint32_t H = C.header_table_size, M = C.max_inflight;
-    uint8_t* scr = C.scratch + c * qs_conn_scratch(H, M);
+    // a refused connection (hhuff_slots.h) has no slab: scr is never dereferenced, the call touches nothing of it
+    const ConnSlot cs = conn_slot<SLOTS>(C.cmap, c);
+    uint8_t* scr = C.scratch + cs.slot * qs_conn_scratch(H, M);
     QsState* ts = reinterpret_cast<QsState*>(scr);
     QsConn t;
     t.s = QsState{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    const bool fresh = !(C.flags & HHUFF_QENC_CONTINUE);
-    if (!fresh) t.s = *ts;
+    const bool fresh = !(C.flags & HHUFF_QENC_CONTINUE) || cs.reset;
+    if (!fresh && !cs.refused) t.s = *ts;
     // a session is evicting or it is not, duplicating or not: another kind of call touches nothing of it
     constexpr uint32_t kMode = (EV ? kQsEvicting : 0u) | (DUP ? kQsDuplicating : 0u);
-    const bool wrong = !fresh && (t.s.failed & (kQsEvicting | kQsDuplicating)) != kMode;
+    const bool wrong = cs.refused || (!fresh && (t.s.failed & (kQsEvicting | kQsDuplicating)) != kMode);
     t.s.failed &= 1u;
     t.ent = reinterpret_cast<QsEntry*>(scr + sizeof(QsState));
     t.inf = reinterpret_cast<QsInflight*>(scr + sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry));
@@ -816,7 +820,7 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     const uint64_t room = eend > ebase ? eend - ebase : 0ull;
     uint64_t enc_len = 0;
     bool setcap = false, nospace = false;
-    if (!t.s.failed && fresh && (C.flags & HHUFF_QENC_SET_CAPACITY)) {
+    if (!wrong && !t.s.failed && fresh && (C.flags & HHUFF_QENC_SET_CAPACITY)) {
         const uint32_t n = int_len(H, 5);
         if (n > room)
             nospace = true;  // not even the capacity instruction fits: nothing of this step is written
@@ -1122,13 +1126,20 @@ hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream) {
     const uint32_t ge = (uint32_t)std::min<uint64_t>((2ull * nhdr + nres + nconn + 255u) / 256u, 16384ull);
     HHUFF_LAUNCH(e, qse_prep_kernel, gp, 256, stream, A);
     if (e == hipSuccess) e = launch_long_bits(true, call.in, call.hdr, nhdr, call.server_off, call.server_len, A.rec, A.lw, stream);
-    if (call.flags & HHUFF_QENC_DUP) {  // (only with HHUFF_QENC_EVICT: the C entry refuses it alone)
-        HHUFF_LAUNCH(e, (qse_walk_kernel<true, true>), (nconn + 63u) / 64u, 64, stream, A);
-    } else if (call.flags & HHUFF_QENC_EVICT) {
-        HHUFF_LAUNCH(e, (qse_walk_kernel<true, false>), (nconn + 63u) / 64u, 64, stream, A);
-    } else {
-        HHUFF_LAUNCH(e, (qse_walk_kernel<false, false>), (nconn + 63u) / 64u, 64, stream, A);
-    }
+    auto walk = [&](auto slots) {  // the kernel's instantiation with or without connection slots (hhuff_slots.h)
+        constexpr bool S = decltype(slots)::value;
+        if (call.flags & HHUFF_QENC_DUP) {  // (only with HHUFF_QENC_EVICT: the C entry refuses it alone)
+            HHUFF_LAUNCH(e, (qse_walk_kernel<true, true, S>), (nconn + 63u) / 64u, 64, stream, A);
+        } else if (call.flags & HHUFF_QENC_EVICT) {
+            HHUFF_LAUNCH(e, (qse_walk_kernel<true, false, S>), (nconn + 63u) / 64u, 64, stream, A);
+        } else {
+            HHUFF_LAUNCH(e, (qse_walk_kernel<false, false, S>), (nconn + 63u) / 64u, 64, stream, A);
+        }
+    };
+    if (call.cmap)
+        walk(std::true_type{});
+    else
+        walk(std::false_type{});
     HHUFF_LAUNCH(e, qse_emit_kernel, ge, 256, stream, A);
     if (e == hipSuccess) e = launch_long_payload(call.in, A.lw, stream);
     const hipError_t f = hipFreeAsync(ws, stream);

@@ -693,6 +693,112 @@ int hhuff_qpack_flatten_sessions(const uint8_t *in, uint64_t in_size, const hhuf
                                  int32_t *dec_status, uint32_t *dec_consumed, void *scratch, uint64_t scratch_size,
                                  unsigned flags, void *stream);
 
+/* (2h) Connection slots: connections that come and go.  The four stateful families above -- HPACK blocks
+ *      (hhuff_hpack_decode_blocks / _parse_requests / _parse_responses), the QPACK decoder step (hhuff_qpack_decode
+ *      / _parse_requests / _parse_responses), the HPACK encoder (hhuff_hpack_flatten_responses) and the QPACK
+ *      encoder sessions (hhuff_qpack_flatten_sessions) -- keep one slab of scratch per connection, address it by the
+ *      connection's position in the call, and start every connection fresh or none (their *_CONTINUE flag).  Each
+ *      has a _slots variant that takes a hhuff_conn_slots_t first and is otherwise the same function: scratch is
+ *      then `nslots` slabs (scratch_size >= hhuff_*_scratch_size(nslots, ...)), the call lists only the nconn
+ *      connections that have something this step, in any order, and says per connection which slab is its own and
+ *      whether it starts fresh there.  slots == NULL is the function without the suffix: the same bytes, statuses
+ *      and scratch contents, no launch and no workspace more.
+ *      1. Addressing.  Connection c of the call uses slab slot[c].  Offsets kept inside the tables stay relative
+ *         to scratch, so scratch may still be moved between calls.  The call neither reads nor writes the slab of
+ *         a slot no listed connection owns.
+ *      2. Freshness.  Connection c starts fresh when the call has no *_CONTINUE flag, or when flags[c] has
+ *         HHUFF_CONN_RESET: exactly what a call without *_CONTINUE does for that family -- an empty table at its
+ *         initial capacity, the failed state cleared.  For a QPACK encoder session it is a new encoder: table,
+ *         inflight list and largest_known_received empty, num_blocked 0, the session's mode taken from this call's
+ *         HHUFF_QENC_EVICT / HHUFF_QENC_DUP bits (the mode-mismatch refusal applies to continuing connections
+ *         only), and with HHUFF_QENC_SET_CAPACITY its encoder stream opens with Set Dynamic Table Capacity.
+ *      3. Ownership.  A slot belongs to the lowest-numbered connection of the call that names it.  A connection
+ *         is refused when it names a slot >= nslots, a slot an earlier connection of the call owns, or carries a
+ *         flag bit other than HHUFF_CONN_RESET.  A refused connection touches no slab and writes no payload byte:
+ *           HPACK blocks    bstatus = HHUFF_BLK_EINVAL, nfields = 0, req / res = the record of a reset state
+ *           QPACK decode    enc_status and every sstatus = HHUFF_QPK_EINVAL, enc_consumed = insert_count = 0,
+ *                           nfields = req_insert_count = 0, req / res = the record of a reset state (no ack)
+ *           HPACK encode    every rstatus = HHUFF_RES_EINVAL, out_len = headers_size = 0
+ *           QPACK sessions  dec_status and every rstatus = HHUFF_RES_EINVAL, dec_consumed = enc_out_len = 0,
+ *                           out_len = header_len = 0
+ *         Two calls in flight on different streams must name disjoint slots: the caller's contract, not checked.
+ *      4. The call returns HHUFF_EINVAL and enqueues nothing when nslots is 0 or above 2^31 - 1, scratch_size is
+ *         below nslots slabs, or slot is NULL and nconn > nslots.
+ *      The call takes 4 (nconn + nslots) bytes more from the library's pool and runs two small kernels ahead of
+ *      the family's own (none of it when slot and flags are both NULL). */
+#define HHUFF_CONN_RESET 1u /* this connection starts fresh in its slot, whatever *_CONTINUE says */
+typedef struct hhuff_conn_slots {
+    const uint32_t *slot; /* device u32[nconn]: the scratch slot of the call's connection c; NULL: slot c = c */
+    const uint8_t *flags; /* device u8[nconn] or NULL (= all 0): HHUFF_CONN_*; other bits must be 0 */
+    uint32_t nslots;      /* slots in scratch: scratch_size >= hhuff_*_scratch_size(nslots, ...) */
+} hhuff_conn_slots_t;     /* the struct itself is host memory, read before the call returns */
+#define HHUFF_BLK_EINVAL (-303) /* bstatus: the block's connection was refused (point 3) */
+#define HHUFF_QPK_EINVAL (-303) /* enc_status / sstatus: the connection was refused (point 3) */
+int hhuff_hpack_decode_blocks_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                    const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                                    uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
+                                    uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
+                                    uint32_t *nfields, int32_t *bstatus, void *scratch, uint64_t scratch_size,
+                                    unsigned flags, void *stream);
+int hhuff_hpack_parse_requests_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                     const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                                     uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
+                                     uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
+                                     uint32_t *nfields, int32_t *bstatus, hhuff_request_t *req, void *scratch,
+                                     uint64_t scratch_size, unsigned flags, void *stream);
+int hhuff_hpack_parse_responses_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                      const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                                      uint32_t table_size, const uint8_t *trailers, uint8_t *arena,
+                                      const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len,
+                                      uint32_t *value_off, uint32_t *value_len, uint8_t *fflags, uint32_t *nfields,
+                                      int32_t *bstatus, hhuff_response_t *res, void *scratch, uint64_t scratch_size,
+                                      unsigned flags, void *stream);
+int hhuff_qpack_decode_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                             const uint32_t *enc_off, const uint32_t *enc_len, const uint32_t *sec_off,
+                             const uint32_t *conn_first, uint32_t nconn, uint32_t nsec, uint32_t header_table_size,
+                             uint64_t max_blocked, const uint32_t *num_blocked, uint8_t *arena,
+                             const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len, uint32_t *value_off,
+                             uint32_t *value_len, uint8_t *fflags, uint32_t *nfields, int32_t *sstatus,
+                             uint64_t *req_insert_count, int32_t *enc_status, uint32_t *enc_consumed,
+                             uint64_t *insert_count, void *scratch, uint64_t scratch_size, unsigned flags, void *stream);
+int hhuff_qpack_parse_requests_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                     const uint32_t *enc_off, const uint32_t *enc_len, const uint32_t *sec_off,
+                                     const uint32_t *conn_first, uint32_t nconn, uint32_t nsec,
+                                     uint32_t header_table_size, uint64_t max_blocked, const uint32_t *num_blocked,
+                                     uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len,
+                                     uint32_t *value_off, uint32_t *value_len, uint8_t *fflags, uint32_t *nfields,
+                                     int32_t *sstatus, uint64_t *req_insert_count, int32_t *enc_status,
+                                     uint32_t *enc_consumed, uint64_t *insert_count, const uint64_t *stream_id,
+                                     hhuff_qpack_request_t *req, void *scratch, uint64_t scratch_size, unsigned flags,
+                                     void *stream);
+int hhuff_qpack_parse_responses_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                      const uint32_t *enc_off, const uint32_t *enc_len, const uint32_t *sec_off,
+                                      const uint32_t *conn_first, uint32_t nconn, uint32_t nsec,
+                                      uint32_t header_table_size, uint64_t max_blocked, const uint32_t *num_blocked,
+                                      uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len,
+                                      uint32_t *value_off, uint32_t *value_len, uint8_t *fflags, uint32_t *nfields,
+                                      int32_t *sstatus, uint64_t *req_insert_count, int32_t *enc_status,
+                                      uint32_t *enc_consumed, uint64_t *insert_count, const uint64_t *stream_id,
+                                      hhuff_qpack_response_head_t *res, void *scratch, uint64_t scratch_size,
+                                      unsigned flags, void *stream);
+int hhuff_hpack_flatten_responses_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                        const hhuff_hpack_header_t *hdr, uint32_t nhdr,
+                                        const hhuff_hpack_response_t *res, const uint32_t *conn_first, uint32_t nconn,
+                                        uint32_t nres, uint32_t server_off, uint32_t server_len, uint8_t *out,
+                                        const uint64_t *out_off, uint32_t *out_len, uint32_t *headers_size,
+                                        int32_t *rstatus, void *scratch, uint64_t scratch_size, unsigned flags,
+                                        void *stream);
+int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t *slots, const uint8_t *in, uint64_t in_size,
+                                       const hhuff_hpack_header_t *hdr, uint32_t nhdr, const hhuff_qpack_response_t *res,
+                                       const uint32_t *conn_first, uint32_t nconn, uint32_t nres,
+                                       const uint64_t *stream_id, const uint32_t *dec_off, const uint32_t *dec_len,
+                                       uint32_t header_table_size, uint64_t max_blocked, uint32_t max_inflight,
+                                       uint32_t server_off, uint32_t server_len, uint8_t *out, const uint64_t *out_off,
+                                       uint32_t *out_len, uint32_t *header_len, int32_t *rstatus, uint8_t *rflags,
+                                       uint8_t *enc_out, const uint64_t *enc_out_off, uint32_t *enc_out_len,
+                                       int32_t *dec_status, uint32_t *dec_consumed, void *scratch,
+                                       uint64_t scratch_size, unsigned flags, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
