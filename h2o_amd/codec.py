@@ -37,6 +37,12 @@ class _ConnSlotsStruct(ctypes.Structure):  # include/hhuff.h hhuff_conn_slots_t
     _fields_ = [("slot", _vp), ("flags", _vp), ("nslots", ctypes.c_uint32)]
 
 
+class _QpackDsessionsStruct(ctypes.Structure):  # include/hhuff.h hhuff_qpack_dsessions_t
+    _fields_ = [("state", _vp), ("state_size", ctypes.c_uint64), ("cancel_first", _vp), ("cancel_id", _vp),
+                ("cancel_flags", _vp), ("dec_out", _vp), ("dec_out_off", _vp), ("dec_out_len", _vp), ("wake_id", _vp),
+                ("wake_first", _vp), ("nwake", _vp), ("parked", _vp), ("dflags", _vp), ("flags", ctypes.c_uint32)]
+
+
 SLOTS_SYMBOLS = ("hhuff_hpack_decode_blocks_slots", "hhuff_hpack_parse_requests_slots", "hhuff_hpack_parse_responses_slots",
                  "hhuff_qpack_decode_slots", "hhuff_qpack_parse_requests_slots", "hhuff_qpack_parse_responses_slots",
                  "hhuff_hpack_flatten_responses_slots", "hhuff_qpack_flatten_sessions_slots")
@@ -139,6 +145,17 @@ def lib():
             f = getattr(L, name)
             f.restype = ctypes.c_int
             f.argtypes = [ctypes.POINTER(_ConnSlotsStruct)] + list(base.argtypes)
+        # include/hhuff.h (2e'''): the request / response steps with decoder sessions -- the sessions and the slots
+        # first, no num_blocked
+        for name in ("hhuff_qpack_parse_requests", "hhuff_qpack_parse_responses"):
+            at = list(getattr(L, name).argtypes)
+            f = getattr(L, name + "_sessions")
+            f.restype = ctypes.c_int
+            f.argtypes = [ctypes.POINTER(_QpackDsessionsStruct), ctypes.POINTER(_ConnSlotsStruct)] + at[:10] + at[11:]
+        L.hhuff_qpack_dsession_state_size.restype = ctypes.c_uint64
+        L.hhuff_qpack_dsession_state_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.hhuff_qpack_dsession_out_bound.restype = ctypes.c_uint64
+        L.hhuff_qpack_dsession_out_bound.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
         L.hhuff_version.restype = ctypes.c_char_p
         L.hhuff_last_error_string.restype = ctypes.c_char_p
         L.hhuff_grid_size.restype = ctypes.c_int
@@ -188,7 +205,9 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_qpack_flatten_sessions", "hhuff_set_decode_kernel",
             "hhuff_decode_batch_host_packed", "hhuff_encode_batch_host_packed", "hhuff_set_edge_defer_min",
             "hhuff_decode_batch_multi", "hhuff_encode_batch_multi", "hhuff_shard_bounds",
-            "hhuff_debug_encode_blocks_per_cu") + SLOTS_SYMBOLS
+            "hhuff_debug_encode_blocks_per_cu", "hhuff_qpack_parse_requests_sessions",
+            "hhuff_qpack_parse_responses_sessions", "hhuff_qpack_dsession_state_size",
+            "hhuff_qpack_dsession_out_bound") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -468,9 +487,63 @@ QPK_CONTINUE = 1
 QREQ_BYTES = 72  # sizeof(hhuff_qpack_request_t)
 
 
+QDS_SYNC = QDS_SILENT = QDS_WAKE_PENDING = 1
+
+
+def qpack_dsession_state_size(n, max_blocked=100):
+    """include/hhuff.h hhuff_qpack_dsession_state_size"""
+    return int(lib().hhuff_qpack_dsession_state_size(n, max_blocked))
+
+
+def qpack_dsession_out_bound(nsec_of_conn, ncancel_of_conn=0):
+    """include/hhuff.h hhuff_qpack_dsession_out_bound (numpy arrays, tensors or ints)"""
+    return 10 * (nsec_of_conn + ncancel_of_conn) + 10
+
+
+class QpackDsessions:
+    """include/hhuff.h hhuff_qpack_dsessions_t for qpack_decode's sessions= argument.  state: the uint8 device tensor
+    a previous step returned (None: allocated, for a first step).  cancel_first int32 (u32 bits) [nconn + 1],
+    cancel_id int64, cancel_flags uint8 (QDS_SILENT): this step's cancellations, or None.  dec_out_off int64
+    [nconn + 1] (None: every connection's region is exactly its bound), dec_out uint8; wake_first int32 [nconn + 1]
+    (None: max_blocked entries a connection), wake_id int64; sync: QDS_SYNC."""
+
+    def __init__(self, state=None, cancel_first=None, cancel_id=None, cancel_flags=None, dec_out_off=None, dec_out=None,
+                 wake_first=None, wake_id=None, sync=False):
+        self.state, self.cancel_first, self.cancel_id, self.cancel_flags = state, cancel_first, cancel_id, cancel_flags
+        self.dec_out_off, self.dec_out, self.wake_first, self.wake_id, self.sync = dec_out_off, dec_out, wake_first, wake_id, sync
+
+
+def _qpack_dsessions(ds, r, conn_first, nconn, nstate, max_blocked, dev):
+    """fill in the defaults of `ds`, add its outputs to r -> the C struct (and what must stay alive with it)"""
+    import torch
+
+    if ds.dec_out_off is None:
+        cnt = (conn_first[1:] - conn_first[:-1]).to(torch.int64)
+        if ds.cancel_first is not None:
+            cnt = cnt + (ds.cancel_first[1:] - ds.cancel_first[:-1]).to(torch.int64)
+        ds.dec_out_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
+                                    torch.cumsum(qpack_dsession_out_bound(cnt), 0)])
+    if ds.dec_out is None:
+        ds.dec_out = torch.empty(max(1, int(ds.dec_out_off[-1].item())), dtype=torch.uint8, device=dev)
+    if ds.wake_first is None:
+        ds.wake_first = (torch.arange(nconn + 1, dtype=torch.int64, device=dev) * max_blocked).to(torch.int32)
+    if ds.wake_id is None:
+        ds.wake_id = torch.empty(max(1, int(ds.wake_first[-1].item())), dtype=torch.int64, device=dev)
+    if ds.state is None:
+        ds.state = torch.empty(max(16, qpack_dsession_state_size(nstate, max_blocked)), dtype=torch.uint8, device=dev)
+    i32 = lambda n: torch.empty(max(1, n), dtype=torch.int32, device=dev)  # noqa: E731
+    r.update(dec_out=ds.dec_out, dec_out_off=ds.dec_out_off, dec_out_len=i32(nconn), wake_id=ds.wake_id,
+             wake_first=ds.wake_first, nwake=i32(nconn), parked=i32(nconn),
+             dflags=torch.empty(max(1, nconn), dtype=torch.uint8, device=dev), state=ds.state)
+    return _QpackDsessionsStruct(_dp(ds.state), ds.state.numel(), _dp(ds.cancel_first), _dp(ds.cancel_id),
+                                 _dp(ds.cancel_flags), _dp(ds.dec_out), _dp(ds.dec_out_off), _dp(r["dec_out_len"]),
+                                 _dp(ds.wake_id), _dp(ds.wake_first), _dp(r["nwake"]), _dp(r["parked"]), _dp(r["dflags"]),
+                                 QDS_SYNC if ds.sync else 0)
+
+
 def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table_size=4096, max_blocked=100,
                  num_blocked=None, arena_off=None, in_size=None, stream=None, scratch=None, cont=False, arena=None,
-                 stream_id=None, responses=False, slots=None):
+                 stream_id=None, responses=False, slots=None, sessions=None):
     """QPACK decoder step (include/hhuff.h hhuff_qpack_decode) on device tensors: enc_off / enc_len (per
     connection), sec_off / conn_first / num_blocked int32 tensors (u32 bits), arena_off int64; nsec =
     conn_first[-1] as a host int.  Returns a dict of device tensors: arena, name_off, name_len, value_off,
@@ -480,7 +553,11 @@ def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table
     hhuff_qpack_parse_requests (h2o_qpack_parse_request per section), plus "req": uint8 [nsec, 72] records
     (hhuff_qpack_request_t).  responses=True (with stream_id): the HTTP/3 client's step,
     hhuff_qpack_parse_responses (h2o_qpack_parse_response per section), plus "res": uint8 [nsec, 40] records
-    (hhuff_qpack_response_head_t).  slots (ConnSlots): the _slots variants (see hpack_decode_blocks)."""
+    (hhuff_qpack_response_head_t).  slots (ConnSlots): the _slots variants (see hpack_decode_blocks).
+    sessions (QpackDsessions, with stream_id; num_blocked must be None): hhuff_qpack_parse_requests_sessions /
+    _parse_responses_sessions -- the parked streams and the decoder stream kept on the device; plus dec_out,
+    dec_out_off, dec_out_len, wake_id, wake_first, nwake, parked, dflags and `state` (carry it like scratch:
+    QpackDsessions(state=r["state"]) with cont=True)."""
     import torch
 
     dev = data.device
@@ -506,7 +583,16 @@ def qpack_decode(data, enc_off, enc_len, sec_off, conn_first, nsec, header_table
             _dp(r["fflags"]), _dp(r["nfields"]), _dp(r["sstatus"]), _dp(r["req_insert_count"]), _dp(r["enc_status"]),
             _dp(r["enc_consumed"]), _dp(r["insert_count"])]
     tail = [_dp(scratch), scratch.numel(), QPK_CONTINUE if cont else 0, _stream(stream)]
-    if stream_id is None:
+    if sessions is not None:
+        assert stream_id is not None and num_blocked is None, "sessions: a request / response step, no num_blocked"
+        name = "hhuff_qpack_parse_responses_sessions" if responses else "hhuff_qpack_parse_requests_sessions"
+        key, size = ("res", QRES_BYTES) if responses else ("req", QREQ_BYTES)
+        r[key] = torch.empty((max(1, nsec), size), dtype=torch.uint8, device=dev)
+        dst = _qpack_dsessions(sessions, r, conn_first, nconn, nconn if slots is None else slots.nslots, max_blocked, dev)
+        st = None if slots is None else ctypes.byref(_ConnSlotsStruct(_dp(slots.slot), _dp(slots.flags), slots.nslots))
+        _check(getattr(lib(), name)(ctypes.byref(dst), st, *(args[:10] + args[11:] + [_dp(stream_id), _dp(r[key])] + tail)),
+               name)
+    elif stream_id is None:
         _stateful("hhuff_qpack_decode", slots, args + tail)
     elif responses:
         r["res"] = torch.empty((max(1, nsec), QRES_BYTES), dtype=torch.uint8, device=dev)

@@ -461,11 +461,23 @@ int qpack_step(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_s
                uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
                int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count, const uint64_t* stream_id,
                hhuff_qpack_request_t* req, hhuff_qpack_response_head_t* res, void* scratch, uint64_t scratch_size,
-               unsigned flags, void* stream) {
+               unsigned flags, void* stream, bool sessions = false, const hhuff_qpack_dsessions_t* ds = nullptr) {
+    if (sessions && max_blocked > 4096) return arg_fail("sessions: max_blocked above 4096");
     if (slots && header_table_size > (1u << 30)) return arg_fail("header_table_size above 2^30");
     if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size, hhuff::qpack_conn_scratch(header_table_size)))
         return arg_fail(bad);
     if (nconn == 0) return HHUFF_OK;
+    if (sessions) {  // include/hhuff.h (2e''')
+        if (!ds) return arg_fail("sessions: NULL hhuff_qpack_dsessions_t");
+        if (nconn > 0x7FFFFFFFu) return arg_fail("sessions: nconn above 2^31 - 1");
+        if (!ds->state || !ds->dec_out || !ds->dec_out_off || !ds->dec_out_len || (!ds->wake_id && max_blocked) || !ds->wake_first ||
+            !ds->nwake || !ds->parked || !ds->dflags || (ds->cancel_first && !ds->cancel_id))
+            return arg_fail("sessions: NULL array");
+        if (ds->flags & ~HHUFF_QDS_SYNC) return arg_fail("sessions: unknown flag bit");
+        if (ds->state_size < hhuff_qpack_dsession_state_size(slots ? slots->nslots : nconn, (uint32_t)max_blocked))
+            return arg_fail("sessions: state smaller than hhuff_qpack_dsession_state_size");
+        if (((uintptr_t)ds->state & 15u) != 0) return arg_fail("sessions: state must be 16-byte aligned");
+    }
     if (!in || !enc_off || !enc_len || !sec_off || !conn_first || !enc_status || !enc_consumed || !insert_count ||
         !scratch)
         return arg_fail("NULL array");
@@ -484,10 +496,50 @@ int qpack_step(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_s
     e = hhuff::launch_qpack(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
                             num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
                             req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
-                            (hipStream_t)stream, stream_id, req, res, map.cmap);
+                            (hipStream_t)stream, stream_id, req, res, map.cmap, sessions ? ds : nullptr);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack launch");
 }
 }  // namespace
+
+HHUFF_API uint64_t hhuff_qpack_dsession_state_size(uint32_t n, uint32_t max_blocked) {
+    return max_blocked > 4096 ? 0u : (uint64_t)n * hhuff::qpack_dsession_slab(max_blocked);
+}
+
+HHUFF_API uint64_t hhuff_qpack_dsession_out_bound(uint32_t nsec_of_conn, uint32_t ncancel_of_conn) {
+    return 10ull * ((uint64_t)nsec_of_conn + ncancel_of_conn) + 10u;
+}
+
+HHUFF_API int hhuff_qpack_parse_requests_sessions(
+    const hhuff_qpack_dsessions_t* ds, const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+    const uint32_t* enc_off, const uint32_t* enc_len, const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn,
+    uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked, uint8_t* arena, const uint64_t* arena_off,
+    uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+    int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
+    const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch, uint64_t scratch_size, unsigned flags,
+    void* stream) {
+    if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
+    if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
+    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
+                      nullptr, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, nullptr, scratch,
+                      scratch_size, flags, stream, true, ds);
+}
+
+HHUFF_API int hhuff_qpack_parse_responses_sessions(
+    const hhuff_qpack_dsessions_t* ds, const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+    const uint32_t* enc_off, const uint32_t* enc_len, const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn,
+    uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked, uint8_t* arena, const uint64_t* arena_off,
+    uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+    int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
+    const uint64_t* stream_id, hhuff_qpack_response_head_t* res, void* scratch, uint64_t scratch_size, unsigned flags,
+    void* stream) {
+    if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
+    if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
+    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
+                      nullptr, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, nullptr, res, scratch,
+                      scratch_size, flags, stream, true, ds);
+}
 
 HHUFF_API int hhuff_qpack_decode_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
                                        const uint32_t* enc_off, const uint32_t* enc_len,

@@ -199,7 +199,9 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
                         uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                         uint8_t* scratch, uint32_t flags, hipStream_t stream, const uint64_t* stream_id = nullptr,
                         hhuff_qpack_request_t* qreq = nullptr, hhuff_qpack_response_head_t* qres = nullptr,
-                        const uint32_t* cmap = nullptr);
+                        const uint32_t* cmap = nullptr, const hhuff_qpack_dsessions_t* ds = nullptr);
+// bytes of one decoder session (include/hhuff.h (2e''')) with a list of max_blocked entries
+uint64_t qpack_dsession_slab(uint32_t max_blocked);
 int grid_size(int device, int which);
 // the staged / stream prices (ps per string, per byte) a mixed-length decode on `device` uses: the fitted
 // defaults, pinned values, or (calibrate != 0: measured now, synchronously) this device's own

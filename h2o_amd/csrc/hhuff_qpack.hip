@@ -34,6 +34,7 @@
 #include "hhuff_device.h"
 #include "hhuff.h"
 #include "hhuff_launch.h"
+#include "hhuff_qpark.h"
 #include "hhuff_request.h"
 #include "hhuff_slots.h"
 
@@ -431,6 +432,39 @@ __device__ __forceinline__ void load_dec_tables(uint32_t* s_lut, uint32_t* s_kin
     __syncthreads();
 }
 
+// one connection's encoder stream (cs: its slab, by the call's map or by the connection's own number)
+__device__ __forceinline__ void q_encoder_conn(const QpkArgs& A, uint64_t c, const ConnSlot cs, const DecTables& T) {
+    if (cs.refused) {  // no slab of its own: nothing of its encoder stream is taken
+        A.enc_status[c] = HHUFF_QPK_EINVAL;
+        A.enc_consumed[c] = 0;
+        A.insert_count[c] = 0;
+        return;
+    }
+    QState* ps = reinterpret_cast<QState*>(A.scratch + cs.slot * A.conn_scratch);
+    if (!(A.flags & HHUFF_QPK_CONTINUE) || cs.reset) {  // h2o_qpack_create_decoder (:240-252)
+        QState s0{};
+        s0.base_offset = 1;
+        s0.max_size = A.T;
+        *ps = s0;
+    }
+    QTable t = q_table(A, cs.slot);
+    t.s.dirty = 0;
+    int32_t st = 0;
+    uint32_t consumed = 0;
+    uint64_t ic = 0;
+    if (t.s.failed) {
+        st = HHUFF_QPK_SKIPPED;
+    } else if (A.enc_len[c]) {
+        const uint64_t p = A.enc_off[c];
+        st = q_handle_input(t, A, p, p + A.enc_len[c], consumed, ic, T);
+        t.s.failed = st != 0;
+    }
+    A.enc_status[c] = st;
+    A.enc_consumed[c] = consumed;
+    A.insert_count[c] = ic;
+    *ps = t.s;
+}
+
 template <bool SLOTS>
 __global__ __launch_bounds__(256) void qpack_encoder_kernel(QpkArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
@@ -441,37 +475,127 @@ __global__ __launch_bounds__(256) void qpack_encoder_kernel(QpkArgs A) {
     T.lut = s_lut;
     T.kinfo = s_kinfo;
     T.ones = s_ones;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < A.nconn; c += (uint64_t)gridDim.x * blockDim.x)
+        q_encoder_conn(A, c, conn_slot<SLOTS>(A.cmap, c), T);
+}
+
+// ---- decoder sessions (include/hhuff.h (2e'''), hhuff_qpark.h) ----
+struct QdsArgs {  // hhuff_qpack_dsessions_t as the kernels see it
+    uint8_t* state;
+    uint64_t slab;  // bytes of a session
+    uint32_t cap;   // max_blocked: entries of a session's list
+    uint32_t flags;
+    const uint32_t* cancel_first;
+    const uint64_t* cancel_id;
+    const uint8_t* cancel_flags;
+    uint8_t* dec_out;
+    const uint64_t* dec_out_off;
+    uint32_t* dec_out_len;
+    uint64_t* wake_id;
+    const uint32_t* wake_first;
+    uint32_t *nwake, *parked;
+    uint8_t* dflags;
+    uint32_t* map;       // the step's connection map: written by the encoder-stream pass, read by the others
+    const uint32_t* given;  // the slot map of the call (hhuff_slots.h); NULL: connection c in slot c
+};
+
+// The encoder-stream pass of a session step.  It settles first which connections the step refuses -- a dec_out
+// region under the bound for the connection's own sections and cancellations, a cancel_first that decreases --
+// and writes the verdict into the step's connection map, so every later pass sees such a connection as one the
+// slot map refused and forms no address in its table or session.
+__global__ __launch_bounds__(256) void qpack_encoder_ds_kernel(QpkArgs A, QdsArgs D) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
+    __shared__ uint32_t s_kinfo[32];
+    __shared__ uint32_t s_ones[HHUFF_ONES_NENT];
+    load_dec_tables(s_lut, s_kinfo, s_ones);
+    DecTables T;  // assigned, not brace-initialised (see hhuff_blocks.hip)
+    T.lut = s_lut;
+    T.kinfo = s_kinfo;
+    T.ones = s_ones;
     for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < A.nconn; c += (uint64_t)gridDim.x * blockDim.x) {
-        const ConnSlot cs = conn_slot<SLOTS>(A.cmap, c);
-        if (cs.refused) {  // no slab of its own: nothing of its encoder stream is taken
-            A.enc_status[c] = HHUFF_QPK_EINVAL;
-            A.enc_consumed[c] = 0;
-            A.insert_count[c] = 0;
-            continue;
+        uint32_t m = D.given ? D.given[c] : (uint32_t)c;
+        if (m != kConnRefused) {
+            const uint32_t k0 = A.conn_first[c], k1 = A.conn_first[c + 1];
+            const uint32_t x0 = D.cancel_first ? D.cancel_first[c] : 0u, x1 = D.cancel_first ? D.cancel_first[c + 1] : 0u;
+            const uint64_t o0 = D.dec_out_off[c], o1 = D.dec_out_off[c + 1];
+            if (x1 < x0 || k1 < k0 || o1 < o0 || o1 - o0 < qp_out_bound((uint64_t)k1 - k0, (uint64_t)x1 - x0)) m = kConnRefused;
         }
-        QState* ps = reinterpret_cast<QState*>(A.scratch + cs.slot * A.conn_scratch);
-        if (!(A.flags & HHUFF_QPK_CONTINUE) || cs.reset) {  // h2o_qpack_create_decoder (:240-252)
-            QState s0{};
-            s0.base_offset = 1;
-            s0.max_size = A.T;
-            *ps = s0;
+        D.map[c] = m;
+        q_encoder_conn(A, c, conn_slot_of(m), T);
+    }
+}
+
+// The session pass, in place of qpack_blocked_kernel: one lane per connection walks its sections (point 1), its
+// cancellations (2), its list (3: wake) and writes the Insert Count Increment (4).
+__global__ __launch_bounds__(256) void qpack_dsession_kernel(QpkArgs A, QdsArgs D) {
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < A.nconn; c += (uint64_t)gridDim.x * blockDim.x) {
+        const ConnSlot cs = conn_slot_of(D.map[c]);
+        uint32_t out_n = 0, nw = 0, np = 0, df = 0;
+        if (!cs.refused) {
+            QpHead* h = reinterpret_cast<QpHead*>(D.state + cs.slot * D.slab);
+            QpEntry* ent = reinterpret_cast<QpEntry*>(h + 1);
+            const QState* ps = reinterpret_cast<const QState*>(A.scratch + cs.slot * A.conn_scratch);
+            const bool fresh = !(A.flags & HHUFF_QPK_CONTINUE) || cs.reset;
+            uint32_t n = fresh ? 0u : min(h->parked, D.cap);
+            uint64_t krc = fresh ? 0u : h->known_received;
+            if (!ps->failed) {
+                const uint64_t total = ps->total_inserts;
+                uint8_t* out = D.dec_out + D.dec_out_off[c];
+                const uint64_t room = D.dec_out_off[c + 1] - D.dec_out_off[c];
+                auto put = [&](const uint8_t* b, uint32_t len) {  // an instruction, whole or not at all
+                    if ((uint64_t)out_n + len > room) return;
+                    for (uint32_t i = 0; i < len; ++i) out[out_n + i] = b[i];
+                    out_n += len;
+                };
+                uint8_t tmp[16];
+                for (uint32_t k = A.conn_first[c]; k < A.conn_first[c + 1]; ++k) {  // 1
+                    const int32_t st = A.sstatus[k];
+                    if (st == HHUFF_QPK_SKIPPED || st == HHUFF_QPK_EINVAL) continue;
+                    const uint64_t id = A.stream_id[k];
+                    const uint32_t i = qp_find(ent, n, id);
+                    if (st == HHUFF_QPK_BLOCKED) {
+                        if (i == n && !qp_park(ent, n, D.cap, id, A.req_insert_count[k])) A.sstatus[k] = kDF;
+                        continue;
+                    }
+                    if (i != n) qp_remove(ent, n, i);
+                    const uint32_t al = A.qreq ? A.qreq[k].ack_len : A.qres[k].ack_len;
+                    if (al == 0) continue;
+                    const uint8_t* ab = A.qreq ? A.qreq[k].ack : A.qres[k].ack;
+                    const uint32_t len = min(al, 16u);
+                    for (uint32_t j = 0; j < len; ++j) tmp[j] = ab[j];
+                    put(tmp, len);
+                    krc = qp_acknowledged(krc, A.req_insert_count[k]);
+                }
+                if (D.cancel_first) {  // 2
+                    for (uint32_t x = D.cancel_first[c]; x < D.cancel_first[c + 1]; ++x) {
+                        const uint64_t id = D.cancel_id[x];
+                        const uint32_t i = qp_find(ent, n, id);
+                        if (i != n) qp_remove(ent, n, i);
+                        if (D.cancel_flags && (D.cancel_flags[x] & HHUFF_QDS_SILENT)) continue;
+                        put(tmp, qp_put_int(tmp, 0x40u, id, 6));
+                    }
+                }
+                const uint32_t w0 = D.wake_first[c], w1 = D.wake_first[c + 1];  // 3
+                bool pending = false;
+                nw = qp_wake(ent, n, total, D.wake_id + w0, w1 > w0 ? w1 - w0 : 0u, pending);
+                df = pending ? HHUFF_QDS_WAKE_PENDING : 0u;
+                if (D.flags & HHUFF_QDS_SYNC) {  // 4
+                    const uint64_t inc = qp_increment(total, krc);
+                    if (inc) {
+                        put(tmp, qp_put_int(tmp, 0x00u, inc, 6));
+                        krc = total;
+                    }
+                }
+            }
+            h->parked = n;
+            h->pad = 0;
+            h->known_received = krc;
+            np = n;
         }
-        QTable t = q_table(A, cs.slot);
-        t.s.dirty = 0;
-        int32_t st = 0;
-        uint32_t consumed = 0;
-        uint64_t ic = 0;
-        if (t.s.failed) {
-            st = HHUFF_QPK_SKIPPED;
-        } else if (A.enc_len[c]) {
-            const uint64_t p = A.enc_off[c];
-            st = q_handle_input(t, A, p, p + A.enc_len[c], consumed, ic, T);
-            t.s.failed = st != 0;
-        }
-        A.enc_status[c] = st;
-        A.enc_consumed[c] = consumed;
-        A.insert_count[c] = ic;
-        *ps = t.s;
+        D.dec_out_len[c] = out_n;
+        D.nwake[c] = nw;
+        D.parked[c] = np;
+        D.dflags[c] = (uint8_t)df;
     }
 }
 
@@ -979,6 +1103,8 @@ uint64_t qpack_conn_scratch(uint32_t header_table_size) {
            2ull * qpk_ring_bytes(header_table_size);
 }
 
+uint64_t qpack_dsession_slab(uint32_t max_blocked) { return qp_slab_bytes(max_blocked); }
+
 hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, const uint32_t* enc_len,
                         const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
                         uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked, uint8_t* arena,
@@ -986,7 +1112,8 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
                         uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus,
                         uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                         uint8_t* scratch, uint32_t flags, hipStream_t stream, const uint64_t* stream_id,
-                        hhuff_qpack_request_t* qreq, hhuff_qpack_response_head_t* qres, const uint32_t* cmap) {
+                        hhuff_qpack_request_t* qreq, hhuff_qpack_response_head_t* qres, const uint32_t* cmap,
+                        const hhuff_qpack_dsessions_t* ds) {
     if (nconn == 0) return hipSuccess;
     QpkArgs A{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
               max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
@@ -1006,7 +1133,9 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
     const uint64_t o_cons = o_pay + up(4 * n_max), o_st = o_cons + up(4 * n_max), o_ws = o_st + up(n_max);
     const uint64_t o_out = o_ws + up(literals_dev_ws((uint32_t)n_max, in_size));
     const uint64_t o_fsn = o_out + up((8 * in_size) / 5 + 64), o_fsv = o_fsn + up(8 * in_size + 8);
-    const uint64_t wbytes = o_fsv + up(8 * in_size + 8);  // field slots: one per input byte
+    const uint64_t o_map = o_fsv + up(8 * in_size + 8);  // field slots: one per input byte
+    // a session step without a slot map makes its connection map here (the encoder-stream pass fills it)
+    const uint64_t wbytes = o_map + (ds && !cmap ? up(4 * (uint64_t)nconn) : 0u);
     uint8_t* work = nullptr;
     hipError_t e = hipSuccess;
     {
@@ -1059,7 +1188,29 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
         hipLaunchKernelGGL(qpack_blocked_kernel, dim3(std::min((nconn + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
         return hipGetLastError();
     };
-    if (e == hipSuccess) e = cmap ? step(std::true_type{}) : step(std::false_type{});
+    auto session_step = [&]() {  // the passes of `step` on the step's own map, the session pass behind them
+        QdsArgs D{static_cast<uint8_t*>(ds->state), qp_slab_bytes((uint32_t)max_blocked), (uint32_t)max_blocked, ds->flags,
+                  ds->cancel_first, ds->cancel_id, ds->cancel_flags, ds->dec_out, ds->dec_out_off, ds->dec_out_len,
+                  ds->wake_id, ds->wake_first, ds->nwake, ds->parked, ds->dflags,
+                  cmap ? const_cast<uint32_t*>(cmap) : reinterpret_cast<uint32_t*>(work + o_map), cmap};
+        A.cmap = D.map;
+        const dim3 gc(std::min((nconn + 255u) / 256u, 65535u));
+        hipLaunchKernelGGL(qpack_encoder_ds_kernel, gc, dim3(256), 0, stream, A, D);
+        hipLaunchKernelGGL(qpack_table_kernel<true>, dim3((uint32_t)(((uint64_t)nconn + 3) / 4)), dim3(256), 0, stream, A);
+        hipError_t f = hipGetLastError();
+        if (f != hipSuccess) return f;
+        if (nsec != 0) {
+            const dim3 gs(std::min((nsec + 255u) / 256u, 65535u));
+            if (qres)
+                hipLaunchKernelGGL((qpack_sections_kernel<kSecResp, true>), gs, dim3(256), 0, stream, A);
+            else
+                hipLaunchKernelGGL((qpack_sections_kernel<kSecReq, true>), gs, dim3(256), 0, stream, A);
+            hipLaunchKernelGGL(qpack_copy_kernel, dim3(std::min((nsec + 255u) / 256u, 4096u)), dim3(256), 0, stream, A);
+        }
+        hipLaunchKernelGGL(qpack_dsession_kernel, gc, dim3(256), 0, stream, A, D);
+        return hipGetLastError();
+    };
+    if (e == hipSuccess) e = ds ? session_step() : cmap ? step(std::true_type{}) : step(std::false_type{});
     if (work) {
         const hipError_t f = hipFreeAsync(work, stream);
         if (e == hipSuccess) e = f;

@@ -22,12 +22,14 @@ struct ConnSlot {
 // Every kernel that calls this has two instantiations and its launcher picks by cmap != NULL.  SLOTS = false (a
 // call without slots): connection c in slot c, as it continues or not by the call's flag alone -- constants, so
 // the kernel's code is what it was before there were slots and the dense path costs what it did.
+__device__ __forceinline__ ConnSlot conn_slot_of(uint32_t m) {  // a map word
+    const bool refused = m == kConnRefused;
+    return ConnSlot{refused ? 0ull : (uint64_t)(m & ~kConnReset), refused, !refused && (m & kConnReset) != 0};
+}
 template <bool SLOTS>
 __device__ __forceinline__ ConnSlot conn_slot(const uint32_t* __restrict__ cmap, uint64_t c) {
     if (!SLOTS) return ConnSlot{c, false, false};
-    const uint32_t m = cmap[c];
-    const bool refused = m == kConnRefused;
-    return ConnSlot{refused ? 0ull : (uint64_t)(m & ~kConnReset), refused, !refused && (m & kConnReset) != 0};
+    return conn_slot_of(cmap[c]);
 }
 
 // Rule 4 of the contract, on the host: 0, or the text of the refusal.  slab = the family's bytes per slot.

@@ -394,6 +394,110 @@ int hhuff_qpack_parse_responses(const uint8_t *in, uint64_t in_size, const uint3
                                 uint64_t *insert_count, const uint64_t *stream_id, hhuff_qpack_response_head_t *res,
                                 void *scratch, uint64_t scratch_size, unsigned flags, void *stream);
 
+/* (2e''') QPACK decoder sessions: the step of hhuff_qpack_parse_requests / _parse_responses with the layer h2o keeps
+ *      around its decoder (lib/http3/server.c) on the device too -- which streams of a connection are parked and at
+ *      which Required Insert Count (conn->num_qpack_blocked :133, stream->qpack_blocked_ref :245), which of them may
+ *      go on after a step's inserts (qpack_unblock_streams :1950-1966), the release of a reset stream
+ *      (cancel_qpack_decoder :562-571, on_stream_destroy :919-922) -- and the connection's decoder stream: the
+ *      Section Acknowledgments (send_header_ack, qpack.c:643-650), Stream Cancellations
+ *      (h2o_qpack_decoder_send_stream_cancel, :500-504) and Insert Count Increments
+ *      (h2o_qpack_decoder_send_state_sync, :487-498), in the form hhuff_qpack_flatten_sessions reads as dec_off /
+ *      dec_len.  The arguments behind `slots` are those of hhuff_qpack_parse_requests / _parse_responses without
+ *      num_blocked: the session keeps that count.  slots ((2h)) may be NULL: connection c uses slab c, of the
+ *      table scratch and of the session state alike.  max_blocked is also the length of a session's list.
+ *      State: ds->state holds hhuff_qpack_dsession_state_size(n, max_blocked) bytes, n = slots->nslots with slots
+ *      and nconn without: n equal slabs of 16 + 16 max_blocked bytes -- the parked count, the Known Received Count,
+ *      then max_blocked entries {stream_id u64, ref u64}, oldest first.  Memory of its own (16-byte aligned):
+ *      hhuff_qpack_scratch_size and the table slabs are what they were.  No addresses inside: it may be moved
+ *      between calls.  A session starts fresh exactly when its table does (no HHUFF_QPK_CONTINUE, or
+ *      HHUFF_CONN_RESET for the connection): nothing parked, Known Received Count 0.
+ *      One step of connection c, after the passes of hhuff_qpack_decode, in this order:
+ *      1. Its sections in order.  Section k has come up blocked when the sections pass gave it HHUFF_QPK_BLOCKED
+ *         (its Required Insert Count is not reached by the table as the step's whole encoder stream left it).
+ *         Blocked and stream_id[k] parked already: it stays parked with the ref it has, sstatus[k] stays
+ *         HHUFF_QPK_BLOCKED (a resubmission that still waits).  Blocked, not parked, max_blocked streams parked:
+ *         sstatus[k] = HHUFF_QPK_DECOMPRESSION_FAILED.  Blocked, not parked, a slot free: {stream_id[k],
+ *         req_insert_count[k]} joins the list (server.c:1551-1555).  Any other status except HHUFF_QPK_SKIPPED /
+ *         _EINVAL: the stream's entry, if it has one, leaves the list; and when the record carries an
+ *         acknowledgment (ack_len > 0) its bytes are appended to the connection's dec_out region and the Known
+ *         Received Count rises to req_insert_count[k] if that is larger (RFC 9204 4.4.1).  The caller's contract,
+ *         not checked: no later section of a stream is submitted while an earlier one is parked.
+ *      2. Its cancellations cancel_id[cancel_first[c] .. cancel_first[c+1]) in order: a parked stream leaves the
+ *         list; without HHUFF_QDS_SILENT in cancel_flags a Stream Cancellation (0x40 | stream id, 6-bit prefix) is
+ *         appended to dec_out whether or not the stream was parked, as cancel_qpack_decoder sends it.
+ *      3. Wake: every parked entry with ref <= the table's insert count leaves the list (server.c:1958), its stream
+ *         id written to wake_id[wake_first[c] ..) oldest first; nwake[c] counts them.  The caller submits the woken
+ *         streams' sections in its next step, where they are ordinary sections (or resubmits parked sections
+ *         speculatively with the inserts: point 1 handles both).  Entries the region wake_first[c+1] -
+ *         wake_first[c] cannot hold stay parked and set HHUFF_QDS_WAKE_PENDING in dflags[c]; the scan runs every
+ *         step, so they are found again.
+ *      4. With HHUFF_QDS_SYNC: n = the table's total inserts - the Known Received Count; when n > 0, an Insert
+ *         Count Increment (0x00 | n, 6-bit prefix) is appended and the Known Received Count becomes the total.
+ *         (h2o_qpack_decoder_send_state_sync counts every insert since the last sync, whatever was acknowledged
+ *         in between; its own encoder refuses such an increment, qpack.c:907-909, and h2o never calls it.  With no
+ *         acknowledgment between two syncs the bytes are the reference function's.)
+ *      dec_out_len[c] = the step's bytes in dec_out[dec_out_off[c] ..): acknowledgments in section order, then
+ *      cancellations, then the increment.  parked[c] = the parked count after the step.  A connection whose
+ *      encoder stream has failed (enc_status != 0, now or earlier) emits nothing and wakes nothing: its lengths are
+ *      0, its sections HHUFF_QPK_SKIPPED, parked[c] what it was.
+ *      Refusal: a connection whose dec_out region is smaller than hhuff_qpack_dsession_out_bound(its sections,
+ *      its cancellations), or over which cancel_first decreases, is refused for the step before any pass touches
+ *      its table or session, with the outputs of a refused connection of (2h) point 3 -- enc_status and every
+ *      sstatus HHUFF_QPK_EINVAL, enc_consumed = insert_count = nfields = req_insert_count = 0, reset records --
+ *      and dec_out_len = nwake = parked = dflags = 0.  A connection the slot map refuses is refused here alike.
+ *      Stream ids are QUIC's: below 2^62, so an instruction takes at most 10 bytes and the bound holds; an
+ *      instruction of a larger id that would cross the region's end is left out whole.
+ *      The call returns HHUFF_EINVAL and enqueues nothing for max_blocked above 4096, nconn above 2^31 - 1, a
+ *      state_size below hhuff_qpack_dsession_state_size, a NULL required array (state, dec_out, dec_out_off,
+ *      dec_out_len, wake_first, nwake, parked, dflags; wake_id unless max_blocked is 0; cancel_id with cancel_first;
+ *      stream_id and the records with nsec != 0) or an unknown bit in ds->flags; nconn == 0 returns 0 and enqueues nothing.
+ *      Launches: those of hhuff_qpack_parse_requests with the blocked-limit pass replaced by the session pass
+ *      (one lane per connection); the refusal test runs inside the encoder-stream pass.  4 nconn bytes more
+ *      from the pool when slots is NULL. */
+#define HHUFF_QDS_SYNC 1u         /* ds->flags: point 4 */
+#define HHUFF_QDS_SILENT 1u       /* cancel_flags: release the slot, send nothing (on_stream_destroy) */
+#define HHUFF_QDS_WAKE_PENDING 1u /* dflags: due entries stayed parked because the wake region was full */
+typedef struct hhuff_qpack_dsessions {
+    void *state;                  /* device: the sessions */
+    uint64_t state_size;
+    const uint32_t *cancel_first; /* device u32[nconn + 1], or NULL: no cancellations */
+    const uint64_t *cancel_id;    /* device u64: the cancelled stream ids */
+    const uint8_t *cancel_flags;  /* device u8 per cancellation, or NULL (= all 0): HHUFF_QDS_SILENT */
+    uint8_t *dec_out;             /* device: the decoder-stream bytes */
+    const uint64_t *dec_out_off;  /* device u64[nconn + 1]: the regions of dec_out */
+    uint32_t *dec_out_len;        /* device u32[nconn], written */
+    uint64_t *wake_id;            /* device u64: the streams to resume */
+    const uint32_t *wake_first;   /* device u32[nconn + 1]: the regions of wake_id */
+    uint32_t *nwake;              /* device u32[nconn], written */
+    uint32_t *parked;             /* device u32[nconn], written: the parked count after the step */
+    uint8_t *dflags;              /* device u8[nconn], written: HHUFF_QDS_WAKE_PENDING */
+    uint32_t flags;               /* HHUFF_QDS_SYNC */
+} hhuff_qpack_dsessions_t;        /* the struct itself is host memory, read before the call returns */
+struct hhuff_conn_slots;          /* (2h) hhuff_conn_slots_t */
+uint64_t hhuff_qpack_dsession_state_size(uint32_t n, uint32_t max_blocked); /* 0 for max_blocked above 4096 */
+uint64_t hhuff_qpack_dsession_out_bound(uint32_t nsec_of_conn, uint32_t ncancel_of_conn);
+int hhuff_qpack_parse_requests_sessions(const hhuff_qpack_dsessions_t *ds, const struct hhuff_conn_slots *slots,
+                                        const uint8_t *in, uint64_t in_size, const uint32_t *enc_off,
+                                        const uint32_t *enc_len, const uint32_t *sec_off, const uint32_t *conn_first,
+                                        uint32_t nconn, uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked,
+                                        uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
+                                        uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
+                                        uint32_t *nfields, int32_t *sstatus, uint64_t *req_insert_count,
+                                        int32_t *enc_status, uint32_t *enc_consumed, uint64_t *insert_count,
+                                        const uint64_t *stream_id, hhuff_qpack_request_t *req, void *scratch,
+                                        uint64_t scratch_size, unsigned flags, void *stream);
+int hhuff_qpack_parse_responses_sessions(const hhuff_qpack_dsessions_t *ds, const struct hhuff_conn_slots *slots,
+                                         const uint8_t *in, uint64_t in_size, const uint32_t *enc_off,
+                                         const uint32_t *enc_len, const uint32_t *sec_off, const uint32_t *conn_first,
+                                         uint32_t nconn, uint32_t nsec, uint32_t header_table_size,
+                                         uint64_t max_blocked, uint8_t *arena, const uint64_t *arena_off,
+                                         uint32_t *name_off, uint32_t *name_len, uint32_t *value_off,
+                                         uint32_t *value_len, uint8_t *fflags, uint32_t *nfields, int32_t *sstatus,
+                                         uint64_t *req_insert_count, int32_t *enc_status, uint32_t *enc_consumed,
+                                         uint64_t *insert_count, const uint64_t *stream_id,
+                                         hhuff_qpack_response_head_t *res, void *scratch, uint64_t scratch_size,
+                                         unsigned flags, void *stream);
+
 /* (2f) HTTP/2 response header blocks, encode side (SURVEY f4 encode half): h2o_hpack_flatten_response
  *      (lib/http2/hpack.c:1137-1177) and h2o_hpack_flatten_trailers (:1179-1196) -- and, for h2o's HTTP/2
  *      client (lib/common/http2client.c:1140), h2o_hpack_flatten_request (:1044-1096) -- for many responses of many
