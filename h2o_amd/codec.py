@@ -637,10 +637,11 @@ def qpack_response_bound(name_value_bytes, nhdr, server_len, dfid_len):
 
 
 def qpack_flatten_responses(data, hdr, res, nres, out_off, server_off=0, server_len=0, in_size=None, out=None,
-                            stream=None):
+                            stream=None, out_len=None, header_len=None, rstatus=None):
     """HTTP/3 response HEADERS frames (include/hhuff.h hhuff_qpack_flatten_responses) on device tensors: hdr =
     uint8 tensor of HPE_HEADER_DTYPE records, res = uint8 tensor of QPE_RESPONSE_DTYPE records (32 B), out_off
-    int64 [nres + 1].  Returns a dict of device tensors: out, out_len, header_len, rstatus."""
+    int64 [nres + 1].  Returns a dict of device tensors: out, out_len, header_len, rstatus (the caller's int32
+    tensors of nres entries where given, else new ones)."""
     import torch
 
     dev = data.device
@@ -649,7 +650,8 @@ def qpack_flatten_responses(data, hdr, res, nres, out_off, server_off=0, server_
     if out is None:
         out = torch.empty(max(1, int(out_off[-1].item())), dtype=torch.uint8, device=dev)
     i32 = lambda n: torch.empty(max(1, n), dtype=torch.int32, device=dev)  # noqa: E731
-    r = dict(out=out, out_len=i32(nres), header_len=i32(nres), rstatus=i32(nres))
+    r = dict(out=out, out_len=i32(nres) if out_len is None else out_len,
+             header_len=i32(nres) if header_len is None else header_len, rstatus=i32(nres) if rstatus is None else rstatus)
     _check(lib().hhuff_qpack_flatten_responses(
         _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), nres, server_off, server_len, _dp(out),
         _dp(out_off), _dp(r["out_len"]), _dp(r["header_len"]), _dp(r["rstatus"]), _stream(stream)),
@@ -730,12 +732,14 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
 
 
 def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_off=0, server_len=0, in_size=None,
-                            out=None, scratch=None, cont=False, stream=None, slots=None):
+                            out=None, scratch=None, cont=False, stream=None, slots=None, out_len=None, headers_size=None,
+                            rstatus=None):
     """HTTP/2 response header blocks (include/hhuff.h hhuff_hpack_flatten_responses) on device tensors:
     hdr = uint8 tensor of HPE_HEADER_DTYPE records (20 B each), res = uint8 tensor of HPE_RESPONSE_DTYPE
     records (40 B), conn_first int32 (u32 bits), out_off int64 [nres + 1]; nres = conn_first[-1] as a host int.
-    Returns a dict of device tensors: out, out_len, headers_size, rstatus, and the scratch holding the encoder
-    tables (pass it back with cont=True for the connections' next responses).  slots (ConnSlots):
+    Returns a dict of device tensors: out, out_len, headers_size, rstatus (the caller's int32 tensors of nres entries
+    where given, else new ones), and the scratch holding the encoder tables (pass it back with cont=True for the
+    connections' next responses).  slots (ConnSlots):
     hhuff_hpack_flatten_responses_slots (see hpack_decode_blocks)."""
     import torch
 
@@ -746,7 +750,9 @@ def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_of
     if out is None:
         out = torch.empty(max(1, int(out_off[-1].item())), dtype=torch.uint8, device=dev)
     i32 = lambda n: torch.empty(max(1, n), dtype=torch.int32, device=dev)  # noqa: E731
-    r = dict(out=out, out_len=i32(nres), headers_size=i32(nres), rstatus=i32(nres))
+    r = dict(out=out, out_len=i32(nres) if out_len is None else out_len,
+             headers_size=i32(nres) if headers_size is None else headers_size,
+             rstatus=i32(nres) if rstatus is None else rstatus)
     ss = int(lib().hhuff_hpack_enc_scratch_size(nconn if slots is None else slots.nslots))
     if scratch is None:
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
