@@ -43,6 +43,11 @@ class _QpackDsessionsStruct(ctypes.Structure):  # include/hhuff.h hhuff_qpack_ds
                 ("wake_first", _vp), ("nwake", _vp), ("parked", _vp), ("dflags", _vp), ("flags", ctypes.c_uint32)]
 
 
+class _ConnFamilyStruct(ctypes.Structure):  # include/hhuff.h hhuff_conn_family_t
+    _fields_ = [("family", ctypes.c_uint32), ("table_size", ctypes.c_uint32), ("max_inflight", ctypes.c_uint32),
+                ("max_blocked", ctypes.c_uint32)]
+
+
 SLOTS_SYMBOLS = ("hhuff_hpack_decode_blocks_slots", "hhuff_hpack_parse_requests_slots", "hhuff_hpack_parse_responses_slots",
                  "hhuff_qpack_decode_slots", "hhuff_qpack_parse_requests_slots", "hhuff_qpack_parse_responses_slots",
                  "hhuff_hpack_flatten_responses_slots", "hhuff_qpack_flatten_sessions_slots")
@@ -156,6 +161,14 @@ def lib():
         L.hhuff_qpack_dsession_state_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
         L.hhuff_qpack_dsession_out_bound.restype = ctypes.c_uint64
         L.hhuff_qpack_dsession_out_bound.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        # include/hhuff.h (2i): connection images
+        for name in ("hhuff_conn_slab_size", "hhuff_conn_image_bound"):
+            getattr(L, name).restype = ctypes.c_uint64
+            getattr(L, name).argtypes = [ctypes.POINTER(_ConnFamilyStruct)]
+        for name in ("hhuff_conn_export", "hhuff_conn_import"):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [ctypes.POINTER(_ConnFamilyStruct), _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
+                                         ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp]
         L.hhuff_version.restype = ctypes.c_char_p
         L.hhuff_last_error_string.restype = ctypes.c_char_p
         L.hhuff_grid_size.restype = ctypes.c_int
@@ -207,7 +220,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_decode_batch_multi", "hhuff_encode_batch_multi", "hhuff_shard_bounds",
             "hhuff_debug_encode_blocks_per_cu", "hhuff_qpack_parse_requests_sessions",
             "hhuff_qpack_parse_responses_sessions", "hhuff_qpack_dsession_state_size",
-            "hhuff_qpack_dsession_out_bound") + SLOTS_SYMBOLS
+            "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
+            "hhuff_conn_import") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -275,6 +289,62 @@ def _stateful(name, slots, args):
         return
     st = _ConnSlotsStruct(_dp(slots.slot), _dp(slots.flags), slots.nslots)
     _check(getattr(lib(), name + "_slots")(ctypes.byref(st), *args), name + "_slots")
+
+
+# include/hhuff.h (2i): connection images
+FAM_HPACK_DEC, FAM_QPACK_DEC, FAM_HPACK_ENC, FAM_QPACK_ENC, FAM_QPACK_DSESSION = range(5)
+IMG_SPACE, IMG_EINVAL, IMG_EFORMAT, IMG_EPARAM = -300, -303, -304, -305
+
+
+def conn_family(family, table_size=0, max_inflight=0, max_blocked=0):
+    """hhuff_conn_family_t: which slabs a scratch holds (FAM_* and the family's own parameters, 0 for the others)"""
+    return _ConnFamilyStruct(int(family), int(table_size), int(max_inflight), int(max_blocked))
+
+
+def conn_slab_size(fam) -> int:
+    """the family's bytes per slot; 0: parameters its own call refuses"""
+    return int(lib().hhuff_conn_slab_size(ctypes.byref(fam)))
+
+
+def conn_image_bound(fam) -> int:
+    """the largest image of one connection of the family (a multiple of 16)"""
+    return int(lib().hhuff_conn_image_bound(ctypes.byref(fam)))
+
+
+def conn_export(fam, scratch, nslots, slot, img=None, img_off=None, stream=None):
+    """hhuff_conn_export of the slots in `slot` (int32 device tensor, u32 bits) of `scratch` (nslots slabs).
+    img None: the size query runs first and lays the regions out back to back (each image's own length, a multiple
+    of 16), then the images are written -> (img, img_off, img_len, status).  With img and img_off (int64 device
+    tensor [n + 1]) the caller's regions are used as they are; a region too small gives status IMG_SPACE and the
+    length needed in img_len."""
+    import torch
+
+    n = slot.numel()
+    dev = scratch.device
+    img_len = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    status = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    L, st = lib(), _stream(stream)
+    head = [ctypes.byref(fam), _dp(scratch), scratch.numel() * scratch.element_size(), int(nslots), _dp(slot), n]
+    if img is None:
+        _check(L.hhuff_conn_export(*head, None, None, _dp(img_len), _dp(status), st), "hhuff_conn_export")
+        img_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        img_off[1:] = torch.cumsum(img_len[:n].to(torch.int64) & 0xFFFFFFFF, 0)
+        img = torch.empty(max(16, int(img_off[-1])), dtype=torch.uint8, device=dev)
+    _check(L.hhuff_conn_export(*head, _dp(img), _dp(img_off), _dp(img_len), _dp(status), st), "hhuff_conn_export")
+    return img, img_off, img_len[:n], status[:n]
+
+
+def conn_import(fam, scratch, nslots, slot, img, img_off, img_len, stream=None):
+    """hhuff_conn_import: item k's image (img[img_off[k] .. +img_len[k])) into slot slot[k] of `scratch` -> status
+    (int32 device tensor: 0, IMG_EINVAL, IMG_EFORMAT or IMG_EPARAM; a refused item's slab is untouched)"""
+    import torch
+
+    n = slot.numel()
+    status = torch.empty(max(1, n), dtype=torch.int32, device=scratch.device)
+    _check(lib().hhuff_conn_import(ctypes.byref(fam), _dp(scratch), scratch.numel() * scratch.element_size(), int(nslots),
+                                   _dp(slot), n, _dp(img), _dp(img_off), _dp(img_len), _dp(status), _stream(stream)),
+           "hhuff_conn_import")
+    return status[:n]
 
 
 def decode_slot_size(in_size: int) -> int:

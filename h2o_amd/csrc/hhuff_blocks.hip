@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "hhuff_device.h"
+#include "hhuff_image.h"
 #include "hhuff.h"
 #include "hhuff_launch.h"
 #include "hhuff_request.h"
@@ -115,6 +116,12 @@ struct Entry {  // one dynamic-table entry: references to its name and value byt
     uint32_t pad;
 };
 static_assert(sizeof(TableState) == 32 && sizeof(Entry) == 32, "scratch records");
+// connection images (hhuff_image.h) restate the two records and the scratch source
+static_assert(offsetof(TableState, failed) == offsetof(img::BlkState, failed) && offsetof(TableState, cap) == offsetof(img::BlkState, cap) &&
+                  offsetof(Entry, vsrc) == offsetof(img::BlkEntry, vsrc) && offsetof(Entry, vl) == offsetof(img::BlkEntry, vl) &&
+                  offsetof(Entry, cls) == offsetof(img::BlkEntry, cls) && kSrcScr == img::kBlkScr && kSrcOff == img::kBlkOff &&
+                  kClsUnknown == img::kClsUnknown,
+              "hhuff_image.h: HPACK_DEC slab");
 
 __device__ __host__ __forceinline__ uint32_t tbl_entries(uint32_t table_size) { return table_size / kEntryOverhead + 1; }
 __device__ __host__ __forceinline__ uint64_t tbl_ring(uint32_t table_size) { return ((uint64_t)table_size + 15u) & ~15ull; }

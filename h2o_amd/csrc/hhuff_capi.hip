@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "hhuff.h"
+#include "hhuff_image.h"
 #include "hhuff_launch.h"
 #include "hhuff_slots.h"
 
@@ -507,6 +508,70 @@ HHUFF_API uint64_t hhuff_qpack_dsession_state_size(uint32_t n, uint32_t max_bloc
 
 HHUFF_API uint64_t hhuff_qpack_dsession_out_bound(uint32_t nsec_of_conn, uint32_t ncancel_of_conn) {
     return 10ull * ((uint64_t)nsec_of_conn + ncancel_of_conn) + 10u;
+}
+
+// ---- (2i) connection images ----
+namespace {
+// the family's slab as its own entry points size it; 0: parameters they refuse, or hhuff_image.h out of step
+uint64_t conn_family_slab(const hhuff_conn_family_t* fam, hhuff::img::Layout& L) {
+    if (!fam || !hhuff::img::layout(*fam, L)) return 0;
+    uint64_t own = 0;
+    switch (fam->family) {
+        case HHUFF_FAM_HPACK_DEC: own = hhuff::hpack_conn_scratch(fam->table_size); break;
+        case HHUFF_FAM_QPACK_DEC: own = hhuff::qpack_conn_scratch(fam->table_size); break;
+        case HHUFF_FAM_HPACK_ENC: own = hhuff::hpenc_conn_scratch(); break;
+        case HHUFF_FAM_QPACK_ENC: own = hhuff::qpenc_conn_scratch(fam->table_size, fam->max_inflight); break;
+        default: own = hhuff::qpack_dsession_slab(fam->max_blocked); break;
+    }
+    return own == L.slab ? own : 0;
+}
+
+int conn_image_check(const hhuff_conn_family_t* fam, const void* scratch, uint64_t scratch_size, uint32_t nslots,
+                     const void* img) {
+    hhuff::img::Layout L;
+    const uint64_t slab = conn_family_slab(fam, L);
+    if (slab == 0) return arg_fail("connection family: unknown, or parameters the family refuses");
+    if (nslots == 0) return arg_fail("nslots is 0");
+    if (nslots > hhuff::kConnMaxSlots) return arg_fail("nslots above 2^31 - 1");
+    if (scratch_size / slab < nslots) return arg_fail("scratch smaller than nslots slabs");
+    if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
+    if (((uintptr_t)img & 15u) != 0) return arg_fail("img must be 16-byte aligned");
+    return HHUFF_OK;
+}
+}  // namespace
+
+HHUFF_API uint64_t hhuff_conn_slab_size(const hhuff_conn_family_t* fam) {
+    hhuff::img::Layout L;
+    return conn_family_slab(fam, L);
+}
+
+HHUFF_API uint64_t hhuff_conn_image_bound(const hhuff_conn_family_t* fam) {
+    hhuff::img::Layout L;
+    return conn_family_slab(fam, L) ? hhuff::img::image_bound(L) : 0;
+}
+
+HHUFF_API int hhuff_conn_export(const hhuff_conn_family_t* fam, const void* scratch, uint64_t scratch_size, uint32_t nslots,
+                                const uint32_t* slot, uint32_t n, uint8_t* img, const uint64_t* img_off, uint32_t* img_len,
+                                int32_t* status, void* stream) {
+    if (const int rc = conn_image_check(fam, scratch, scratch_size, nslots, img)) return rc;
+    if (n == 0) return HHUFF_OK;
+    if (!scratch || !slot || !img_len || !status || (img && !img_off)) return arg_fail("NULL array");
+    if (((uintptr_t)img_off & 7u) != 0) return arg_fail("img_off must be 8-byte aligned");
+    const hipError_t e = hhuff::launch_conn_export(*fam, (const uint8_t*)scratch, nslots, slot, n, img, img_off, img_len,
+                                                   status, (hipStream_t)stream);
+    return e == hipSuccess ? HHUFF_OK : hip_fail(e, "connection export launch");
+}
+
+HHUFF_API int hhuff_conn_import(const hhuff_conn_family_t* fam, void* scratch, uint64_t scratch_size, uint32_t nslots,
+                                const uint32_t* slot, uint32_t n, const uint8_t* img, const uint64_t* img_off,
+                                const uint32_t* img_len, int32_t* status, void* stream) {
+    if (const int rc = conn_image_check(fam, scratch, scratch_size, nslots, img)) return rc;
+    if (n == 0) return HHUFF_OK;
+    if (!scratch || !slot || !img || !img_off || !img_len || !status) return arg_fail("NULL array");
+    if (((uintptr_t)img_off & 7u) != 0) return arg_fail("img_off must be 8-byte aligned");
+    const hipError_t e = hhuff::launch_conn_import(*fam, (uint8_t*)scratch, nslots, slot, n, img, img_off, img_len, status,
+                                                   (hipStream_t)stream);
+    return e == hipSuccess ? HHUFF_OK : hip_fail(e, "connection import launch");
 }
 
 HHUFF_API int hhuff_qpack_parse_requests_sessions(

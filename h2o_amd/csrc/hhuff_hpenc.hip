@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "hhuff_enc.h"
+#include "hhuff_image.h"
 #include "hhuff_slots.h"
 
 namespace hhuff {
@@ -77,6 +78,12 @@ struct EncEntry {
 static_assert(sizeof(EncState) == 32 && sizeof(EncEntry) == 40, "scratch records");
 constexpr uint64_t kConnScratch = sizeof(EncState) + kMaxEntries * sizeof(EncEntry) + 2 * kRing;
 static_assert(kConnScratch % 16 == 0, "scratch alignment");
+// connection images (hhuff_image.h) restate the two records, the ring and the scratch source
+static_assert(offsetof(EncState, failed) == offsetof(img::HeState, failed) && offsetof(EncState, cap) == offsetof(img::HeState, cap) &&
+                  offsetof(EncEntry, vsrc) == offsetof(img::HeEntry, vsrc) && offsetof(EncEntry, vh) == offsetof(img::HeEntry, vh) &&
+                  offsetof(EncEntry, tok) == offsetof(img::HeEntry, tok) && kSrcScr == img::kHeScr && kSrcOff == img::kHeOff &&
+                  kMaxEntries == img::kHeEntries && kRing == img::kHeRing && kInitialCap == img::kHeCap,
+              "hhuff_image.h: HPACK_ENC slab");
 }  // namespace
 
 struct HpeArgs : HpeCall {  // the call (the kernels read its members as their own) and its workspace

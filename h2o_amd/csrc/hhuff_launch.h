@@ -202,6 +202,14 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
                         const uint32_t* cmap = nullptr, const hhuff_qpack_dsessions_t* ds = nullptr);
 // bytes of one decoder session (include/hhuff.h (2e''')) with a list of max_blocked entries
 uint64_t qpack_dsession_slab(uint32_t max_blocked);
+// Connection images (include/hhuff.h (2i), hhuff_image.hip): one wave per item; fam's parameters checked by the
+// caller (img::layout).  Export only reads scratch; import takes the call's connection map from the pool.
+hipError_t launch_conn_export(const hhuff_conn_family_t& fam, const uint8_t* scratch, uint32_t nslots, const uint32_t* slot,
+                              uint32_t n, uint8_t* image, const uint64_t* img_off, uint32_t* img_len, int32_t* status,
+                              hipStream_t stream);
+hipError_t launch_conn_import(const hhuff_conn_family_t& fam, uint8_t* scratch, uint32_t nslots, const uint32_t* slot,
+                              uint32_t n, const uint8_t* image, const uint64_t* img_off, const uint32_t* img_len,
+                              int32_t* status, hipStream_t stream);
 int grid_size(int device, int which);
 // the staged / stream prices (ps per string, per byte) a mixed-length decode on `device` uses: the fitted
 // defaults, pinned values, or (calibrate != 0: measured now, synchronously) this device's own

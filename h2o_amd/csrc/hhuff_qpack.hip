@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "hhuff_device.h"
+#include "hhuff_image.h"
 #include "hhuff.h"
 #include "hhuff_launch.h"
 #include "hhuff_qpark.h"
@@ -132,6 +133,11 @@ struct QEntry {  // one dynamic-table entry: references to its name and value by
     uint32_t nl, vl, soft, pad;
 };
 static_assert(sizeof(QEntry) == 32, "QEntry layout");
+// connection images (hhuff_image.h) restate the two records and the scratch source
+static_assert(offsetof(QState, max_size) == offsetof(img::QdState, max_size) && offsetof(QState, start) == offsetof(img::QdState, start) &&
+                  offsetof(QState, dirty) == offsetof(img::QdState, dirty) && offsetof(QEntry, vsrc) == offsetof(img::QdEntry, vsrc) &&
+                  offsetof(QEntry, soft) == offsetof(img::QdEntry, soft) && kQScr == img::kQdScr && kQOff == img::kQdOff,
+              "hhuff_image.h: QPACK_DEC slab");
 
 __host__ __device__ __forceinline__ uint32_t qpk_ring_bytes(uint32_t T) { return ((T < 16u ? 16u : T) + 15u) & ~15u; }
 __host__ __device__ __forceinline__ uint32_t qpk_entries(uint32_t T) { return T / kEntryOverhead + 1u; }

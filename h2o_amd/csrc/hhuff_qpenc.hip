@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "hhuff_enc.h"
+#include "hhuff_image.h"
 #include "hhuff_qtable.h"
 #include "hhuff_slots.h"
 
@@ -428,6 +429,12 @@ struct QsInflight {
 };
 constexpr uint32_t kQsEvicting = 2u, kQsDuplicating = 4u;  // in QsState::failed
 static_assert(sizeof(QsState) == 32 && sizeof(QsEntry) == 32 && sizeof(QsInflight) == 16, "scratch records");
+// connection images (hhuff_image.h) restate the state and inflight records and the mode bits
+static_assert(offsetof(QsState, lkr) == offsetof(img::QeState, lkr) && offsetof(QsState, ninflight) == offsetof(img::QeState, ninflight) &&
+                  offsetof(QsState, failed) == offsetof(img::QeState, failed) && offsetof(QsState, evicted) == offsetof(img::QeState, evicted) &&
+                  offsetof(QsInflight, largest) == offsetof(img::QeInflight, largest) && kQsEvicting == img::kQeEvicting &&
+                  kQsDuplicating == img::kQeDuplicating,
+              "hhuff_image.h: QPACK_ENC slab");
 
 __host__ __device__ inline uint64_t qs_conn_scratch(uint32_t H, uint32_t M) {
     return sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry) + (uint64_t)M * sizeof(QsInflight) + ((H + 15ull) & ~15ull);

@@ -903,6 +903,89 @@ int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t *slots, const ui
                                        int32_t *dec_status, uint32_t *dec_consumed, void *scratch,
                                        uint64_t scratch_size, unsigned flags, void *stream);
 
+/* (2i) Connection images: a connection's state leaves the scratch it was born in.  The slabs of the families of
+ *      (2h), and the decoder sessions of (2e'''), keep scratch-relative offsets and ring positions, and their
+ *      stride is fixed by nslots: a slab copied elsewhere points back at the old place.  hhuff_conn_export
+ *      serialises listed slots into compact, position-independent, versioned images; hhuff_conn_import rebuilds a
+ *      slab from an image in any slot of any scratch of the same family parameters, on any device.  An image is
+ *      plain bytes: the caller moves it (hipMemcpyAsync, hipMemcpyPeerAsync) or keeps it -- a checkpoint, a fork,
+ *      a scratch that grows or shrinks, a connection that follows its load to another GPU.
+ *      slot[n], img, img_off[n + 1] (u64, every entry a multiple of 16), img_len[n] and status[n] are device
+ *      arrays; item k's region is img[img_off[k] .. img_off[k + 1]).  Both calls are asynchronous on `stream`.
+ *      1. Slab size.  hhuff_conn_slab_size(fam) = the family's bytes per slot: hhuff_hpack_scratch_size(1,
+ *         table_size), hhuff_qpack_scratch_size(1, table_size), hhuff_hpack_enc_scratch_size(1),
+ *         hhuff_qpack_enc_scratch_size(1, table_size, max_inflight), hhuff_qpack_dsession_state_size(1,
+ *         max_blocked).  It is 0 for parameters the family's own call refuses -- table_size over 65536 for
+ *         QPACK_ENC and over 2^30 for QPACK_DEC, max_blocked over 4096 for QPACK_DSESSION -- for an HPACK_DEC
+ *         table_size over 2^30 (an image's length is a u32), for an unknown family and for a non-zero unused
+ *         field.  Both calls return HHUFF_EINVAL and enqueue nothing when the slab size is 0, nslots is 0 or above
+ *         2^31 - 1, scratch_size is below nslots slabs, scratch or img is not 16-byte aligned, or an array is NULL
+ *         (but img == NULL in export, point 3).  n == 0 returns HHUFF_OK.
+ *      2. Export reads scratch and never writes it.  Item k is slot slot[k] as the last call that listed it left
+ *         it; the connection there goes on as if nothing happened.  Several items may name one slot.  Exactly
+ *         img_len[k] bytes of the region are written, a multiple of 16, pad bytes zero.  Exporting a slot in which
+ *         no call ever started a connection is the caller's error: every read stays inside the slab and every
+ *         write inside the region, the image is unspecified (import may refuse it).
+ *      3. Sizing.  With img == NULL (img_off may then be NULL too) export writes only img_len[k], status[k] = 0.
+ *         A region smaller than the image: status[k] = HHUFF_IMG_SPACE, img_len[k] = the length needed, no byte
+ *         of the region written.  img_len <= 96 + 32 records + string_bytes + 15, records = the live table
+ *         entries plus the inflight or parked records, string_bytes = the live entries' name and value bytes;
+ *         hhuff_conn_image_bound(fam) is that expression at the family's maxima (0 when the slab size is 0).  An
+ *         image of 2^32 - 16 bytes or more (an inflight list of 2^28 records) cannot be stated: HHUFF_IMG_SPACE
+ *         with img_len = 2^32 - 16, sizing query included.
+ *      4. Position independence and canonical form.  An image holds no scratch offset, ring index or ring start;
+ *         entries come oldest first and their bytes form one run in that order.  Two connections whose future
+ *         behaviour is the same have byte-identical images, whatever slots, scratch addresses, call partitioning,
+ *         ring and compaction history produced them.  The hashes the encoders keep beside their entries are
+ *         carried (they are functions of the strings); the HPACK decoder's cached name class is not (it is
+ *         computed again on first use).
+ *      5. Import rebuilds the slab of slot slot[k] from item k's image (img_len[k] = its length, as export gave
+ *         it).  The family's next call lists the connection in that slot with its *_CONTINUE flag and without
+ *         HHUFF_CONN_RESET, and the connection continues exactly as it would have at its source; a QPACK encoder
+ *         session keeps its mode (evicting, duplicating), so the mode-mismatch refusal works after a move.  Slot
+ *         ownership is (2h) point 3: the lowest-numbered item that names a slot owns it, the others get
+ *         HHUFF_IMG_EINVAL, as does a slot >= nslots (export too).  An item with a non-zero status leaves its slab
+ *         untouched.
+ *      6. Images are untrusted bytes.  Import checks the header first -- magic, version, length (== img_len[k],
+ *         inside the region, a multiple of 16), reserved words: HHUFF_IMG_EFORMAT; another family or other
+ *         parameters: HHUFF_IMG_EPARAM -- and then, before the first byte of the slab is written, everything the
+ *         family's kernels rely on for memory safety (HHUFF_IMG_EFORMAT): counts within the entry ring, the
+ *         inflight list and the parked list; size / used == the entries' bytes + 32 each, <= the capacity, the
+ *         capacity <= table_size; the string run as long as the entries' lengths; evicted <= count, lkr <= count,
+ *         an inflight record's largest reference <= count; reserved words and pad bytes zero.  An image that lies
+ *         about content only (a value the peer's table does not hold) is the caller's own problem.
+ *      7. The image: [header 32][state 64][entry records x 32][list records x 16][string run, padded to 16].
+ *           header  +0 magic "HHCI"  +4 u16 version = 1  +6 u16 family  +8 u32 table_size  +12 u32 max_inflight
+ *                   +16 u32 max_blocked  +20 u32 total length  +24, +28 reserved, 0
+ *         The body per family is in DESIGN.md; a layout change bumps the version.
+ *      8. Two calls in flight on different streams must not import into, or run a family call on, the same slot:
+ *         the caller's contract, as in (2h) point 3.
+ *      Out of scope: importing at another table_size, max_inflight or max_blocked (HHUFF_IMG_EPARAM), and a
+ *      host-side reader of image bodies. */
+#define HHUFF_FAM_HPACK_DEC      0u /* hhuff_hpack_decode_blocks / _parse_requests / _parse_responses scratch */
+#define HHUFF_FAM_QPACK_DEC      1u /* hhuff_qpack_decode / _parse_* scratch */
+#define HHUFF_FAM_HPACK_ENC      2u /* hhuff_hpack_flatten_responses scratch */
+#define HHUFF_FAM_QPACK_ENC      3u /* hhuff_qpack_flatten_sessions scratch */
+#define HHUFF_FAM_QPACK_DSESSION 4u /* hhuff_qpack_dsessions_t.state */
+typedef struct hhuff_conn_family {
+    uint32_t family;       /* HHUFF_FAM_* */
+    uint32_t table_size;   /* HPACK_DEC: table_size; QPACK_DEC, QPACK_ENC: header_table_size; else 0 */
+    uint32_t max_inflight; /* QPACK_ENC; else 0 */
+    uint32_t max_blocked;  /* QPACK_DSESSION; else 0 */
+} hhuff_conn_family_t;
+#define HHUFF_IMG_SPACE   (-300) /* export: the region is too small; img_len = the length needed, nothing written */
+#define HHUFF_IMG_EINVAL  (-303) /* slot >= nslots, or (import) a slot an earlier item of the call names */
+#define HHUFF_IMG_EFORMAT (-304) /* import: not an image of this version, or its contents break an invariant */
+#define HHUFF_IMG_EPARAM  (-305) /* import: an image of another family or other family parameters */
+uint64_t hhuff_conn_slab_size(const hhuff_conn_family_t *fam);   /* the family's bytes per slot; 0: bad parameters */
+uint64_t hhuff_conn_image_bound(const hhuff_conn_family_t *fam); /* largest image of one connection, multiple of 16 */
+int hhuff_conn_export(const hhuff_conn_family_t *fam, const void *scratch, uint64_t scratch_size, uint32_t nslots,
+                      const uint32_t *slot, uint32_t n, uint8_t *img, const uint64_t *img_off, uint32_t *img_len,
+                      int32_t *status, void *stream);
+int hhuff_conn_import(const hhuff_conn_family_t *fam, void *scratch, uint64_t scratch_size, uint32_t nslots,
+                      const uint32_t *slot, uint32_t n, const uint8_t *img, const uint64_t *img_off,
+                      const uint32_t *img_len, int32_t *status, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
