@@ -150,6 +150,9 @@ def lib():
             f = getattr(L, name)
             f.restype = ctypes.c_int
             f.argtypes = [ctypes.POINTER(_ConnSlotsStruct)] + list(base.argtypes)
+        # include/hhuff.h (2g''): the encoder sessions with a hhuff_qpack_peer_t array in front of the slots
+        L.hhuff_qpack_flatten_sessions_peers.restype = ctypes.c_int
+        L.hhuff_qpack_flatten_sessions_peers.argtypes = [_vp] + list(L.hhuff_qpack_flatten_sessions_slots.argtypes)
         # include/hhuff.h (2e'''): the request / response steps with decoder sessions -- the sessions and the slots
         # first, no num_blocked
         for name in ("hhuff_qpack_parse_requests", "hhuff_qpack_parse_responses"):
@@ -221,7 +224,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_debug_encode_blocks_per_cu", "hhuff_qpack_parse_requests_sessions",
             "hhuff_qpack_parse_responses_sessions", "hhuff_qpack_dsession_state_size",
             "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
-            "hhuff_conn_import") + SLOTS_SYMBOLS
+            "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -736,6 +739,8 @@ QENC_CONTINUE, QENC_SET_CAPACITY, QENC_EVICT, QENC_DUP = 1, 2, 4, 8
 QPK_DECODER_STREAM = 0x30202
 QPK_DECOMPRESSION_FAILED = 0x30200
 QPK_SKIPPED, QPK_BLOCKED = -301, -302
+# include/hhuff.h (2g''): hhuff_qpack_peer_t, a connection's peer settings
+QPACK_PEER = np.dtype([("max_table_capacity", "<u4"), ("max_blocked", "<u4")])
 
 
 def qpack_session_response_bound(name_value_bytes, nhdr, server_len, dfid_len):
@@ -757,7 +762,8 @@ def qpack_enc_scratch_size(nconn, header_table_size=4096, max_inflight=64):
 def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off, dec_off=None, dec_len=None,
                            header_table_size=4096, max_blocked=100, max_inflight=64, server_off=0, server_len=0,
                            enc_out_off=None, in_size=None, out=None, enc_out=None, scratch=None, cont=False,
-                           set_capacity=False, stream=None, evict=False, dup=False, slots=None):
+                           set_capacity=False, stream=None, evict=False, dup=False, slots=None, peers=None,
+                           peers_call=False):
     """One step of many QPACK encoder sessions (include/hhuff.h hhuff_qpack_flatten_sessions) on device tensors:
     hdr = uint8 tensor of HPE_HEADER_DTYPE records, res = uint8 tensor of QPE_RESPONSE_DTYPE records, conn_first
     int32 (u32 bits) [nconn + 1], stream_id int64 per response, out_off int64 [nres + 1], dec_off / dec_len int32
@@ -769,13 +775,19 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
     enc_out_off then (qpack_session_enc_bound), since header_table_size + 4 bytes need not hold a step's inserts.
     dup=True: HHUFF_QENC_DUP, with evict=True only and likewise on every step or on none: entries about to be pinned
     as the oldest are re-inserted by a Duplicate instruction.  slots (ConnSlots): hhuff_qpack_flatten_sessions_slots
-    (see hpack_decode_blocks); a connection with CONN_RESET is a new encoder in its slot."""
+    (see hpack_decode_blocks); a connection with CONN_RESET is a new encoder in its slot.  peers: a uint8 device
+    tensor of nconn QPACK_PEER records (hhuff_qpack_flatten_sessions_peers): every connection's table capacity,
+    clamped to header_table_size, Required Insert Count modulus and blocked-stream limit, capped by max_blocked, come
+    from its own peer's settings, the same record in every step of the connection's life.  peers_call: take that entry
+    point with peers None too (its pass-through to the _slots call)."""
     import torch
 
     dev = data.device
     in_size = data.numel() if in_size is None else in_size
     nconn = conn_first.numel() - 1
     nhdr = hdr.numel() // HPE_HEADER_DTYPE.itemsize
+    if peers is not None:
+        assert peers.dtype == torch.uint8 and peers.numel() == nconn * QPACK_PEER.itemsize, "one QPACK_PEER per connection"
     if enc_out_off is None:
         enc_out_off = torch.arange(nconn + 1, dtype=torch.int64, device=dev) * ((header_table_size + 4 + 15) // 16 * 16)
     if out is None:
@@ -791,12 +803,18 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
         scratch = torch.empty(max(16, ss), dtype=torch.uint8, device=dev)
     flags = (QENC_CONTINUE if cont else 0) | (QENC_SET_CAPACITY if set_capacity else 0) | (QENC_EVICT if evict else 0) | \
         (QENC_DUP if dup else 0)
-    _stateful("hhuff_qpack_flatten_sessions", slots, [
+    args = [
         _dp(data), in_size, _dp(hdr) if nhdr else None, nhdr, _dp(res), _dp(conn_first), nconn, nres, _dp(stream_id),
         _dp(dec_off), _dp(dec_len), header_table_size, max_blocked, max_inflight, server_off, server_len, _dp(out),
         _dp(out_off), _dp(r["out_len"]), _dp(r["header_len"]), _dp(r["rstatus"]), _dp(r["rflags"]), _dp(enc_out),
         _dp(enc_out_off), _dp(r["enc_out_len"]), _dp(r["dec_status"]), _dp(r["dec_consumed"]), _dp(scratch),
-        scratch.numel(), flags, _stream(stream)])
+        scratch.numel(), flags, _stream(stream)]
+    if peers is None and not peers_call:
+        _stateful("hhuff_qpack_flatten_sessions", slots, args)
+    else:
+        st = None if slots is None else _ConnSlotsStruct(_dp(slots.slot), _dp(slots.flags), slots.nslots)
+        _check(lib().hhuff_qpack_flatten_sessions_peers(_dp(peers), None if st is None else ctypes.byref(st), *args),
+               "hhuff_qpack_flatten_sessions_peers")
     r["scratch"] = scratch
     return r
 

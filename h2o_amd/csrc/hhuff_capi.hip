@@ -385,7 +385,8 @@ HHUFF_API uint64_t hhuff_qpack_enc_scratch_size(uint32_t nconn, uint32_t header_
     return (uint64_t)nconn * hhuff::qpenc_conn_scratch(header_table_size, max_inflight);
 }
 
-HHUFF_API int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+HHUFF_API int hhuff_qpack_flatten_sessions_peers(const hhuff_qpack_peer_t* peers, const hhuff_conn_slots_t* slots,
+                                                 const uint8_t* in, uint64_t in_size,
                                                  const hhuff_hpack_header_t* hdr, uint32_t nhdr,
                                            const hhuff_qpack_response_t* res, const uint32_t* conn_first, uint32_t nconn,
                                            uint32_t nres, const uint64_t* stream_id, const uint32_t* dec_off,
@@ -395,6 +396,7 @@ HHUFF_API int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t* slots
                                            int32_t* rstatus, uint8_t* rflags, uint8_t* enc_out, const uint64_t* enc_out_off,
                                            uint32_t* enc_out_len, int32_t* dec_status, uint32_t* dec_consumed, void* scratch,
                                            uint64_t scratch_size, unsigned flags, void* stream) {
+    if (((uintptr_t)peers & 3u) != 0) return arg_fail("peers must be 4-byte aligned");
     if (header_table_size > 65536u) {
         arg_fail("header_table_size must not exceed 65536");
         return HHUFF_RES_EINVAL;
@@ -425,13 +427,29 @@ HHUFF_API int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t* slots
     hhuff::QseCall call{in, in_size, hdr, nhdr, res, conn_first, nconn, nres, stream_id, dec_off, dec_len,
                               header_table_size, max_blocked, max_inflight, server_off, server_len, out, out_off, out_len,
                               header_len, rstatus, rflags, enc_out, enc_out_off, enc_out_len, dec_status, dec_consumed,
-                              (uint8_t*)scratch, flags, nullptr};
+                              (uint8_t*)scratch, flags, nullptr, peers};
     ConnMap map((hipStream_t)stream);
     hipError_t e = map.make(slots, nconn);
     if (e != hipSuccess) return hip_fail(e, "connection slots");
     call.cmap = map.cmap;
     e = hhuff::launch_qpack_sessions(call, (hipStream_t)stream);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack sessions launch");
+}
+
+HHUFF_API int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
+                                                 const hhuff_hpack_header_t* hdr, uint32_t nhdr,
+                                           const hhuff_qpack_response_t* res, const uint32_t* conn_first, uint32_t nconn,
+                                           uint32_t nres, const uint64_t* stream_id, const uint32_t* dec_off,
+                                           const uint32_t* dec_len, uint32_t header_table_size, uint64_t max_blocked,
+                                           uint32_t max_inflight, uint32_t server_off, uint32_t server_len, uint8_t* out,
+                                           const uint64_t* out_off, uint32_t* out_len, uint32_t* header_len,
+                                           int32_t* rstatus, uint8_t* rflags, uint8_t* enc_out, const uint64_t* enc_out_off,
+                                           uint32_t* enc_out_len, int32_t* dec_status, uint32_t* dec_consumed, void* scratch,
+                                           uint64_t scratch_size, unsigned flags, void* stream) {
+    return hhuff_qpack_flatten_sessions_peers(nullptr, slots, in, in_size, hdr, nhdr, res, conn_first, nconn, nres,
+        stream_id, dec_off, dec_len, header_table_size, max_blocked, max_inflight, server_off, server_len, out,
+        out_off, out_len, header_len, rstatus, rflags, enc_out, enc_out_off, enc_out_len, dec_status, dec_consumed,
+        scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API int hhuff_qpack_flatten_sessions(const uint8_t* in, uint64_t in_size, const hhuff_hpack_header_t* hdr, uint32_t nhdr,

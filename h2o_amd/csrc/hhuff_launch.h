@@ -175,6 +175,7 @@ struct QseCall {
     uint8_t* scratch;
     uint32_t flags;
     const uint32_t* cmap;  // connection slots (hhuff_slots.h); NULL: connection c in slot c
+    const hhuff_qpack_peer_t* peers;  // [nconn] peer settings (include/hhuff.h (2g'')); NULL: the call's own for all
 };
 uint64_t qpenc_conn_scratch(uint32_t header_table_size, uint32_t max_inflight);
 hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream);

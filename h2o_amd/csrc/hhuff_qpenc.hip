@@ -451,7 +451,7 @@ struct QseArgs {
     uint4* plan;     // [4 nres] {base lo, base hi, section length, frame total} {Required Insert Count, delta base |
                      // sign << 31, first field's offset in the frame, datagram-flow-id size} {codes of :status, server,
                      // content-length, datagram-flow-id} {server's insert: place lo, hi, instruction, 0}
-    uint4* cplan;    // [nconn] {enc_out region lo, hi, Set Dynamic Table Capacity first, 0}
+    uint4* cplan;    // [nconn] {enc_out region lo, hi, Set Dynamic Table Capacity first, the capacity it sets}
     LongWork lw;
 };
 
@@ -461,7 +461,8 @@ struct QsConn {
     QsEntry* ent;
     QsInflight* inf;
     uint8_t* str;
-    uint32_t cap;
+    uint32_t cap;          // the table's capacity: the call's header_table_size, or the peer's clamped to it
+    uint32_t scap;         // the string area's bytes: header_table_size whatever the capacity
     uint32_t slots, imin;  // evicting: the ring's size; the smallest reference of any inflight section
 };
 struct QsField {
@@ -599,7 +600,7 @@ __device__ uint32_t qs_field(QsConn& t, QsSection& S, const QsField& F, uint32_t
         if (fits) {
             t.s.evicted = ev;
             t.s.used = used;
-            t.s.str_used = qt_place(t.str, t.cap, t.ent, t.slots, ev, t.s.count, t.s.str_used, F.nl + F.vl);
+            t.s.str_used = qt_place(t.str, t.scap, t.ent, t.slots, ev, t.s.count, t.s.str_used, F.nl + F.vl);
             slot = qt_slot(t.s.count + 1u, t.slots);
         }
     }
@@ -780,8 +781,10 @@ __device__ __forceinline__ uint64_t qs_response_bound(uint64_t name_value_bytes,
 
 // the walk: one lane per connection -- its decoder stream, then its responses in order.  EV: the session evicts
 // (HHUFF_QENC_EVICT), DUP: it also duplicates draining entries (HHUFF_QENC_DUP, with EV only); <false, false> is
-// the table that only grows.
-template <bool EV, bool DUP, bool SLOTS>
+// the table that only grows.  PEERS: the capacity, the Required Insert Count's modulus and the blocked-stream limit
+// come from the connection's peer record (include/hhuff.h (2g'')); the ring, the string area and the slab's place
+// stay those of the call's header_table_size.
+template <bool EV, bool DUP, bool SLOTS, bool PEERS>
 __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     static_assert(EV || !DUP, "HHUFF_QENC_DUP is a mode of the evicting table");
     const QseCall& C = A.c;
@@ -798,12 +801,24 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     if (!fresh && !cs.refused) t.s = *ts;
     // a session is evicting or it is not, duplicating or not: another kind of call touches nothing of it
     constexpr uint32_t kMode = (EV ? kQsEvicting : 0u) | (DUP ? kQsDuplicating : 0u);
-    const bool wrong = cs.refused || (!fresh && (t.s.failed & (kQsEvicting | kQsDuplicating)) != kMode);
+    uint32_t cap = H, maxent = 2u * qt_slots(H);
+    uint64_t mblk = C.max_blocked;
+    if (PEERS) {
+        const hhuff_qpack_peer_t P = C.peers[c];
+        cap = min(P.max_table_capacity, H);
+        maxent = 2u * (P.max_table_capacity / 32u);  // MaxEntries of what the decoder advertised (RFC 9204 4.5.1.1)
+        mblk = min((uint64_t)P.max_blocked, mblk);
+    }
+    // likewise a peer's settings hold for a connection's life, and the record is not stored: a continuing table
+    // that holds more than the record allows was filled under another record
+    const bool wrong = cs.refused || (!fresh && (t.s.failed & (kQsEvicting | kQsDuplicating)) != kMode) ||
+                       (PEERS && !fresh && t.s.used > cap);
     t.s.failed &= 1u;
     t.ent = reinterpret_cast<QsEntry*>(scr + sizeof(QsState));
     t.inf = reinterpret_cast<QsInflight*>(scr + sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry));
     t.str = scr + sizeof(QsState) + (uint64_t)(H / 32u) * sizeof(QsEntry) + (uint64_t)M * sizeof(QsInflight);
-    t.cap = H;
+    t.cap = cap;
+    t.scap = H;
     t.slots = qt_slots(H);
     t.imin = ~0u;
 
@@ -828,13 +843,13 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
     uint64_t enc_len = 0;
     bool setcap = false, nospace = false;
     if (!wrong && !t.s.failed && fresh && (C.flags & HHUFF_QENC_SET_CAPACITY)) {
-        const uint32_t n = int_len(H, 5);
+        const uint32_t n = int_len(cap, 5);
         if (n > room)
             nospace = true;  // not even the capacity instruction fits: nothing of this step is written
         else
             setcap = true, enc_len = n;
     }
-    A.cplan[c] = make_uint4((uint32_t)ebase, (uint32_t)(ebase >> 32), setcap ? 1u : 0u, 0u);
+    A.cplan[c] = make_uint4((uint32_t)ebase, (uint32_t)(ebase >> 32), setcap ? 1u : 0u, cap);
 
     QsNames N;
     uint32_t nb;
@@ -874,7 +889,7 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
                 }
                 const uint64_t bound = qs_response_bound(nv, R.nhdr, server ? C.server_len : 0u,
                                                          (R.flags & HHUFF_QRES_DATAGRAM) ? R.dfid_len : 0u);
-                uint32_t mode = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < C.max_blocked ? 2u : 1u;
+                uint32_t mode = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < mblk ? 2u : 1u;
                 if (t.s.ninflight >= M) mode = 0u;  // no slot: as with no encoder at all
                 if (bad) {
                     st = HHUFF_RES_EINVAL;
@@ -890,7 +905,9 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
                     if (largest != 0) {  // finalize_flatten (:1263-1298), the Required Insert Count wrapped (RFC 9204 4.5.1.1)
                         if (largest < t.s.lkr) largest = t.s.lkr;
                         blocking = largest > t.s.lkr;
-                        ric = largest % (2u * t.slots) + 1u;
+                        // (a peer that advertised under 32 bytes has no entry to refer to: only a record that
+                        // changed in mid-life, the caller's error, meets the guard)
+                        ric = (PEERS && maxent == 0u ? 0u : largest % maxent) + 1u;
                         delta = largest <= S.base ? S.base - largest : 0x80000000u | (largest - S.base - 1u);
                         plen = int_len(ric, 8) + int_len(delta & 0x7FFFFFFFu, 7);
                         t.inf[t.s.ninflight] = QsInflight{C.stream_id[r], largest, S.smallest | (blocking ? 0x80000000u : 0u)};
@@ -910,7 +927,7 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
                 }
             } else {
                 const QsState snap = t.s;
-                const bool buf = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < C.max_blocked;
+                const bool buf = !(R.flags & HHUFF_QRES_NO_ENCODER_STREAM) && (uint64_t)t.s.num_blocked < mblk;
                 QsSection S;
                 QsOwn O;
                 qs_walk_section<EV, DUP>(A, t, R, r, buf ? 2u : 1u, ebase + enc_len, N, S, O);
@@ -1020,7 +1037,7 @@ __global__ __launch_bounds__(256) void qse_emit_kernel(QseArgs A) {
             if (cp.z) {  // Set Dynamic Table Capacity
                 RegSink sink;
                 sink.init(C.enc_out + ((uint64_t)cp.y << 32 | cp.x));
-                sink_int(sink, 0x20u, C.header_table_size, 5);
+                sink_int(sink, 0x20u, cp.w, 5);
                 sink.finish();
             }
             continue;
@@ -1133,20 +1150,27 @@ hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream) {
     const uint32_t ge = (uint32_t)std::min<uint64_t>((2ull * nhdr + nres + nconn + 255u) / 256u, 16384ull);
     HHUFF_LAUNCH(e, qse_prep_kernel, gp, 256, stream, A);
     if (e == hipSuccess) e = launch_long_bits(true, call.in, call.hdr, nhdr, call.server_off, call.server_len, A.rec, A.lw, stream);
-    auto walk = [&](auto slots) {  // the kernel's instantiation with or without connection slots (hhuff_slots.h)
-        constexpr bool S = decltype(slots)::value;
+    // the kernel's instantiation with or without connection slots (hhuff_slots.h) and peer records
+    auto walk = [&](auto slots, auto peers) {
+        constexpr bool S = decltype(slots)::value, P = decltype(peers)::value;
         if (call.flags & HHUFF_QENC_DUP) {  // (only with HHUFF_QENC_EVICT: the C entry refuses it alone)
-            HHUFF_LAUNCH(e, (qse_walk_kernel<true, true, S>), (nconn + 63u) / 64u, 64, stream, A);
+            HHUFF_LAUNCH(e, (qse_walk_kernel<true, true, S, P>), (nconn + 63u) / 64u, 64, stream, A);
         } else if (call.flags & HHUFF_QENC_EVICT) {
-            HHUFF_LAUNCH(e, (qse_walk_kernel<true, false, S>), (nconn + 63u) / 64u, 64, stream, A);
+            HHUFF_LAUNCH(e, (qse_walk_kernel<true, false, S, P>), (nconn + 63u) / 64u, 64, stream, A);
         } else {
-            HHUFF_LAUNCH(e, (qse_walk_kernel<false, false, S>), (nconn + 63u) / 64u, 64, stream, A);
+            HHUFF_LAUNCH(e, (qse_walk_kernel<false, false, S, P>), (nconn + 63u) / 64u, 64, stream, A);
         }
     };
-    if (call.cmap)
-        walk(std::true_type{});
+    auto walk_slots = [&](auto peers) {
+        if (call.cmap)
+            walk(std::true_type{}, peers);
+        else
+            walk(std::false_type{}, peers);
+    };
+    if (call.peers)
+        walk_slots(std::true_type{});
     else
-        walk(std::false_type{});
+        walk_slots(std::false_type{});
     HHUFF_LAUNCH(e, qse_emit_kernel, ge, 256, stream, A);
     if (e == hipSuccess) e = launch_long_payload(call.in, A.lw, stream);
     const hipError_t f = hipFreeAsync(ws, stream);

@@ -582,3 +582,17 @@ def to_qpack_sessions(batch, steps, seed=0, requests=False, dfid_frac=0.02, odd_
                         server_off=q["server_off"], server_len=q["server_len"],
                         out_off=qpack_session_out_offsets(hdr, res, q["server_len"])))
     return out
+
+
+def qpack_peer_population(nconn, capacities, blocked_limits, seed=0):
+    """One hhuff_qpack_peer_t record (codec.QPACK_PEER) per connection for the peers= argument of the encoder
+    sessions: max_table_capacity drawn from `capacities` and max_blocked from `blocked_limits`, independently and
+    uniformly, seeded.  A test population that mixes settings inside every wave; it makes no claim about what real
+    clients advertise."""
+    from .codec import QPACK_PEER
+
+    rng = np.random.default_rng(seed)
+    p = np.zeros(nconn, QPACK_PEER)
+    p["max_table_capacity"] = np.asarray(capacities, np.uint32)[rng.integers(0, len(capacities), nconn)]
+    p["max_blocked"] = np.asarray(blocked_limits, np.uint32)[rng.integers(0, len(blocked_limits), nconn)]
+    return p

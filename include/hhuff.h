@@ -797,6 +797,58 @@ int hhuff_qpack_flatten_sessions(const uint8_t *in, uint64_t in_size, const hhuf
                                  int32_t *dec_status, uint32_t *dec_consumed, void *scratch, uint64_t scratch_size,
                                  unsigned flags, void *stream);
 
+/* (2g'') Encoder sessions with per-connection peer settings.  h2o creates a connection's encoder from that peer's
+ *      SETTINGS frame (lib/http3/common.c:1441-1468, h2o_qpack_create_encoder, qpack.c:884): its table capacity is
+ *      min(the peer's SETTINGS_QPACK_MAX_TABLE_CAPACITY, our own encoder_table_capacity), its blocked-stream limit
+ *      the peer's SETTINGS_QPACK_BLOCKED_STREAMS.  hhuff_qpack_flatten_sessions_peers is
+ *      hhuff_qpack_flatten_sessions_slots (2h) with one record per connection of the call in front; a batch that
+ *      mixes peers goes through one call and one scratch of equal slabs.  peers == NULL is the _slots call: the
+ *      same bytes, statuses, scratch contents, launches and workspace.  With peers given (device, [nconn],
+ *      4-byte aligned), H = the call's header_table_size still fixes the slab stride and
+ *      hhuff_qpack_enc_scratch_size(), and per connection c:
+ *      1. Capacity.  cap_c = min(peers[c].max_table_capacity, H) stands wherever (2g') uses header_table_size as
+ *         a capacity: the insert room tests of both table kinds, need <= header_table_size of point 3, the
+ *         draining quarter cap_c / 4 of point 7, the value HHUFF_QENC_SET_CAPACITY writes, and
+ *         "header_table_size + 4 bytes always fit", which is cap_c + 4.  The entry ring and the string area keep
+ *         the slab's geometry (H / 32 slots, H bytes).
+ *      2. MaxEntries.  The wrapped Required Insert Count of point 4 is (largest_ref mod (2 *
+ *         (peers[c].max_table_capacity / 32))) + 1: RFC 9204 4.5.1.1 takes MaxEntries from the capacity the
+ *         decoder advertised, not from the one the encoder chose to use.  With fewer than 32 bytes advertised
+ *         nothing is ever inserted and no section has a dynamic reference.  With max_table_capacity <= H this is
+ *         the modulus of (2g') at header_table_size = cap_c.
+ *      3. Blocked streams.  A section has an encoder buffer when num_blocked < min(peers[c].max_blocked,
+ *         max_blocked): the call's own max_blocked stays as the server's cap (UINT64_MAX: the peer's value alone).
+ *      4. Equivalence.  For a connection with max_table_capacity <= H every byte of out and enc_out, every status,
+ *         length and flag is what hhuff_qpack_flatten_sessions_slots produces for it with header_table_size =
+ *         max_table_capacity and max_blocked = min(peers[c].max_blocked, max_blocked).
+ *      5. Stability.  A peer's SETTINGS arrive once (RFC 9114 7.2.4): peers[c] must be the same in every step of
+ *         a connection's life.  The session does not store it.  One violation is caught: a continuing connection
+ *         whose table holds more than cap_c bytes is refused for the step exactly like the mode mismatch --
+ *         dec_status[c] and every rstatus[r] = HHUFF_RES_EINVAL, nothing written, the slab untouched.  Any other
+ *         change is the caller's error; it stays memory-safe because cap_c <= H always.  A fresh connection (a
+ *         call without HHUFF_QENC_CONTINUE, or HHUFF_CONN_RESET) takes whatever peers[c] says: that is how a slot
+ *         is reused by another peer.
+ *      6. The call returns HHUFF_EINVAL and enqueues nothing for a peers pointer that is not 4-byte aligned;
+ *         everything the _slots call refuses is refused alike.
+ *      No launch and no workspace beyond the _slots call's. */
+typedef struct hhuff_qpack_peer {
+    uint32_t max_table_capacity; /* the peer's SETTINGS_QPACK_MAX_TABLE_CAPACITY; 0 when it sent none;
+                                    the caller saturates larger values at 2^32 - 1 */
+    uint32_t max_blocked;        /* the peer's SETTINGS_QPACK_BLOCKED_STREAMS, saturated likewise */
+} hhuff_qpack_peer_t;            /* 8 bytes */
+struct hhuff_conn_slots;         /* (2h) */
+int hhuff_qpack_flatten_sessions_peers(const hhuff_qpack_peer_t *peers, const struct hhuff_conn_slots *slots,
+                                       const uint8_t *in, uint64_t in_size, const hhuff_hpack_header_t *hdr,
+                                       uint32_t nhdr, const hhuff_qpack_response_t *res, const uint32_t *conn_first,
+                                       uint32_t nconn, uint32_t nres, const uint64_t *stream_id,
+                                       const uint32_t *dec_off, const uint32_t *dec_len, uint32_t header_table_size,
+                                       uint64_t max_blocked, uint32_t max_inflight, uint32_t server_off,
+                                       uint32_t server_len, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
+                                       uint32_t *header_len, int32_t *rstatus, uint8_t *rflags, uint8_t *enc_out,
+                                       const uint64_t *enc_out_off, uint32_t *enc_out_len, int32_t *dec_status,
+                                       uint32_t *dec_consumed, void *scratch, uint64_t scratch_size, unsigned flags,
+                                       void *stream);
+
 /* (2h) Connection slots: connections that come and go.  The four stateful families above -- HPACK blocks
  *      (hhuff_hpack_decode_blocks / _parse_requests / _parse_responses), the QPACK decoder step (hhuff_qpack_decode
  *      / _parse_requests / _parse_responses), the HPACK encoder (hhuff_hpack_flatten_responses) and the QPACK
@@ -942,7 +994,8 @@ int hhuff_qpack_flatten_sessions_slots(const hhuff_conn_slots_t *slots, const ui
  *      5. Import rebuilds the slab of slot slot[k] from item k's image (img_len[k] = its length, as export gave
  *         it).  The family's next call lists the connection in that slot with its *_CONTINUE flag and without
  *         HHUFF_CONN_RESET, and the connection continues exactly as it would have at its source; a QPACK encoder
- *         session keeps its mode (evicting, duplicating), so the mode-mismatch refusal works after a move.  Slot
+ *         session keeps its mode (evicting, duplicating), so the mode-mismatch refusal works after a move; its
+ *         peer record (2g'') is not in the image: it travels with the caller, as the slot number does.  Slot
  *         ownership is (2h) point 3: the lowest-numbered item that names a slot owns it, the others get
  *         HHUFF_IMG_EINVAL, as does a slot >= nslots (export too).  An item with a non-zero status leaves its slab
  *         untouched.

@@ -12,6 +12,9 @@
 // takes them from its input), acknowledgments and cancellations that release the sections' pins.  After every
 // operation the ring is compared with the list: indices, lengths, every string byte, `used`.  The run fails
 // unless it saw a duplication that evicted its own source and one whose compaction wrote over the source.
+// A second pass replays the same kind of sequences on tables whose capacity is a peer's, clamped below the slab's
+// (hhuff_qpack_flatten_sessions_peers): cap < 32 * slots and str_cap > cap, the ring and the string area still
+// those of header_table_size -- capacities 0, 31, 32, 33, 64, 100, half the slab and one entry short of it.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,12 +32,12 @@ using namespace hhuff;
 
 namespace {
 struct Table {
-    uint32_t cap, slots, count = 0, evicted = 0, used = 0, str_used = 0;
+    uint32_t cap, scap, slots, count = 0, evicted = 0, used = 0, str_used = 0;  // scap: the string area's bytes
     std::unique_ptr<QsEntry[]> ent;
     std::unique_ptr<uint8_t[]> str;
     std::deque<std::string> live;  // the bookkeeping: name + value of entries evicted + 1 .. count
     std::deque<uint32_t> name_len;
-    explicit Table(uint32_t H) : cap(H), slots(qt_slots(H)), ent(new QsEntry[qt_slots(H)]), str(new uint8_t[H]) {}
+    Table(uint32_t H, uint32_t cap_) : cap(cap_), scap(H), slots(qt_slots(H)), ent(new QsEntry[qt_slots(H)]), str(new uint8_t[H]) {}
 };
 
 #define CHECK(c)                                                       \
@@ -52,7 +55,7 @@ void compare(const Table& t) {
         const QsEntry& e = t.ent[qt_slot(i, t.slots)];
         const std::string& s = t.live[i - t.evicted - 1];
         CHECK(e.nl == t.name_len[i - t.evicted - 1] && e.nl + e.vl == s.size());
-        CHECK((uint64_t)e.noff + s.size() <= t.cap && memcmp(t.str.get() + e.noff, s.data(), s.size()) == 0);
+        CHECK((uint64_t)e.noff + s.size() <= t.scap && memcmp(t.str.get() + e.noff, s.data(), s.size()) == 0);
         if (i > t.evicted + 1) CHECK(e.noff == run);  // one contiguous run in insert order
         run = e.noff + e.nl + e.vl;
         used += (uint32_t)s.size() + 32u;
@@ -98,10 +101,10 @@ bool insert(Table& t, const std::string& name, const std::string& value, uint32_
     for (; k; --k) t.live.pop_front(), t.name_len.pop_front();
     const uint32_t len = (uint32_t)(name.size() + value.size());
     const uint32_t tail = t.str_used;
-    t.str_used = qt_place(t.str.get(), t.cap, t.ent.get(), t.slots, t.evicted, t.count, t.str_used, len);
+    t.str_used = qt_place(t.str.get(), t.scap, t.ent.get(), t.slots, t.evicted, t.count, t.str_used, len);
     g_compacted = t.str_used != tail;
     g_compactions += g_compacted ? 1u : 0u;
-    CHECK((uint64_t)t.str_used + len <= t.cap);
+    CHECK((uint64_t)t.str_used + len <= t.scap);
     memcpy(t.str.get() + t.str_used, name.data(), name.size());
     memcpy(t.str.get() + t.str_used + name.size(), value.data(), value.size());
     t.ent[qt_slot(t.count + 1u, t.slots)] =
@@ -121,8 +124,20 @@ int main(int argc, char** argv) {
     auto pick = [&](uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rng() % (hi - lo + 1)); };
     uint64_t inserts = 0, refused = 0, evictions = 0;
     uint64_t dups = 0, dup_refused = 0, dup_self = 0, dup_over = 0, not_draining = 0;
-    for (int s = 0; s < nseq; ++s) {
-        Table t(pick(64, 512));
+    uint64_t clamped_inserts = 0, clamped_evictions = 0, clamped_compactions = 0;
+    for (int s = 0; s < 2 * nseq; ++s) {
+        if (s == nseq) {  // the first pass, capacity = the slab's, has seen both duplications
+            CHECK(dup_self > 0 && dup_over > 0);
+            clamped_inserts = inserts, clamped_evictions = evictions, clamped_compactions = g_compactions;
+        }
+        const uint32_t H = pick(64, 512);
+        uint32_t cap = H;
+        if (s >= nseq) {  // a peer's capacity under the slab's
+            const uint32_t caps[] = {0u, 31u, 32u, 33u, 64u, 100u, H / 2u, H - 32u};
+            cap = caps[s % 8];
+            if (cap >= 32u * qt_slots(H)) cap = 32u * qt_slots(H) - 1u;
+        }
+        Table t(H, cap);
         std::vector<uint32_t> inflight;  // the sections' smallest references
         uint32_t lkr = 0;
         for (int op = 0, nop = (int)pick(20, 200); op < nop; ++op) {
@@ -195,8 +210,8 @@ int main(int argc, char** argv) {
             compare(t);
         }
     }
-    CHECK(dup_self > 0 && dup_over > 0);
-    printf("ok: %d sequences, %llu inserts (%llu entries evicted, %llu compactions), %llu refused; %llu duplications "
+    CHECK(inserts > clamped_inserts && evictions > clamped_evictions && g_compactions > clamped_compactions);
+    printf("ok: 2 x %d sequences (the second half at capacities under the slab's), %llu inserts (%llu entries evicted, %llu compactions), %llu refused; %llu duplications "
            "(%llu evicted their source, %llu of those compacted over it), %llu refused, %llu matches not draining\n",
            nseq, (unsigned long long)inserts, (unsigned long long)evictions, (unsigned long long)g_compactions,
            (unsigned long long)refused, (unsigned long long)dups, (unsigned long long)dup_self,
