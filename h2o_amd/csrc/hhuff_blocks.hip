@@ -21,6 +21,7 @@
 
 #include <type_traits>
 
+#include "hhuff_decwork.h"
 #include "hhuff_device.h"
 #include "hhuff_image.h"
 #include "hhuff.h"
@@ -49,22 +50,8 @@ constexpr uint32_t kLitHuffmanV = 4, kLitUpperV = 5;  // HHUFF_LIT_HUFFMAN / _UP
 constexpr uint32_t kClsUnknown = 0xFFFFu;  // a table entry's name class not computed yet
 }  // namespace
 
-struct BlkArgs {
-    const uint8_t* in;
-    uint64_t in_size;
-    const uint32_t* blk_off;
-    const uint32_t* conn_first;
-    uint32_t nconn, table_size;
-    uint8_t* arena;
-    const uint64_t* arena_off;
-    uint32_t *name_off, *name_len, *value_off, *value_len;
-    uint8_t* fflags;
-    uint32_t* nfields;
-    int32_t* bstatus;
-    uint8_t* scratch;
+struct BlkArgs : HpdCall {  // the call, and what launch_hpack_blocks adds to it
     uint64_t conn_scratch;  // bytes of scratch per connection
-    uint32_t flags;         // HHUFF_BLK_CONTINUE: start from the tables the previous call left in scratch
-    hhuff_request_t* req;   // request mode (hhuff_hpack_parse_requests): h2o_hpack_parse_request per block
     // pre-decoded literals: bit p of lit_bits marks a string literal starting at input byte p, word_pre[w]
     // counts the marks before word w, and literal r (in position order) has the results of the literal
     // kernels: lit_len, lit_pay, lit_cons, lit_st, bytes at lit_out + floor(8 lit_pay[r] / 5).  NULL
@@ -79,9 +66,6 @@ struct BlkArgs {
     // per field slot: the byte sources of its name and value (read by the copy pass)
     uint64_t* fsrc_n;
     uint64_t* fsrc_v;
-    hhuff_response_t* res;   // response mode (hhuff_hpack_parse_responses): h2o_hpack_parse_response per block
-    const uint8_t* trailers;  // response mode: per block, nonzero = trailers (status == NULL); NULL = none
-    const uint32_t* cmap;     // connection slots (hhuff_slots.h); NULL: connection c in slot c
 };
 constexpr int kWalkPlain = 0, kWalkReq = 1, kWalkResp = 2;  // hpack_walk_kernel modes
 
@@ -585,7 +569,7 @@ __global__ __launch_bounds__(256) void blk_table_kernel(BlkArgs A) {
 // connections' literals in lock step, each field costing the wave its slowest lane's literal.  The walk
 // marks may include literals past a table-dependent error (an index beyond the table): decoded, unused.
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t kMarkThreads = 256, kChunkWords = 1024;  // list pass: 1024 bitmap words per block
+constexpr uint32_t kMarkThreads = 256, kChunkWords = kLitChunkWords;  // list pass: 1024 bitmap words per block
 
 // literal at p (H flag + 7-bit-prefix length, then the payload) inside [p, end): mark it, step over it
 __device__ __forceinline__ bool mark_literal(const Win& W, uint64_t& p, uint64_t end, bool is_name,
@@ -723,8 +707,6 @@ __global__ __launch_bounds__(kMarkThreads) void blk_list_kernel(const uint32_t* 
         }
     }
 }
-uint64_t literal_list_chunks(uint64_t nwords) { return (nwords + kChunkWords - 1) / kChunkWords; }
-
 hipError_t launch_literal_list(const uint32_t* lit_bits, const uint32_t* name_bits, const uint32_t* pfx_bits, uint32_t pfx_alt,
                                uint32_t pfx_name, uint64_t nwords, uint32_t* chunk, uint32_t* word_pre, uint32_t* list, uint32_t* lnames,
                                uint8_t* prefix_of, hipStream_t stream) {
@@ -741,90 +723,50 @@ uint64_t hpack_conn_scratch(uint32_t table_size) {
     return sizeof(TableState) + (uint64_t)tbl_entries(table_size) * sizeof(Entry) + 2 * tbl_ring(table_size);
 }
 
-hipError_t launch_hpack_blocks(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off, const uint32_t* conn_first,
-                               uint32_t nconn, uint32_t table_size, uint8_t* arena, const uint64_t* arena_off,
-                               uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
-                               uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_request_t* req,
-                               hhuff_response_t* res, const uint8_t* trailers, uint8_t* scratch, uint32_t flags,
-                               hipStream_t stream, const uint32_t* cmap) {
+hipError_t launch_hpack_blocks(const HpdCall& call, hipStream_t stream) {
+    const uint32_t nconn = call.nconn;
+    const uint64_t in_size = call.in_size;
     if (nconn == 0) return hipSuccess;
-    BlkArgs A{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-              value_len, fflags, nfields, bstatus, scratch, hpack_conn_scratch(table_size), flags, req,
-              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, res, trailers, cmap};
-    // workspace (the library's stream-ordered pool): field sources for every slot (block byte);
-    // with the literal pre-pass (inputs below 4 GiB: u32 positions) its bitmaps, word prefixes, chunk sums,
-    // the literal list and results, and the decoded bytes
-    const uint64_t nslots = in_size;
-    const bool prepass = in_size > 0 && in_size < (1ull << 32);
-    const uint64_t nwords = (in_size + 31) / 32, nchunks = (nwords + kChunkWords - 1) / kChunkWords;
-    const uint64_t n_max = (2 * in_size) / 3 + 2;  // a field with two literals takes >= 3 bytes
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    uint64_t o = 0;
-    const uint64_t o_lit = o;
-    if (prepass) o += up(4 * nwords);
-    const uint64_t o_name = o;
-    if (prepass) o += up(4 * nwords);
-    const uint64_t o_lnames = o;
-    if (prepass) o += up(4 * ((n_max + 31) / 32));
-    const uint64_t zero_end = o;  // [0, zero_end) starts zeroed
-    const uint64_t o_fsn = o;
-    o += up(8 * nslots + 8);
-    const uint64_t o_fsv = o;
-    o += up(8 * nslots + 8);
-    const uint64_t o_pre = o, o_chunk = o_pre + (prepass ? up(4 * nwords) : 0);
-    const uint64_t o_list = o_chunk + (prepass ? up(4 * nchunks + 4) : 0);
-    const uint64_t o_len = o_list + (prepass ? up(4 * n_max) : 0);
-    const uint64_t o_pay = o_len + (prepass ? up(4 * n_max) : 0);
-    const uint64_t o_cons = o_pay + (prepass ? up(4 * n_max) : 0);
-    const uint64_t o_st = o_cons + (prepass ? up(4 * n_max) : 0);
-    const uint64_t o_ws = o_st + (prepass ? up(n_max) : 0);
-    const uint64_t o_out = o_ws + (prepass ? up(literals_dev_ws((uint32_t)n_max, in_size)) : 0);
-    o = o_out + (prepass ? up((8 * in_size) / 5 + 64) : 0);
+    // workspace (the library's stream-ordered pool, hhuff_decwork.h): field sources for every slot (block
+    // byte); with the literal pre-pass (inputs below 4 GiB: u32 positions) its bitmaps, word prefixes, chunk
+    // sums, the literal list and results, and the decoded bytes
+    const bool prepass = hpd_prepass(in_size);
+    const LitDims d = hpd_dims(in_size);
+    const uint64_t lit_ws = prepass ? literals_dev_ws((uint32_t)d.n_max, in_size) : 0;
+    HpdWork W;
     uint8_t* work = nullptr;
-    hipError_t e = work_alloc((void**)&work, o, stream);
+    hipError_t e = work_alloc((void**)&work, hpd_carve(W, in_size, lit_ws, nullptr), stream);
     if (e != hipSuccess) return e;
-    A.fsrc_n = reinterpret_cast<uint64_t*>(work + o_fsn);
-    A.fsrc_v = reinterpret_cast<uint64_t*>(work + o_fsv);
-    e = hipMemsetAsync(work, 0, zero_end, stream);
+    hpd_carve(W, in_size, lit_ws, work);
+    const LitWork& L = W.lit;  // (all NULL without the pre-pass: every literal is decoded in place)
+    const BlkArgs A{call, hpack_conn_scratch(call.table_size), L.lit_bits, L.word_pre, L.len, L.pay, L.cons, L.st, L.out,
+                    W.fsrc_n, W.fsrc_v};
+    e = hipMemsetAsync(work, 0, W.zero_end, stream);
     if (e == hipSuccess && prepass) {
-        uint32_t* lit_bits = reinterpret_cast<uint32_t*>(work + o_lit);
-        uint32_t* name_bits = reinterpret_cast<uint32_t*>(work + o_name);
-        uint32_t* lnames = reinterpret_cast<uint32_t*>(work + o_lnames);
-        uint32_t* word_pre = reinterpret_cast<uint32_t*>(work + o_pre);
-        uint32_t* chunk = reinterpret_cast<uint32_t*>(work + o_chunk);
-        uint32_t* n_lit = chunk + nchunks;
-        uint32_t* list = reinterpret_cast<uint32_t*>(work + o_list);
-        hipLaunchKernelGGL(blk_mark_kernel, dim3(2048), dim3(kMarkThreads), 0, stream, in, in_size, blk_off, conn_first,
-                           nconn, lit_bits, name_bits);
+        hipLaunchKernelGGL(blk_mark_kernel, dim3(2048), dim3(kMarkThreads), 0, stream, A.in, in_size, A.blk_off, A.conn_first,
+                           nconn, L.lit_bits, L.name_bits);
         e = hipGetLastError();
         if (e == hipSuccess)
-            e = launch_literal_list(lit_bits, name_bits, nullptr, 7u, 7u, nwords, chunk, word_pre, list, lnames, nullptr, stream);
+            e = launch_literal_list(L.lit_bits, L.name_bits, nullptr, 7u, 7u, d.nwords, L.chunk, L.word_pre, L.list, L.lnames,
+                                    nullptr, stream);
         if (e == hipSuccess)
-            e = launch_literals_dev(in, in_size, list, (uint32_t)n_max, n_lit, 7u, kLitNoRawCopy, lnames, work + o_out,
-                                    reinterpret_cast<uint32_t*>(work + o_len), reinterpret_cast<uint32_t*>(work + o_pay),
-                                    reinterpret_cast<uint32_t*>(work + o_cons), work + o_st, work + o_ws, stream);
-        A.lit_bits = lit_bits;
-        A.word_pre = word_pre;
-        A.lit_len = reinterpret_cast<const uint32_t*>(work + o_len);
-        A.lit_pay = reinterpret_cast<const uint32_t*>(work + o_pay);
-        A.lit_cons = reinterpret_cast<const uint32_t*>(work + o_cons);
-        A.lit_st = work + o_st;
-        A.lit_out = work + o_out;
+            e = launch_literals_dev(A.in, in_size, L.list, (uint32_t)d.n_max, L.chunk + d.nchunks, 7u, kLitNoRawCopy, L.lnames,
+                                    L.out, L.len, L.pay, L.cons, L.st, L.ws, stream);
     }
     if (e == hipSuccess) {
         const uint32_t blocks = min((nconn + kBlkThreads - 1u) / kBlkThreads, 65535u);
         auto walk = [&](auto slots) {  // the kernels' instantiation with or without connection slots
             constexpr bool S = decltype(slots)::value;
-            if (req)
+            if (A.req)
                 hipLaunchKernelGGL((hpack_walk_kernel<kWalkReq, S>), dim3(blocks), dim3(kBlkThreads), 0, stream, A);
-            else if (res)
+            else if (A.res)
                 hipLaunchKernelGGL((hpack_walk_kernel<kWalkResp, S>), dim3(blocks), dim3(kBlkThreads), 0, stream, A);
             else
                 hipLaunchKernelGGL((hpack_walk_kernel<kWalkPlain, S>), dim3(blocks), dim3(kBlkThreads), 0, stream, A);
             hipLaunchKernelGGL(blk_copy_kernel, dim3(4096), dim3(256), 0, stream, A);
             hipLaunchKernelGGL(blk_table_kernel<S>, dim3((uint32_t)(((uint64_t)nconn + 3) / 4)), dim3(256), 0, stream, A);
         };
-        if (cmap)
+        if (A.cmap)
             walk(std::true_type{});
         else
             walk(std::false_type{});

@@ -227,43 +227,37 @@ HHUFF_API uint64_t hhuff_hpack_scratch_size(uint32_t nconn, uint32_t table_size)
 }
 
 namespace {
-int hpack_blocks(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                 const uint32_t* blk_off, const uint32_t* conn_first, uint32_t nconn,
-                 uint32_t table_size, uint8_t* arena, const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
-                 uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* bstatus,
-                 hhuff_request_t* req, hhuff_response_t* res, const uint8_t* trailers, void* scratch,
-                 uint64_t scratch_size, unsigned flags, void* stream) {
-    if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size, hhuff::hpack_conn_scratch(table_size)))
+// the checks and the launch the six HPACK block calls share; c.cmap is made here
+int hpack_blocks(const hhuff_conn_slots_t* slots, hhuff::HpdCall& c, uint64_t scratch_size, void* stream) {
+    if (const char* bad = hhuff::conn_slots_check(slots, c.nconn, scratch_size, hhuff::hpack_conn_scratch(c.table_size)))
         return arg_fail(bad);
-    if (nconn == 0) return HHUFF_OK;
-    if (!in || !blk_off || !conn_first || !arena || !arena_off || !name_off || !name_len || !value_off || !value_len ||
-        !fflags || !nfields || !bstatus || !scratch)
+    if (c.nconn == 0) return HHUFF_OK;
+    if (!c.in || !c.blk_off || !c.conn_first || !c.arena || !c.arena_off || !c.name_off || !c.name_len || !c.value_off ||
+        !c.value_len || !c.fflags || !c.nfields || !c.bstatus || !c.scratch)
         return arg_fail("NULL array");
-    if (!slots && scratch_size < hhuff_hpack_scratch_size(nconn, table_size))
+    if (!slots && scratch_size < hhuff_hpack_scratch_size(c.nconn, c.table_size))
         return arg_fail("scratch smaller than hhuff_hpack_scratch_size");
-    if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
-    if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
-    if (((uintptr_t)res & 3u) != 0) return arg_fail("res must be 4-byte aligned");
+    if (((uintptr_t)c.scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
+    if (((uintptr_t)c.req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
+    if (((uintptr_t)c.res & 3u) != 0) return arg_fail("res must be 4-byte aligned");
     ConnMap map((hipStream_t)stream);
-    hipError_t e = map.make(slots, nconn);
+    hipError_t e = map.make(slots, c.nconn);
     if (e != hipSuccess) return hip_fail(e, "connection slots");
-    e = hhuff::launch_hpack_blocks(in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                                   value_off, value_len, fflags, nfields, bstatus, req, res, trailers, (uint8_t*)scratch,
-                                   flags, (hipStream_t)stream, map.cmap);
+    c.cmap = map.cmap;
+    e = hhuff::launch_hpack_blocks(c, (hipStream_t)stream);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "hpack block launch");
 }
 }  // namespace
 
 HHUFF_API int hhuff_hpack_decode_blocks_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                                              const uint32_t* blk_off,
-                                        const uint32_t* conn_first, uint32_t nconn, uint32_t table_size, uint8_t* arena,
-                                        const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
-                                        uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
-                                        int32_t* bstatus, void* scratch, uint64_t scratch_size, unsigned flags,
-                                        void* stream) {
-    return hpack_blocks(slots, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                        value_off, value_len, fflags, nfields, bstatus, nullptr, nullptr, nullptr, scratch, scratch_size,
-                        flags, stream);
+                                              const uint32_t* blk_off, const uint32_t* conn_first, uint32_t nconn,
+                                              uint32_t table_size, uint8_t* arena, const uint64_t* arena_off,
+                                              uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
+                                              uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* bstatus,
+                                              void* scratch, uint64_t scratch_size, unsigned flags, void* stream) {
+    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, nullptr, nullptr, nullptr, nullptr};
+    return hpack_blocks(slots, call, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_hpack_decode_blocks(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off,
@@ -272,22 +266,22 @@ HHUFF_API int hhuff_hpack_decode_blocks(const uint8_t* in, uint64_t in_size, con
                                         uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
                                         int32_t* bstatus, void* scratch, uint64_t scratch_size, unsigned flags,
                                         void* stream) {
-    return hhuff_hpack_decode_blocks_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, arena,
-        arena_off, name_off, name_len, value_off, value_len, fflags, nfields, bstatus, scratch, scratch_size, flags,
-        stream);
+    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, nullptr, nullptr, nullptr, nullptr};
+    return hpack_blocks(nullptr, call, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_hpack_parse_requests_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                                               const uint32_t* blk_off,
-                                         const uint32_t* conn_first, uint32_t nconn, uint32_t table_size, uint8_t* arena,
-                                         const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
-                                         uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
-                                         int32_t* bstatus, hhuff_request_t* req, void* scratch, uint64_t scratch_size,
-                                         unsigned flags, void* stream) {
+                                               const uint32_t* blk_off, const uint32_t* conn_first, uint32_t nconn,
+                                               uint32_t table_size, uint8_t* arena, const uint64_t* arena_off,
+                                               uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
+                                               uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* bstatus,
+                                               hhuff_request_t* req, void* scratch, uint64_t scratch_size, unsigned flags,
+                                               void* stream) {
     if (nconn != 0 && !req) return arg_fail("NULL array");
-    return hpack_blocks(slots, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                        value_off, value_len, fflags, nfields, bstatus, req, nullptr, nullptr, scratch, scratch_size,
-                        flags, stream);
+    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, req, nullptr, nullptr, nullptr};
+    return hpack_blocks(slots, call, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_hpack_parse_requests(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off,
@@ -296,22 +290,23 @@ HHUFF_API int hhuff_hpack_parse_requests(const uint8_t* in, uint64_t in_size, co
                                          uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
                                          int32_t* bstatus, hhuff_request_t* req, void* scratch, uint64_t scratch_size,
                                          unsigned flags, void* stream) {
-    return hhuff_hpack_parse_requests_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, arena,
-        arena_off, name_off, name_len, value_off, value_len, fflags, nfields, bstatus, req, scratch, scratch_size,
-        flags, stream);
+    if (nconn != 0 && !req) return arg_fail("NULL array");
+    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, req, nullptr, nullptr, nullptr};
+    return hpack_blocks(nullptr, call, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_hpack_parse_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                                                const uint32_t* blk_off,
-                                          const uint32_t* conn_first, uint32_t nconn, uint32_t table_size,
-                                          const uint8_t* trailers, uint8_t* arena, const uint64_t* arena_off,
-                                          uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
-                                          uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_response_t* res,
-                                          void* scratch, uint64_t scratch_size, unsigned flags, void* stream) {
+                                                const uint32_t* blk_off, const uint32_t* conn_first, uint32_t nconn,
+                                                uint32_t table_size, const uint8_t* trailers, uint8_t* arena,
+                                                const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
+                                                uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+                                                int32_t* bstatus, hhuff_response_t* res, void* scratch,
+                                                uint64_t scratch_size, unsigned flags, void* stream) {
     if (nconn != 0 && !res) return arg_fail("NULL array");
-    return hpack_blocks(slots, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len,
-                        value_off, value_len, fflags, nfields, bstatus, nullptr, res, trailers, scratch, scratch_size,
-                        flags, stream);
+    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, nullptr, res, trailers, nullptr};
+    return hpack_blocks(slots, call, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_hpack_parse_responses(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off,
@@ -320,9 +315,10 @@ HHUFF_API int hhuff_hpack_parse_responses(const uint8_t* in, uint64_t in_size, c
                                           uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
                                           uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_response_t* res,
                                           void* scratch, uint64_t scratch_size, unsigned flags, void* stream) {
-    return hhuff_hpack_parse_responses_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, trailers,
-        arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, bstatus, res, scratch,
-        scratch_size, flags, stream);
+    if (nconn != 0 && !res) return arg_fail("NULL array");
+    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, nullptr, res, trailers, nullptr};
+    return hpack_blocks(nullptr, call, scratch_size, stream);
 }
 
 HHUFF_API uint64_t hhuff_hpack_enc_scratch_size(uint32_t nconn) { return (uint64_t)nconn * hhuff::hpenc_conn_scratch(); }
@@ -472,50 +468,43 @@ HHUFF_API uint64_t hhuff_qpack_scratch_size(uint32_t nconn, uint32_t header_tabl
 }
 
 namespace {
-int qpack_step(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-               const uint32_t* enc_off, const uint32_t* enc_len,
-               const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
-               uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked, uint8_t* arena,
-               const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
-               uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
-               int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count, const uint64_t* stream_id,
-               hhuff_qpack_request_t* req, hhuff_qpack_response_head_t* res, void* scratch, uint64_t scratch_size,
-               unsigned flags, void* stream, bool sessions = false, const hhuff_qpack_dsessions_t* ds = nullptr) {
-    if (sessions && max_blocked > 4096) return arg_fail("sessions: max_blocked above 4096");
-    if (slots && header_table_size > (1u << 30)) return arg_fail("header_table_size above 2^30");
-    if (const char* bad = hhuff::conn_slots_check(slots, nconn, scratch_size, hhuff::qpack_conn_scratch(header_table_size)))
+// the checks and the launch the eight QPACK decoder calls share; c.cmap is made here.  sessions: one of the
+// two _sessions calls, which `ds` alone cannot tell (they refuse a NULL ds, but only behind other checks)
+int qpack_step(const hhuff_conn_slots_t* slots, hhuff::QpdCall& c, bool sessions, const hhuff_qpack_dsessions_t* ds,
+               uint64_t scratch_size, void* stream) {
+    if (sessions && c.max_blocked > 4096) return arg_fail("sessions: max_blocked above 4096");
+    if (slots && c.T > (1u << 30)) return arg_fail("header_table_size above 2^30");
+    if (const char* bad = hhuff::conn_slots_check(slots, c.nconn, scratch_size, hhuff::qpack_conn_scratch(c.T)))
         return arg_fail(bad);
-    if (nconn == 0) return HHUFF_OK;
+    if (c.nconn == 0) return HHUFF_OK;
     if (sessions) {  // include/hhuff.h (2e''')
         if (!ds) return arg_fail("sessions: NULL hhuff_qpack_dsessions_t");
-        if (nconn > 0x7FFFFFFFu) return arg_fail("sessions: nconn above 2^31 - 1");
-        if (!ds->state || !ds->dec_out || !ds->dec_out_off || !ds->dec_out_len || (!ds->wake_id && max_blocked) || !ds->wake_first ||
-            !ds->nwake || !ds->parked || !ds->dflags || (ds->cancel_first && !ds->cancel_id))
+        if (c.nconn > 0x7FFFFFFFu) return arg_fail("sessions: nconn above 2^31 - 1");
+        if (!ds->state || !ds->dec_out || !ds->dec_out_off || !ds->dec_out_len || (!ds->wake_id && c.max_blocked) ||
+            !ds->wake_first || !ds->nwake || !ds->parked || !ds->dflags || (ds->cancel_first && !ds->cancel_id))
             return arg_fail("sessions: NULL array");
         if (ds->flags & ~HHUFF_QDS_SYNC) return arg_fail("sessions: unknown flag bit");
-        if (ds->state_size < hhuff_qpack_dsession_state_size(slots ? slots->nslots : nconn, (uint32_t)max_blocked))
+        if (ds->state_size < hhuff_qpack_dsession_state_size(slots ? slots->nslots : c.nconn, (uint32_t)c.max_blocked))
             return arg_fail("sessions: state smaller than hhuff_qpack_dsession_state_size");
         if (((uintptr_t)ds->state & 15u) != 0) return arg_fail("sessions: state must be 16-byte aligned");
     }
-    if (!in || !enc_off || !enc_len || !sec_off || !conn_first || !enc_status || !enc_consumed || !insert_count ||
-        !scratch)
+    if (!c.in || !c.enc_off || !c.enc_len || !c.sec_off || !c.conn_first || !c.enc_status || !c.enc_consumed ||
+        !c.insert_count || !c.scratch)
         return arg_fail("NULL array");
-    if (nsec && (!arena || !arena_off || !name_off || !name_len || !value_off || !value_len || !fflags || !nfields ||
-                 !sstatus || !req_insert_count))
+    if (c.nsec && (!c.arena || !c.arena_off || !c.name_off || !c.name_len || !c.value_off || !c.value_len || !c.fflags ||
+                   !c.nfields || !c.sstatus || !c.req_insert_count))
         return arg_fail("NULL array");
-    if (header_table_size > (1u << 30)) return arg_fail("header_table_size above 2^30");
+    if (c.T > (1u << 30)) return arg_fail("header_table_size above 2^30");
     // u32 offsets, and the literal workspace is sized for in_size + 2 literals in 32 bits
-    if (in_size > (1ull << 32) - 3) return arg_fail("in_size must be at most 2^32 - 3 (u32 offsets)");
-    if (!slots && scratch_size < hhuff_qpack_scratch_size(nconn, header_table_size))
+    if (c.in_size > (1ull << 32) - 3) return arg_fail("in_size must be at most 2^32 - 3 (u32 offsets)");
+    if (!slots && scratch_size < hhuff_qpack_scratch_size(c.nconn, c.T))
         return arg_fail("scratch smaller than hhuff_qpack_scratch_size");
-    if (((uintptr_t)scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
+    if (((uintptr_t)c.scratch & 15u) != 0) return arg_fail("scratch must be 16-byte aligned");
     ConnMap map((hipStream_t)stream);
-    hipError_t e = map.make(slots, nconn);
+    hipError_t e = map.make(slots, c.nconn);
     if (e != hipSuccess) return hip_fail(e, "connection slots");
-    e = hhuff::launch_qpack(in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                            num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                            req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
-                            (hipStream_t)stream, stream_id, req, res, map.cmap, sessions ? ds : nullptr);
+    c.cmap = map.cmap;
+    e = hhuff::launch_qpack(c, ds, (hipStream_t)stream);
     return e == hipSuccess ? HHUFF_OK : hip_fail(e, "qpack launch");
 }
 }  // namespace
@@ -602,10 +591,11 @@ HHUFF_API int hhuff_qpack_parse_requests_sessions(
     void* stream) {
     if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
     if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
-    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                      nullptr, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, nullptr, scratch,
-                      scratch_size, flags, stream, true, ds);
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, nullptr, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        stream_id, req, nullptr, nullptr};
+    return qpack_step(slots, call, true, ds, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_responses_sessions(
@@ -618,25 +608,27 @@ HHUFF_API int hhuff_qpack_parse_responses_sessions(
     void* stream) {
     if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
     if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
-    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                      nullptr, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, nullptr, res, scratch,
-                      scratch_size, flags, stream, true, ds);
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, nullptr, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        stream_id, nullptr, res, nullptr};
+    return qpack_step(slots, call, true, ds, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_decode_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                                       const uint32_t* enc_off, const uint32_t* enc_len,
-                                 const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
-                                 uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked,
-                                 uint8_t* arena, const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
-                                 uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
-                                 int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status,
-                                 uint32_t* enc_consumed, uint64_t* insert_count, void* scratch, uint64_t scratch_size,
-                                 unsigned flags, void* stream) {
-    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                      num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, nullptr, nullptr, nullptr, scratch,
-                      scratch_size, flags, stream);
+                                       const uint32_t* enc_off, const uint32_t* enc_len, const uint32_t* sec_off,
+                                       const uint32_t* conn_first, uint32_t nconn, uint32_t nsec, uint32_t header_table_size,
+                                       uint64_t max_blocked, const uint32_t* num_blocked, uint8_t* arena,
+                                       const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len,
+                                       uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
+                                       int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status,
+                                       uint32_t* enc_consumed, uint64_t* insert_count, void* scratch, uint64_t scratch_size,
+                                       unsigned flags, void* stream) {
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        nullptr, nullptr, nullptr, nullptr};
+    return qpack_step(slots, call, false, nullptr, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_decode(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, const uint32_t* enc_len,
@@ -647,28 +639,30 @@ HHUFF_API int hhuff_qpack_decode(const uint8_t* in, uint64_t in_size, const uint
                                  int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status,
                                  uint32_t* enc_consumed, uint64_t* insert_count, void* scratch, uint64_t scratch_size,
                                  unsigned flags, void* stream) {
-    return hhuff_qpack_decode_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
-        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len,
-        fflags, nfields, sstatus, req_insert_count, enc_status, enc_consumed, insert_count, scratch, scratch_size,
-        flags, stream);
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        nullptr, nullptr, nullptr, nullptr};
+    return qpack_step(nullptr, call, false, nullptr, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_requests_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                                               const uint32_t* enc_off,
-                                         const uint32_t* enc_len, const uint32_t* sec_off, const uint32_t* conn_first,
-                                         uint32_t nconn, uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked,
-                                         const uint32_t* num_blocked, uint8_t* arena, const uint64_t* arena_off,
-                                         uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
-                                         uint8_t* fflags, uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
-                                         int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
-                                         const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch,
-                                         uint64_t scratch_size, unsigned flags, void* stream) {
+                                               const uint32_t* enc_off, const uint32_t* enc_len, const uint32_t* sec_off,
+                                               const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
+                                               uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked,
+                                               uint8_t* arena, const uint64_t* arena_off, uint32_t* name_off,
+                                               uint32_t* name_len, uint32_t* value_off, uint32_t* value_len, uint8_t* fflags,
+                                               uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
+                                               int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
+                                               const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch,
+                                               uint64_t scratch_size, unsigned flags, void* stream) {
     if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
     if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
-    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                      num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, nullptr, scratch,
-                      scratch_size, flags, stream);
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        stream_id, req, nullptr, nullptr};
+    return qpack_step(slots, call, false, nullptr, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_requests(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off,
@@ -680,28 +674,33 @@ HHUFF_API int hhuff_qpack_parse_requests(const uint8_t* in, uint64_t in_size, co
                                          int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                                          const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch,
                                          uint64_t scratch_size, unsigned flags, void* stream) {
-    return hhuff_qpack_parse_requests_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
-        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len,
-        fflags, nfields, sstatus, req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, scratch,
-        scratch_size, flags, stream);
+    if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
+    if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        stream_id, req, nullptr, nullptr};
+    return qpack_step(nullptr, call, false, nullptr, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
-                                                const uint32_t* enc_off,
-                                          const uint32_t* enc_len, const uint32_t* sec_off, const uint32_t* conn_first,
-                                          uint32_t nconn, uint32_t nsec, uint32_t header_table_size, uint64_t max_blocked,
-                                          const uint32_t* num_blocked, uint8_t* arena, const uint64_t* arena_off,
-                                          uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
-                                          uint8_t* fflags, uint32_t* nfields, int32_t* sstatus, uint64_t* req_insert_count,
-                                          int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
-                                          const uint64_t* stream_id, hhuff_qpack_response_head_t* res, void* scratch,
-                                          uint64_t scratch_size, unsigned flags, void* stream) {
+                                                const uint32_t* enc_off, const uint32_t* enc_len, const uint32_t* sec_off,
+                                                const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
+                                                uint32_t header_table_size, uint64_t max_blocked,
+                                                const uint32_t* num_blocked, uint8_t* arena, const uint64_t* arena_off,
+                                                uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
+                                                uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus,
+                                                uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed,
+                                                uint64_t* insert_count, const uint64_t* stream_id,
+                                                hhuff_qpack_response_head_t* res, void* scratch, uint64_t scratch_size,
+                                                unsigned flags, void* stream) {
     if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
     if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
-    return qpack_step(slots, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size, max_blocked,
-                      num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                      req_insert_count, enc_status, enc_consumed, insert_count, stream_id, nullptr, res, scratch,
-                      scratch_size, flags, stream);
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        stream_id, nullptr, res, nullptr};
+    return qpack_step(slots, call, false, nullptr, scratch_size, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_responses(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off,
@@ -713,10 +712,13 @@ HHUFF_API int hhuff_qpack_parse_responses(const uint8_t* in, uint64_t in_size, c
                                           int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                                           const uint64_t* stream_id, hhuff_qpack_response_head_t* res, void* scratch,
                                           uint64_t scratch_size, unsigned flags, void* stream) {
-    return hhuff_qpack_parse_responses_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
-        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len,
-        fflags, nfields, sstatus, req_insert_count, enc_status, enc_consumed, insert_count, stream_id, res, scratch,
-        scratch_size, flags, stream);
+    if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
+    if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
+    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
+                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
+                        stream_id, nullptr, res, nullptr};
+    return qpack_step(nullptr, call, false, nullptr, scratch_size, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "hhuff.h"
+#include "hhuff_carve.h"  // Carve: how every launcher cuts up its workspace
 
 namespace hhuff {
 hipError_t launch_decode(const uint8_t* in, uint64_t in_size, const uint32_t* in_off, const uint32_t* in_len, uint32_t n,
@@ -82,8 +83,8 @@ uint64_t literals_dev_ws(uint32_t n_max, uint64_t in_size);
 // The literal list of marked input bytes (hhuff_blocks.hip): bit p of lit_bits marks a literal at byte p.
 // Writes word_pre (marks before each bitmap word), list (positions in order), lnames (bit r set when the
 // literal's name_bits bit is), prefix_of[r] (when given) = pfx_alt if its pfx_bits bit is set, else pfx_name for
-// a name, else 7, and *n_lit = chunk[nchunks]; chunk: u32[literal_list_chunks(nwords) + 1] of workspace.
-uint64_t literal_list_chunks(uint64_t nwords);
+// a name, else 7, and *n_lit = chunk[nchunks]; chunk: u32[literal_list_chunks(nwords) + 1] of workspace
+// (hhuff_decwork.h, which lays these pieces out for both decoders).
 hipError_t launch_literal_list(const uint32_t* lit_bits, const uint32_t* name_bits, const uint32_t* pfx_bits, uint32_t pfx_alt,
                                uint32_t pfx_name, uint64_t nwords, uint32_t* chunk, uint32_t* word_pre, uint32_t* list, uint32_t* lnames,
                                uint8_t* prefix_of, hipStream_t stream);
@@ -91,20 +92,6 @@ hipError_t launch_literal_list(const uint32_t* lit_bits, const uint32_t* name_bi
 hipError_t work_alloc(void** p, uint64_t bytes, hipStream_t stream);
 // hand the pool's kept memory on the current device back to the driver (hhuff_pool_trim)
 hipError_t pool_trim();
-
-// A buffer cut into 16-byte aligned pieces by one sequence of take<T>(count) calls.  Run on a null base the
-// sequence yields the size in `off` (the pointers mean nothing), run again on the allocation it yields the
-// pointers: no size is written twice.
-struct Carve {
-    uint8_t* base;
-    uint64_t off = 0;
-    template <class T>
-    T* take(uint64_t count) {
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += (count * sizeof(T) + 15u) & ~15ull;
-        return p;
-    }
-};
 
 // HTTP/2 response header blocks, encode side (hhuff_hpenc.hip): include/hhuff.h hhuff_hpack_flatten_responses,
 // its arguments in its order; scratch = nconn x hpenc_conn_scratch() bytes
@@ -180,27 +167,67 @@ struct QseCall {
 uint64_t qpenc_conn_scratch(uint32_t header_table_size, uint32_t max_inflight);
 hipError_t launch_qpack_sessions(const QseCall& call, hipStream_t stream);
 
-// HPACK header blocks (f4): see include/hhuff.h hhuff_hpack_decode_blocks; scratch = nconn x
-// hpack_conn_scratch(table_size) bytes of device memory (with cmap: one slab per slot)
+// HPACK header blocks, decode side (f4, hhuff_blocks.hip): the arguments of include/hhuff.h
+// hhuff_hpack_parse_requests and _responses (hhuff_hpack_decode_blocks: neither req nor res); scratch = nconn x
+// hpack_conn_scratch(table_size) bytes of device memory (with cmap: one slab per slot).  The kernels get this
+// struct as the front of their argument block, so its members stand in the order that block always had --
+// scratch and flags ahead of req, res and trailers -- and not in the public one: the order moves the kernels'
+// register allocation (profiles/dec_refactor_resources.txt).
+struct HpdCall {
+    const uint8_t* in;
+    uint64_t in_size;
+    const uint32_t* blk_off;
+    const uint32_t* conn_first;
+    uint32_t nconn, table_size;
+    uint8_t* arena;
+    const uint64_t* arena_off;
+    uint32_t *name_off, *name_len, *value_off, *value_len;
+    uint8_t* fflags;
+    uint32_t* nfields;
+    int32_t* bstatus;
+    uint8_t* scratch;
+    uint32_t flags;           // HHUFF_BLK_CONTINUE: start from the tables the previous call left in scratch
+    hhuff_request_t* req;     // request mode (hhuff_hpack_parse_requests): h2o_hpack_parse_request per block
+    hhuff_response_t* res;    // response mode (hhuff_hpack_parse_responses): h2o_hpack_parse_response per block
+    const uint8_t* trailers;  // response mode: per block, nonzero = trailers (status == NULL); NULL = none
+    const uint32_t* cmap;     // connection slots (hhuff_slots.h); NULL: connection c in slot c
+};
 uint64_t hpack_conn_scratch(uint32_t table_size);
-hipError_t launch_hpack_blocks(const uint8_t* in, uint64_t in_size, const uint32_t* blk_off, const uint32_t* conn_first,
-                               uint32_t nconn, uint32_t table_size, uint8_t* arena, const uint64_t* arena_off,
-                               uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
-                               uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_request_t* req,
-                               hhuff_response_t* res, const uint8_t* trailers, uint8_t* scratch, uint32_t flags,
-                               hipStream_t stream, const uint32_t* cmap = nullptr);
-// QPACK decoder (f4): see include/hhuff.h hhuff_qpack_decode; scratch = nconn x
-// qpack_conn_scratch(header_table_size) bytes of device memory
+hipError_t launch_hpack_blocks(const HpdCall& call, hipStream_t stream);
+
+// QPACK decoder (f4, hhuff_qpack.hip): the arguments of include/hhuff.h hhuff_qpack_parse_requests and
+// _responses (hhuff_qpack_decode: none of stream_id, qreq, qres); scratch = nconn x qpack_conn_scratch(T) bytes
+// of device memory.  T, qreq and qres are spelled the way the kernels spell them, and the members stand in the
+// order the kernels' argument block always had (num_blocked with the offsets, scratch and flags ahead of
+// stream_id), as in HpdCall.
+struct QpdCall {
+    const uint8_t* in;
+    uint64_t in_size;
+    const uint32_t *enc_off, *enc_len, *sec_off, *conn_first, *num_blocked;
+    uint32_t nconn, nsec, T;  // T = header_table_size
+    uint64_t max_blocked;
+    uint8_t* arena;
+    const uint64_t* arena_off;
+    uint32_t *name_off, *name_len, *value_off, *value_len;
+    uint8_t* fflags;
+    uint32_t* nfields;
+    int32_t* sstatus;
+    uint64_t* req_insert_count;
+    int32_t* enc_status;
+    uint32_t* enc_consumed;
+    uint64_t* insert_count;
+    uint8_t* scratch;
+    uint32_t flags;
+    // h2o_qpack_parse_request mode (hhuff_qpack_parse_requests): per section its stream id and record
+    const uint64_t* stream_id;
+    hhuff_qpack_request_t* qreq;
+    // h2o_qpack_parse_response mode (hhuff_qpack_parse_responses): per section its record (and stream_id)
+    hhuff_qpack_response_head_t* qres;
+    const uint32_t* cmap;  // connection slots (hhuff_slots.h); NULL: connection c in slot c
+};
 uint64_t qpack_conn_scratch(uint32_t header_table_size);
-hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, const uint32_t* enc_len,
-                        const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
-                        uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked, uint8_t* arena,
-                        const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
-                        uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus,
-                        uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
-                        uint8_t* scratch, uint32_t flags, hipStream_t stream, const uint64_t* stream_id = nullptr,
-                        hhuff_qpack_request_t* qreq = nullptr, hhuff_qpack_response_head_t* qres = nullptr,
-                        const uint32_t* cmap = nullptr, const hhuff_qpack_dsessions_t* ds = nullptr);
+// ds: the call's decoder sessions (include/hhuff.h (2e''')); NULL: a step without them
+hipError_t launch_qpack(const QpdCall& call, const hhuff_qpack_dsessions_t* ds, hipStream_t stream);
 // bytes of one decoder session (include/hhuff.h (2e''')) with a list of max_blocked entries
 uint64_t qpack_dsession_slab(uint32_t max_blocked);
 // Connection images (include/hhuff.h (2i), hhuff_image.hip): one wave per item; fam's parameters checked by the

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "hhuff_decwork.h"
 #include "hhuff_device.h"
 #include "hhuff_image.h"
 #include "hhuff.h"
@@ -58,25 +59,8 @@ constexpr int64_t kQuicIntMax = 4611686018427387903LL;  // PTLS_QUICINT_MAX
 constexpr int64_t kIntIncomplete = -255, kIntBad = -9;
 }  // namespace
 
-struct QpkArgs {
-    const uint8_t* in;
-    uint64_t in_size;
-    const uint32_t *enc_off, *enc_len, *sec_off, *conn_first, *num_blocked;
-    uint32_t nconn, nsec, T;  // T = header_table_size
-    uint64_t max_blocked;
-    uint8_t* arena;
-    const uint64_t* arena_off;
-    uint32_t *name_off, *name_len, *value_off, *value_len;
-    uint8_t* fflags;
-    uint32_t* nfields;
-    int32_t* sstatus;
-    uint64_t* req_insert_count;
-    int32_t* enc_status;
-    uint32_t* enc_consumed;
-    uint64_t* insert_count;
-    uint8_t* scratch;
-    uint64_t conn_scratch;
-    uint32_t flags;
+struct QpkArgs : QpdCall {  // the call, and what launch_qpack adds to it
+    uint64_t conn_scratch;  // bytes of scratch per connection
     // pre-decoded encoder-stream literals (launch_qpack's pre-pass): bit p of lit_bits marks a literal whose
     // header starts at input byte p; word_pre[w] counts the marks before word w; literal r has the literal
     // kernels' results lit_len / lit_st, its bytes at lit_out + floor(8 payload / 5) (Huffman) or in the
@@ -91,12 +75,6 @@ struct QpkArgs {
     // bytes (0: already in the arena); qpack_copy_kernel moves them.  NULL: the sections kernel copies.
     uint64_t* fsrc_n;
     uint64_t* fsrc_v;
-    // h2o_qpack_parse_request mode (hhuff_qpack_parse_requests): per section its stream id and record
-    const uint64_t* stream_id;
-    hhuff_qpack_request_t* qreq;
-    // h2o_qpack_parse_response mode (hhuff_qpack_parse_responses): per section its record (and stream_id)
-    hhuff_qpack_response_head_t* qres;
-    const uint32_t* cmap;  // connection slots (hhuff_slots.h); NULL: connection c in slot c
 };
 
 // Byte sources of table entries and field strings: kind in the top 3 bits, offset below.  Every source stays
@@ -1111,72 +1089,40 @@ uint64_t qpack_conn_scratch(uint32_t header_table_size) {
 
 uint64_t qpack_dsession_slab(uint32_t max_blocked) { return qp_slab_bytes(max_blocked); }
 
-hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc_off, const uint32_t* enc_len,
-                        const uint32_t* sec_off, const uint32_t* conn_first, uint32_t nconn, uint32_t nsec,
-                        uint32_t header_table_size, uint64_t max_blocked, const uint32_t* num_blocked, uint8_t* arena,
-                        const uint64_t* arena_off, uint32_t* name_off, uint32_t* name_len, uint32_t* value_off,
-                        uint32_t* value_len, uint8_t* fflags, uint32_t* nfields, int32_t* sstatus,
-                        uint64_t* req_insert_count, int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
-                        uint8_t* scratch, uint32_t flags, hipStream_t stream, const uint64_t* stream_id,
-                        hhuff_qpack_request_t* qreq, hhuff_qpack_response_head_t* qres, const uint32_t* cmap,
-                        const hhuff_qpack_dsessions_t* ds) {
+hipError_t launch_qpack(const QpdCall& call, const hhuff_qpack_dsessions_t* ds, hipStream_t stream) {
+    const uint32_t nconn = call.nconn, nsec = call.nsec;
+    const uint64_t in_size = call.in_size, max_blocked = call.max_blocked;
+    const uint32_t* cmap = call.cmap;
+    hhuff_qpack_request_t* qreq = call.qreq;
+    hhuff_qpack_response_head_t* qres = call.qres;
     if (nconn == 0) return hipSuccess;
-    QpkArgs A{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
-              max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-              req_insert_count, enc_status, enc_consumed, insert_count, scratch, qpack_conn_scratch(header_table_size),
-              flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream_id, qreq, qres, cmap};
-    // workspace: the literal pre-pass's bitmaps, word prefixes, chunk sums, the literal list with each
-    // literal's prefix, the literal kernels' results and decoded bytes (positions are u32: in_size < 2^32,
-    // checked by the C ABI), and the field slots' byte sources
-    const uint64_t nwords = in_size / 32 + 1, nchunks = literal_list_chunks(nwords);
-    const uint64_t n_max = in_size + 2;  // every literal header takes a byte
-    auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
-    const uint64_t o_lit = 0, o_name = o_lit + up(4 * nwords), o_p3 = o_name + up(4 * nwords);
-    const uint64_t o_lnames = o_p3 + up(4 * nwords);
-    const uint64_t zero_end = o_lnames + up(4 * ((n_max + 31) / 32));  // [0, zero_end) starts zeroed
-    const uint64_t o_pre = zero_end, o_chunk = o_pre + up(4 * nwords), o_list = o_chunk + up(4 * nchunks + 4);
-    const uint64_t o_pfx = o_list + up(4 * n_max), o_len = o_pfx + up(n_max), o_pay = o_len + up(4 * n_max);
-    const uint64_t o_cons = o_pay + up(4 * n_max), o_st = o_cons + up(4 * n_max), o_ws = o_st + up(n_max);
-    const uint64_t o_out = o_ws + up(literals_dev_ws((uint32_t)n_max, in_size));
-    const uint64_t o_fsn = o_out + up((8 * in_size) / 5 + 64), o_fsv = o_fsn + up(8 * in_size + 8);
-    const uint64_t o_map = o_fsv + up(8 * in_size + 8);  // field slots: one per input byte
-    // a session step without a slot map makes its connection map here (the encoder-stream pass fills it)
-    const uint64_t wbytes = o_map + (ds && !cmap ? up(4 * (uint64_t)nconn) : 0u);
+    // workspace (hhuff_decwork.h): the literal pre-pass's bitmaps, word prefixes, chunk sums, the literal list
+    // with each literal's prefix, the literal kernels' results and decoded bytes (positions are u32: in_size <
+    // 2^32, checked by the C ABI), the field slots' byte sources, and for a session step without a slot map
+    // its connection map (the encoder-stream pass fills it)
+    const LitDims d = qpd_dims(in_size);
+    const uint64_t lit_ws = literals_dev_ws((uint32_t)d.n_max, in_size), map_conns = ds && !cmap ? nconn : 0u;
+    QpdWork W;
     uint8_t* work = nullptr;
-    hipError_t e = hipSuccess;
-    {
-        e = work_alloc((void**)&work, wbytes, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(work, 0, zero_end, stream);
-        uint32_t* lit_bits = reinterpret_cast<uint32_t*>(work + o_lit);
-        uint32_t* name_bits = reinterpret_cast<uint32_t*>(work + o_name);
-        uint32_t* chunk = reinterpret_cast<uint32_t*>(work + o_chunk);
-        uint32_t* list = reinterpret_cast<uint32_t*>(work + o_list);
-        uint32_t* word_pre = reinterpret_cast<uint32_t*>(work + o_pre);
-        uint32_t* p3_bits = reinterpret_cast<uint32_t*>(work + o_p3);
-        if (e == hipSuccess) {
-            const uint64_t items = (uint64_t)nconn + nsec;
-            hipLaunchKernelGGL(qpack_mark_kernel, dim3((uint32_t)std::min<uint64_t>((items + 255) / 256, 65535)), dim3(256),
-                               0, stream, A, QMarks{lit_bits, name_bits, p3_bits});
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess)  // prefixes: section names 3, encoder-stream names 5, values 7
-            e = launch_literal_list(lit_bits, name_bits, p3_bits, 3u, 5u, nwords, chunk, word_pre, list,
-                                    reinterpret_cast<uint32_t*>(work + o_lnames), work + o_pfx, stream);
-        if (e == hipSuccess)
-            e = launch_literals_dev(in, in_size, list, (uint32_t)n_max, chunk + nchunks, 7u,
-                                    HHUFF_LIT_QPACK | kLitNoRawCopy, reinterpret_cast<uint32_t*>(work + o_lnames),
-                                    work + o_out, reinterpret_cast<uint32_t*>(work + o_len),
-                                    reinterpret_cast<uint32_t*>(work + o_pay), reinterpret_cast<uint32_t*>(work + o_cons),
-                                    work + o_st, work + o_ws, stream, work + o_pfx);
-        A.lit_bits = lit_bits;
-        A.word_pre = word_pre;
-        A.lit_len = reinterpret_cast<const uint32_t*>(work + o_len);
-        A.lit_st = work + o_st;
-        A.lit_pfx = work + o_pfx;
-        A.lit_out = work + o_out;
-        A.fsrc_n = reinterpret_cast<uint64_t*>(work + o_fsn);
-        A.fsrc_v = reinterpret_cast<uint64_t*>(work + o_fsv);
+    hipError_t e = work_alloc((void**)&work, qpd_carve(W, in_size, lit_ws, map_conns, nullptr), stream);
+    if (e != hipSuccess) return e;
+    qpd_carve(W, in_size, lit_ws, map_conns, work);
+    const LitWork& L = W.lit;
+    QpkArgs A{call, qpack_conn_scratch(call.T), L.lit_bits, L.word_pre, L.len, L.st, L.pfx, L.out, W.fsrc_n, W.fsrc_v};
+    e = hipMemsetAsync(work, 0, W.zero_end, stream);
+    if (e == hipSuccess) {
+        const uint64_t items = (uint64_t)nconn + nsec;
+        hipLaunchKernelGGL(qpack_mark_kernel, dim3((uint32_t)std::min<uint64_t>((items + 255) / 256, 65535)), dim3(256), 0,
+                           stream, A, QMarks{L.lit_bits, L.name_bits, L.p3_bits});
+        e = hipGetLastError();
     }
+    if (e == hipSuccess)  // prefixes: section names 3, encoder-stream names 5, values 7
+        e = launch_literal_list(L.lit_bits, L.name_bits, L.p3_bits, 3u, 5u, d.nwords, L.chunk, L.word_pre, L.list, L.lnames,
+                                L.pfx, stream);
+    if (e == hipSuccess)
+        e = launch_literals_dev(A.in, in_size, L.list, (uint32_t)d.n_max, L.chunk + d.nchunks, 7u,
+                                HHUFF_LIT_QPACK | kLitNoRawCopy, L.lnames, L.out, L.len, L.pay, L.cons, L.st, L.ws, stream,
+                                L.pfx);
     auto step = [&](auto slots) {  // the kernels' instantiation with or without connection slots
         constexpr bool S = decltype(slots)::value;
         hipLaunchKernelGGL(qpack_encoder_kernel<S>, dim3(std::min((nconn + 255u) / 256u, 65535u)), dim3(256), 0, stream, A);
@@ -1198,7 +1144,7 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
         QdsArgs D{static_cast<uint8_t*>(ds->state), qp_slab_bytes((uint32_t)max_blocked), (uint32_t)max_blocked, ds->flags,
                   ds->cancel_first, ds->cancel_id, ds->cancel_flags, ds->dec_out, ds->dec_out_off, ds->dec_out_len,
                   ds->wake_id, ds->wake_first, ds->nwake, ds->parked, ds->dflags,
-                  cmap ? const_cast<uint32_t*>(cmap) : reinterpret_cast<uint32_t*>(work + o_map), cmap};
+                  cmap ? const_cast<uint32_t*>(cmap) : W.map, cmap};
         A.cmap = D.map;
         const dim3 gc(std::min((nconn + 255u) / 256u, 65535u));
         hipLaunchKernelGGL(qpack_encoder_ds_kernel, gc, dim3(256), 0, stream, A, D);
@@ -1217,11 +1163,8 @@ hipError_t launch_qpack(const uint8_t* in, uint64_t in_size, const uint32_t* enc
         return hipGetLastError();
     };
     if (e == hipSuccess) e = ds ? session_step() : cmap ? step(std::true_type{}) : step(std::false_type{});
-    if (work) {
-        const hipError_t f = hipFreeAsync(work, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
+    const hipError_t f = hipFreeAsync(work, stream);
+    return e != hipSuccess ? e : f;
 }
 
 }  // namespace hhuff
