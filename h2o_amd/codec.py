@@ -203,6 +203,19 @@ def lib():
                                                _vp, ctypes.c_uint64, _vp, _vp, _vp]
         L.hhuff_shard_bounds.restype = ctypes.c_int
         L.hhuff_shard_bounds.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp]
+        L.hhuff_tokens_table_size.restype = ctypes.c_uint64
+        L.hhuff_tokens_table_size.argtypes = [ctypes.c_uint32, ctypes.c_uint64]
+        L.hhuff_tokens_build.restype = ctypes.c_int
+        L.hhuff_tokens_build.argtypes = [_vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64]
+        L.hhuff_intern_strings.restype = ctypes.c_int
+        L.hhuff_intern_strings.argtypes = [_vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, _vp,
+                                           ctypes.c_uint32, _vp]
+        L.hhuff_intern_fields.restype = ctypes.c_int
+        L.hhuff_intern_fields.argtypes = [_vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, ctypes.c_uint32,
+                                          ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]
+        L.hhuff_intern_headers.restype = ctypes.c_int
+        L.hhuff_intern_headers.argtypes = [_vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
+                                           ctypes.c_uint32, _vp, _vp]
         _lib = L
     return _lib
 
@@ -224,7 +237,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_debug_encode_blocks_per_cu", "hhuff_qpack_parse_requests_sessions",
             "hhuff_qpack_parse_responses_sessions", "hhuff_qpack_dsession_state_size",
             "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
-            "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers") + SLOTS_SYMBOLS
+            "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers", "hhuff_tokens_table_size", "hhuff_tokens_build",
+            "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -348,6 +362,96 @@ def conn_import(fam, scratch, nslots, slot, img, img_off, img_len, stream=None):
                                    _dp(slot), n, _dp(img), _dp(img_off), _dp(img_len), _dp(status), _stream(stream)),
            "hhuff_conn_import")
     return status[:n]
+
+
+# include/hhuff.h (2j): token interning
+TOK_NONE, TOK_EFORMAT = -1, -2
+
+
+def tokens_table_size(ntokens, name_bytes) -> int:
+    """hhuff_tokens_table_size: the bytes of a table of ntokens names of name_bytes bytes in all; 0: bad parameters"""
+    return int(lib().hhuff_tokens_table_size(int(ntokens), int(name_bytes)))
+
+
+def tokens_build(names, user=None):
+    """hhuff_tokens_build on the host (no GPU): names = a list of bytes, user = their 32-bit words (None: all 0)
+    -> the table, a numpy uint8 array of tokens_table_size bytes.  Raises HhuffError where the call refuses the list
+    (two equal names, an empty name, a name over 255 bytes, no names or more than 4096)."""
+    blob = np.frombuffer(b"".join(names), np.uint8).copy()
+    off = np.zeros(len(names) + 1, np.uint32)
+    off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+    words = None if user is None else np.ascontiguousarray(user, np.uint32)
+    assert words is None or words.size == len(names)
+    size = tokens_table_size(len(names), blob.size)
+    table = np.zeros(max(size, 16), np.uint8)
+    rc = lib().hhuff_tokens_build(blob.ctypes.data, off.ctypes.data, len(names), None if words is None else words.ctypes.data,
+                                  table.ctypes.data, size)
+    if rc != 0:
+        raise HhuffError("hhuff_tokens_build refused the list (%d)" % rc)
+    return table[:size]
+
+
+class TokenSet:
+    """A token set on the device: the caller's names (a list of bytes; the token id is the index) and one 32-bit word
+    per name, compiled by hhuff_tokens_build and uploaded.  The three calls of include/hhuff.h (2j) run on it; uint32
+    arrays are int32 device tensors (same bits), as everywhere in this module."""
+
+    def __init__(self, names, user=None, device="cuda"):
+        import torch
+
+        self.names = list(names)
+        self.host = tokens_build(self.names, user)
+        self.table = torch.from_numpy(self.host.copy()).to(device)
+        assert self.table.data_ptr() % 16 == 0
+        self.size = int(self.host.size)
+
+    def intern_strings(self, data, off, length, n=None, miss_user=0, in_size=None, token=None, user_out=None, want_user=True,
+                       stream=None):
+        """hhuff_intern_strings: string i = data[off[i] .. off[i] + length[i]) -> (token int32 [n], user_out int32 [n] or
+        None)"""
+        import torch
+
+        n = off.numel() if n is None else int(n)
+        if token is None:
+            token = torch.empty(max(1, n), dtype=torch.int32, device=data.device)
+        if user_out is None and want_user:
+            user_out = torch.empty(max(1, n), dtype=torch.int32, device=data.device)
+        _check(lib().hhuff_intern_strings(_dp(self.table), self.size, _dp(data), data.numel() if in_size is None else in_size,
+                                          _dp(off), _dp(length), n, _dp(token), _dp(user_out), int(miss_user) & 0xFFFFFFFF,
+                                          _stream(stream)), "hhuff_intern_strings")
+        return token[:n], None if user_out is None else user_out[:n]
+
+    def intern_fields(self, arena, name_off, name_len, first, nfields, nslots, miss_user=0, arena_size=None, token=None,
+                      user_out=None, want_user=True, stream=None):
+        """hhuff_intern_fields behind a block or section decoder: first = its blk_off / sec_off ([nblk + 1]), nslots the
+        host copy of first[nblk].  Slots that are no block's field keep what token / user_out held (new arrays: -1 /
+        miss_user) -> (token int32 [nslots], user_out or None)"""
+        import torch
+
+        nblk, nslots = nfields.numel(), int(nslots)
+        if token is None:
+            token = torch.full((max(1, nslots),), TOK_NONE, dtype=torch.int32, device=arena.device)
+        if user_out is None and want_user:
+            user_out = torch.full((max(1, nslots),), int(np.uint32(miss_user & 0xFFFFFFFF).view(np.int32)), dtype=torch.int32,
+                                  device=arena.device)
+        _check(lib().hhuff_intern_fields(_dp(self.table), self.size, _dp(arena), arena.numel() if arena_size is None else arena_size,
+                                         _dp(name_off), _dp(name_len), _dp(first), _dp(nfields), nblk, nslots, _dp(token),
+                                         _dp(user_out), int(miss_user) & 0xFFFFFFFF, _stream(stream)), "hhuff_intern_fields")
+        return token[:nslots], None if user_out is None else user_out[:nslots]
+
+    def intern_headers(self, data, hdr, keep_mask=None, in_size=None, want_token=True, stream=None):
+        """hhuff_intern_headers before an encoder: hdr = the device bytes of HPE_HEADER_DTYPE records, as the flatten
+        calls take them; every record's flags become (flags & keep_mask) | (the name's word, or 0) in place
+        (keep_mask None: HDR_DONT_COMPRESS) -> token int32 [nhdr] or None"""
+        import torch
+
+        keep_mask = HDR_DONT_COMPRESS if keep_mask is None else keep_mask
+        nhdr = hdr.numel() * hdr.element_size() // HPE_HEADER_DTYPE.itemsize
+        token = torch.empty(max(1, nhdr), dtype=torch.int32, device=data.device) if want_token else None
+        _check(lib().hhuff_intern_headers(_dp(self.table), self.size, _dp(data), data.numel() if in_size is None else in_size,
+                                          _dp(hdr), nhdr, int(keep_mask) & 0xFFFFFFFF, _dp(token), _stream(stream)),
+               "hhuff_intern_headers")
+        return None if token is None else token[:nhdr]
 
 
 def decode_slot_size(in_size: int) -> int:

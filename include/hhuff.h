@@ -1039,6 +1039,65 @@ int hhuff_conn_import(const hhuff_conn_family_t *fam, void *scratch, uint64_t sc
                       const uint32_t *slot, uint32_t n, const uint8_t *img, const uint64_t *img_off,
                       const uint32_t *img_len, int32_t *status, void *stream);
 
+/* (2j) Token interning: name -> token id.  Every h2o function restated above hands its caller tokens, not byte
+ *      strings: h2o_hpack_decode_header and QPACK's decode_header intern a literal name through h2o_lookup_token
+ *      (lib/http2/hpack.c:398-400, lib/http3/qpack.c:585), and the encoders start from h2o_iovec_is_token(name)
+ *      and the token's flags (hpack.c:861-862, qpack.c:1219-1224).  A token set is the caller's list of names, each
+ *      with one caller-defined 32-bit word; the token id is the index in that list (h2o passes its h2o__tokens[]:
+ *      the id is what `h2o__tokens + id` is to h2o).  The library embeds no list.  The comparison is bytewise and
+ *      case-sensitive, as h2o_lookup_token's memcmp is.
+ *      1. hhuff_tokens_build compiles the list on the host into a table: host memory in, host memory out, no HIP
+ *         call (it works on a machine without a GPU).  names = the names back to back, name i =
+ *         names[name_off[i] .. name_off[i + 1]); user[i] = token i's word (NULL: all 0).  1 <= ntokens <= 4096, every
+ *         name 1..255 bytes of any value.  HHUFF_EINVAL, with `table` untouched, for two equal names, an empty name,
+ *         a name over 255 bytes, a decreasing name_off, ntokens out of range, a NULL array, or a table_size below
+ *         hhuff_tokens_table_size(ntokens, name_bytes), name_bytes = name_off[ntokens] - name_off[0] (the function
+ *         is 0 for ntokens out of range or name_bytes outside [ntokens, 255 ntokens]).  The table is exactly
+ *         hhuff_tokens_table_size bytes long -- a multiple of 16; that number is the table_size of the calls below --
+ *         and deterministic: equal arguments give equal bytes.
+ *      2. The table holds no address.  The caller copies it to 16-byte-aligned device memory and may copy it again
+ *         anywhere.  It begins with a header -- magic "HHTK", u16 version = 1, u16 0, u32 ntokens, u32 size -- and is
+ *         a hash table with open addressing whose probe bound was found at build time: a lookup is
+ *         that bounded number of bucket reads and a full comparison of the name whose 16 tag bits match.
+ *      3. hhuff_intern_strings: for i < n, token[i] = the id of the name equal to in[off[i] .. off[i] + len[i]), or
+ *         HHUFF_TOK_NONE -- also for length 0, length over 255 and a range that passes in_size.  user_out[i] (may be
+ *         NULL) = that token's word, or miss_user.
+ *      4. hhuff_intern_fields: the same on the output of the block and section decoders of (2c) .. (2e'''): arena,
+ *         name_off, name_len as they wrote them, first = the call's blk_off / sec_off (nblk + 1 entries), nslots =
+ *         the host copy of first[nblk].  Block b's fields are the slots first[b] .. first[b] + min(nfields[b],
+ *         first[b + 1] - first[b]) - 1; every other slot of token / user_out is left untouched, as the decoders leave
+ *         those slots of name_off unwritten.
+ *      5. hhuff_intern_headers: the encoder side of (2f) .. (2g'').  For each header h,
+ *         hdr[h].flags = (hdr[h].flags & keep_mask) | (hit ? word : 0), and no other byte of hdr[h] is written;
+ *         token[h] (may be NULL) as in point 3.  With the words HHUFF_HDR_TOKEN | HHUFF_HDR_LIKELY_TO_REPEAT as each
+ *         token's flags say and keep_mask = HHUFF_HDR_DONT_COMPRESS the call supplies what (2f) and (2g') ask the
+ *         caller for.  A name out of range is a miss; the encoder reports the range itself.
+ *      6. The three device calls are asynchronous on `stream`, one launch each, without pool workspace.  They return
+ *         HHUFF_EINVAL and enqueue nothing for a NULL required array, a table_size under the header's 32 bytes or a
+ *         table that is not 16-byte aligned; n / nblk / nhdr (or nslots) of 0 returns HHUFF_OK and enqueues nothing.
+ *         (The five functions of this section leave hhuff_last_error_string() as it was.)
+ *         They read only bytes of in / arena inside the given size, but for the aligned dwords (by address) that
+ *         hold a name's bytes, which are read whole.
+ *      7. The table in device memory is untrusted bytes, as an image is to hhuff_conn_import.  A header whose magic,
+ *         version, reserved words, counts or recorded size disagree with table_size makes every token output of the
+ *         call HHUFF_TOK_EFORMAT and leaves user_out and the headers' flags untouched.  Whatever the other bytes
+ *         hold, no load leaves [table, table + table_size) and no store leaves the outputs: a damaged table can only
+ *         give wrong ids. */
+#define HHUFF_TOK_NONE    (-1) /* the bytes are no token's name */
+#define HHUFF_TOK_EFORMAT (-2) /* the table is not one hhuff_tokens_build wrote (every output of the call) */
+uint64_t hhuff_tokens_table_size(uint32_t ntokens, uint64_t name_bytes); /* 0: bad parameters */
+int hhuff_tokens_build(const uint8_t *names, const uint32_t *name_off, uint32_t ntokens, const uint32_t *user,
+                       void *table, uint64_t table_size);
+int hhuff_intern_strings(const void *table, uint64_t table_size, const uint8_t *in, uint64_t in_size,
+                         const uint32_t *off, const uint32_t *len, uint32_t n, int32_t *token, uint32_t *user_out,
+                         uint32_t miss_user, void *stream);
+int hhuff_intern_fields(const void *table, uint64_t table_size, const uint8_t *arena, uint64_t arena_size,
+                        const uint32_t *name_off, const uint32_t *name_len, const uint32_t *first,
+                        const uint32_t *nfields, uint32_t nblk, uint32_t nslots, int32_t *token, uint32_t *user_out,
+                        uint32_t miss_user, void *stream);
+int hhuff_intern_headers(const void *table, uint64_t table_size, const uint8_t *in, uint64_t in_size,
+                         hhuff_hpack_header_t *hdr, uint32_t nhdr, uint32_t keep_mask, int32_t *token, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
