@@ -1529,8 +1529,11 @@ struct EncArgs {
     uint32_t* pk_off;  // packed mode (encode_staged_kernel<.., true>): u32[n + 1] output places
 };
 
+// The {code, length} table into LDS, padded to N entries: those from 256 on are {0, 0}, for bytes outside a string
+template <uint32_t N = 256>
 __device__ __forceinline__ void load_enc_table(uint2* s_enc, int nthreads) {
-    for (uint32_t k = threadIdx.x; k < 256; k += nthreads) s_enc[k] = make_uint2(g_enc_code[k], g_enc_nbits[k]);
+    for (uint32_t k = threadIdx.x; k < N; k += nthreads)
+        s_enc[k] = N == 256 || k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
 }
 
 __device__ __forceinline__ void finish_encode(const EncArgs& A, uint32_t i, uint32_t len, uint32_t ol) {
@@ -1564,8 +1567,7 @@ __global__ __launch_bounds__(WAVES * 64) void encode_staged_kernel(EncArgs A) {
     // + 32 B: a packed run starts up to 15 B into the stage and its last 16-B chunk may end 15 B past it
     __shared__ __attribute__((aligned(16))) uint32_t s_in[WAVES][STAGE / 4 + 8];
     __shared__ __attribute__((aligned(16))) uint32_t s_out[WAVES][STAGE / 4 + 4];
-    for (uint32_t k = threadIdx.x; k < 512; k += WAVES * 64)
-        s_enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
+    load_enc_table<512>(s_enc, WAVES * 64);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* stage = s_in[wave];
@@ -1775,265 +1777,56 @@ __device__ __forceinline__ SortChunk sort_chunk_issue(const EncArgs& A, uint64_t
 #ifndef HHUFF_ENCO_SPT
 #define HHUFF_ENCO_SPT 1
 #endif
-template <int NS, int CH, int SPT = 1>
-__global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
+// One body serves two kernels, told apart by a compile-time policy P.  SortedWide is the kernel as described, four
+// workgroups a CU at CH = 16 KiB.  SortedTrim is the same kernel trimmed to five workgroups a CU, for batches whose
+// chunks fit a smaller stage (launch_encode: a mean string of at most HHUFF_ENCO_SMALL_MEAN bytes).  LDS: a stage of
+// at most 13,568 B, a 257-entry code table (the head and tail words are masked and look up entry 256 outside the
+// string), one packed record a string, 16-bit encoded lengths, byte ranks: 31,072 B at CH = 13,312.  Registers, 96
+// VGPRs for five waves a SIMD (a wave of each workgroup on every SIMD): the chunk's span in scalar registers, a
+// chunk's offsets kept in its LDS records only, the next span handed on through LDS, two copy-out chunks in flight,
+// and the thread index a fresh value in each phase of the loop (fresh() below).  At four workgroups a CU the trimmed
+// code is 2-4 % slower than the wide code (the phase-local index arithmetic alone costs 2 %), so the large stage
+// keeps the wide policy.  Every `if constexpr (P::kTrim)` below is one of those trims.
+struct SortedWide {
+    static constexpr bool kTrim = false;
+    static constexpr uint32_t kEnc = 512;  // code table entries; 256..511: bytes outside a string
+    using Str = uint2;                     // {offset in the span, length} of chunk string t
+    using Rank = uint16_t;
+    static constexpr int copy_batch(int nv) { return nv; }  // copy-out chunks read ahead of their stores: all of them
+};
+struct SortedTrim {
+    static constexpr bool kTrim = true;
+    static constexpr uint32_t kEnc = 257;  // 256: bytes outside a string
+    using Str = uint32_t;                  // offset in the span | length << 14 of chunk string t
+    using Rank = uint8_t;
+    static constexpr int copy_batch(int) { return 2; }  // (96 VGPRs hold two)
+};
+// (A by value, as a kernel holds it: through a reference the copy-out's predicates compiled to seven more instructions)
+template <class P, int NS, int CH, int SPT>
+__device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
     static_assert(SPT == 1 || SPT == 2, "one string a thread, or a sorted pair");
     constexpr uint32_t kSortStr = NS, NT = NS / SPT;
     constexpr int NV = (CH + 16 * NT - 1) / (16 * NT);  // 16-B span chunks per thread
-    __shared__ __attribute__((aligned(16))) uint2 s_enc[512];  // 256..511: bytes outside a string
+    constexpr int CB = P::copy_batch(NV);
+    __shared__ __attribute__((aligned(16))) uint2 s_enc[P::kEnc];
     __shared__ __attribute__((aligned(16))) uint32_t s_in[CH / 4 + 8];
     __shared__ __attribute__((aligned(16))) uint32_t s_out[CH / 4 + 8];
-    __shared__ uint2 s_str[kSortStr];  // {offset in the span, length} of chunk string t
-    __shared__ uint16_t s_perm[kSortStr];
+    __shared__ typename P::Str s_str[kSortStr];
+    // (trimmed) a string's encoded length (kSortFail: none), back to its own thread
+    __shared__ uint16_t s_olen[P::kTrim ? kSortStr : 1];
+    __shared__ typename P::Rank s_perm[kSortStr];
     __shared__ uint32_t s_bin[kSortBins];  // strings per bin, then the bins' first places
-    const uint32_t t = threadIdx.x, lane = t & 63u;
-    for (uint32_t k = t; k < 512; k += NT) s_enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
-    const uint64_t nch = ((uint64_t)A.n + kSortStr - 1) / kSortStr;
-    uint64_t c = blockIdx.x;
-    if (c >= nch) return;
-    auto span_of = [](const SortChunk& q) { return q.hi > q.lo ? ((q.hi + 15u) & ~15u) - (q.lo & ~15u) : 0u; };
-    auto issue_span = [&](uint4 (&v)[NV], const SortChunk& q) {
-        const uint32_t a0 = q.lo & ~15u, span = span_of(q);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const uint32_t k = (uint32_t)j * (16u * NT) + t * 16u;
-            const uint64_t g = (uint64_t)a0 + k;
-            if (k < span && span <= (uint32_t)CH && g + 16 <= A.in_size) v[j] = *reinterpret_cast<const uint4*>(A.in + g);
-        }
-    };
-    auto commit_span = [&](const uint4 (&v)[NV], const SortChunk& q) {
-        const uint32_t a0 = q.lo & ~15u, span = span_of(q);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const uint32_t k = (uint32_t)j * (16u * NT) + t * 16u;
-            const uint64_t g = (uint64_t)a0 + k;
-            if (k < span) *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_in) + k) =
-                g + 16 <= A.in_size ? v[j] : load16_tail(A.in, A.in_size, g);
-        }
-    };
-    auto issue_chunk = [&](SortChunk (&q)[SPT], uint64_t qb) {
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) q[u] = sort_chunk_issue(A, qb, t + (uint32_t)u * NT, NS);
-    };
-    auto land = [](SortChunk (&q)[SPT]) {  // wait for a chunk's offsets here (see below)
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e), "+v"(q[u].lo), "+v"(q[u].hi) : : "memory");
-    };
-    for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // then cleared by each chunk once every wave has read it
-    __syncthreads();
-    // prepare(q): chunk q's span into the input stage, the output stage zeroed from z0 on ([0, z0) is zero
-    // already), its strings' {offset, length} and their ranks within their length bins.  Called once
-    // nothing reads those areas any more (three barriers a chunk in all).
-    uint4 pv[NV];
-    uint32_t bin[SPT], rank[SPT];
-    auto prepare = [&](const SortChunk (&q)[SPT], uint64_t qb, uint32_t z0) {
-        const uint32_t sp = span_of(q[0]);
-        if (sp > (uint32_t)CH) return;  // workgroup-uniform: the per-thread path needs none of it
-        commit_span(pv, q[0]);
-        for (uint32_t k = z0 + t * 16u; k < sp + 16u; k += 16u * NT)
-            *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k) = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-            const uint32_t tt = t + (uint32_t)u * NT;
-            const uint32_t ln = qb + tt < A.n ? q[u].e - q[u].s : 0u;
-            s_str[tt] = make_uint2(q[u].s - (q[0].lo & ~15u), ln);
-            // counting sort by the bulk loop's trip count (encode_chunk_v2: dwords from the string's first
-            // aligned dword to its end), which the wave's longest string sets
-            bin[u] = ln ? min((q[u].s + ln - (q[u].s & ~3u)) >> 2, kSortBins - 1u) : 0u;
-            rank[u] = atomicAdd(&s_bin[bin[u]], 1u);
-        }
-    };
-    SortChunk cur[SPT];
-    issue_chunk(cur, c * kSortStr);
-    issue_span(pv, cur[0]);
-    prepare(cur, c * kSortStr, 0u);
-    // the next chunk's offsets are loaded a chunk ahead (after barrier 2) and waited for after barrier 3,
-    // before the chunk's stores: no load is then waited for behind a data-dependent number of stores
-    SortChunk nxt[SPT];
-    issue_chunk(nxt, (c + gridDim.x < nch ? c + gridDim.x : c) * kSortStr);
-    land(nxt);  // (once)
-    PROF_DECL  // profile builds: barrier 1 / ranks + barrier 2 / encode / barrier 3 + lengths / copy out / prepare
-    for (;;) {
-        const uint64_t cb = c * kSortStr;
-        const uint32_t lo = cur[0].lo, hi = cur[0].hi, a0 = lo & ~15u, span = span_of(cur[0]);
-        EdgeRec* rec = A.edges + 2 * c;  // two records a chunk (sorted_edge_recs)
-        const uint64_t cn = c + gridDim.x;
-        const bool more = cn < nch;
-        const uint64_t cn2 = cn + gridDim.x;  // the chunk after next
-        __syncthreads();  // the chunk's stage, strings and ranks are in
-        PROF_MARK(0);
-        if (span > (uint32_t)CH) {  // (workgroup-uniform) a chunk larger than the stage: one thread per string
-#pragma unroll
-            for (int u = 0; u < SPT; ++u) {
-                const uint64_t i = cb + t + (uint32_t)u * NT;
-                const uint32_t len = i < A.n ? cur[u].e - cur[u].s : 0u;
-                uint32_t ol = kFailLen;
-                if (i < A.n && len <= kMaxStrLen) {
-                    RegSink sink;
-                    sink.init(A.out + cur[u].s);
-                    ol = encode_core(GlobalSource{A.in, A.in_size}, cur[u].s, len, sink, s_enc);
-                }
-                if (i < A.n) finish_encode(A, (uint32_t)i, len, ol);
-            }
-            if (A.edges && t < 2) rec[t].m = make_uint4(0u, 0u, 0u, 0u);  // direct stores: no edges to defer
-            if (!more) break;
-            issue_span(pv, nxt[0]);
-            prepare(nxt, cn * kSortStr, 0u);
-            {
-                SortChunk nn[SPT];
-                issue_chunk(nn, (cn2 < nch ? cn2 : cn) * kSortStr);
-                land(nn);
-#pragma unroll
-                for (int u = 0; u < SPT; ++u) {
-                    cur[u] = nxt[u];
-                    nxt[u] = nn[u];
-                }
-            }
-            c = cn;
-            continue;
-        }
-        {  // every wave scans the bin counts (two per lane)
-            const uint32_t x0 = s_bin[2 * lane], x1 = s_bin[2 * lane + 1];
-            const uint32_t ex = wave_excl_scan(x0 + x1, (int)lane);
-#pragma unroll
-            for (int u = 0; u < SPT; ++u) {
-                const uint32_t eb = (uint32_t)__shfl((int)ex, (int)(bin[u] >> 1)), xb = (uint32_t)__shfl((int)x0, (int)(bin[u] >> 1));
-                s_perm[eb + ((bin[u] & 1u) ? xb : 0u) + rank[u]] = (uint16_t)(t + (uint32_t)u * NT);
-            }
-        }
-        __syncthreads();
-        PROF_MARK(1);
-        for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // read by every wave above: cleared for the next chunk
-        if (more) issue_span(pv, nxt[0]);     // the next chunk's span: in flight during the encode
-        SortChunk nn[SPT];
-        issue_chunk(nn, (cn2 < nch ? cn2 : (more ? cn : c)) * kSortStr);
-        // sorted position t = 64 wave + lane: wave w encodes the w-th length group (SPT = 2: then also the
-        // sorted position NS - 1 - t, so the pair's lengths add up to about twice the mean)
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-            const uint32_t j = s_perm[u == 0 ? t : NS - 1u - t];
-            const uint2 sj = s_str[j];
-            const bool vj = cb + j < A.n;
-            const bool act = vj && sj.y != 0 && sj.y <= kMaxStrLen;
-            // (DEFER_LONG: the second walk of kept strings with long codes ends before barrier 3 below)
-            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, false, true>(
-                s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x, s_enc, act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
-            // the encoded length goes back to the string's own record (read by its own thread only), so the
-            // lengths and statuses are stored in string order, coalesced
-            s_str[j].x = act && tb != kFailLen ? (tb + 7) >> 3 : kFailLen;
-        }
-        PROF_MARK(2);
-        __syncthreads();
-        uint32_t olen[SPT];
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) olen[u] = s_str[t + (uint32_t)u * NT].x;
-        // the next chunk goes in now, before this chunk's stores: its span loads (in flight since the encode
-        // began) are then waited for with no store ahead of them in the memory counter
-        if (more) prepare(nxt, cn * kSortStr, span);  // (overwrites this thread's records: olen read above)
-        // the chunk after next's offsets are waited for here too, on every path: `nxt = nn` below then copies
-        // registers with no load pending, not behind this chunk's stores
-        land(nn);
-        PROF_MARK(5);
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-            const uint64_t i = cb + t + (uint32_t)u * NT;
-            if (i < A.n) finish_encode(A, (uint32_t)i, cur[u].e - cur[u].s, olen[u]);
-        }
-        PROF_MARK(3);
-        // the stage's MSB-first words, byte-swapped on the way out (each read chunk is zeroed for the next
-        // chunk); the chunk's first and last 16-B chunks are deferred (edge_fix_kernel)
-        const uint32_t kl = (span - 1u) & ~15u;
-        // every chunk's LDS read first (NV of them), then the stores: one LDS round trip a chunk, not one each
-        uint4 cv[NV];
-#pragma unroll
-        for (int jv = 0; jv < NV; ++jv) {
-            const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
-            if (k < span) cv[jv] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(s_out) + k);
-        }
-#pragma unroll
-        for (int jv = 0; jv < NV; ++jv) {
-            const uint32_t k = (uint32_t)jv * (16u * NT) + t * 16u;
-            if (k >= span) break;
-            const uint64_t g = (uint64_t)a0 + k;
-            uint4* sp = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k);
-            uint4 v = cv[jv];
-            const bool full = g >= lo && g + 16 <= hi;
-            // (a partial edge chunk stored one byte a lane below is zeroed there, after its bytes are read)
-            if (full || A.edges || !HHUFF_EDGE_BYTES) *sp = make_uint4(0u, 0u, 0u, 0u);
-            v = make_uint4(bswap32(v.x), bswap32(v.y), bswap32(v.z), bswap32(v.w));
-            if (full) st16_out(A.out + g, v);
-            if (k == 0 || k == kl) {
-                const uint32_t elo = lo > g ? (uint32_t)(lo - g) : 0u;
-                const uint32_t ehi = hi - g < 16 ? (uint32_t)(hi - g) : 16u;
-                if (A.edges) {
-                    EdgeRec* e = rec + (k == 0 ? 0 : 1);
-                    e->v = v;
-                    e->m = make_uint4((uint32_t)g, (uint32_t)(g >> 32), full ? 0u : elo, full ? 0u : ehi);
-                } else if (!HHUFF_EDGE_BYTES && !full && ehi > elo) {  // small batches: the shared chunk's own bytes
-                    store_range16r(A.out + g, v, elo, ehi);
-                }
-            }
-        }
-        if (HHUFF_EDGE_BYTES && !A.edges && t < 64u) {  // small batches: the two partial chunks, a byte a lane (wave 0)
-            const uint8_t* so = reinterpret_cast<const uint8_t*>(s_out);
-            edge_bytes<true>(A.out, a0, so, span, lo, hi, (int)t);
-            // lane b read byte b ^ 3 of its chunk and zeroes byte b: every read lands before any lane's zeroing
-            wave_lds_sync();
-            if (t < 32u && span != 0) {  // zero the bytes read (the chunk was left in place above when partial)
-                const uint32_t ke = t < 16u ? 0u : kl;
-                if (!((uint64_t)a0 + ke >= lo && (uint64_t)a0 + ke + 16 <= hi))
-                    reinterpret_cast<uint8_t*>(s_out)[ke + (t & 15u)] = 0;
-            }
-        }
-        if (A.edges && t == 0 && (kl == 0 || span == 0)) rec[1].m = make_uint4(0u, 0u, 0u, 0u);  // one chunk, or none
-        if (A.edges && t == 0 && span == 0) rec[0].m = make_uint4(0u, 0u, 0u, 0u);
-        PROF_MARK(4);
-        if (!more) {
-            PROF_FLUSH(1);
-            break;
-        }
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-            cur[u] = nxt[u];
-            nxt[u] = nn[u];
-        }
-        c = cn;
-    }
-}
-
-// The same kernel trimmed to five workgroups a CU, for batches whose chunks fit a smaller stage (launch_encode:
-// a mean string of at most HHUFF_ENCO_SMALL_MEAN bytes).  LDS: a stage of at most 13,568 B, a 257-entry code
-// table (the head and tail words are masked and look up entry 256 outside the string), one packed record a string,
-// 16-bit encoded lengths, byte ranks: 31,072 B at CH = 13,312.  Registers, 96 VGPRs for five waves a SIMD (a wave
-// of each workgroup on every SIMD): the chunk's span in scalar registers, a chunk's offsets kept in its LDS
-// records only, the next span handed on through LDS, two copy-out chunks in flight, and the thread index a fresh
-// value in each phase of the loop (fresh() below).  At four workgroups a CU the trimmed kernel is 2-4 % slower than
-// the one above (the phase-local index arithmetic alone costs 2 %), so the large stage keeps that kernel.
-namespace five {  // (the kernel keeps its name: profiles and bench.py file it under the sorted encoder)
-template <int NS, int CH, int SPT = 1>
-__global__ __launch_bounds__(NS / SPT) __attribute__((amdgpu_waves_per_eu(5)))
-void encode_sorted_kernel(EncArgs A) {
-    static_assert(SPT == 1 || SPT == 2, "one string a thread, or a sorted pair");
-    constexpr uint32_t kSortStr = NS, NT = NS / SPT;
-    static_assert(NS <= 256 && CH % 16 == 0 && CH <= 13568, "a rank is a byte, a span offset 14 bits; five stages a CU");
-    constexpr int NV = (CH + 16 * NT - 1) / (16 * NT);  // 16-B span chunks per thread
-    constexpr int CB = 2;  // those of the copy-out read ahead of their stores (96 VGPRs hold two)
-    __shared__ __attribute__((aligned(16))) uint2 s_enc[257];  // 256: bytes outside a string
-    __shared__ __attribute__((aligned(16))) uint32_t s_in[CH / 4 + 8];
-    __shared__ __attribute__((aligned(16))) uint32_t s_out[CH / 4 + 8];
-    __shared__ uint32_t s_str[kSortStr];  // offset in the span | length << 14 of chunk string t
-    __shared__ uint16_t s_olen[kSortStr];  // its encoded length (kSortFail: none), back to its own thread
-    __shared__ uint8_t s_perm[kSortStr];
-    __shared__ uint32_t s_bin[kSortBins];  // strings per bin, then the bins' first places
-    __shared__ uint32_t s_lohi[2][2];       // the next chunk's input span {lo, hi}, by the parity of the trip
+    __shared__ uint32_t s_lohi[2][2];      // (trimmed) the next chunk's input span {lo, hi}, by the parity of the trip
     uint32_t t = threadIdx.x;
     // fresh(): the thread index as a new value.  What a phase of the loop derives from it (addresses of the
     // thread's records and stage chunks, its predicates) is then computed in that phase, not once before the loop
     // and kept in registers across the encode: fourteen VGPRs (111 -> 97 as the allocator leaves them).
-    auto fresh = [&] { __asm__ volatile("" : "+v"(t)); };
+    auto fresh = [&] {
+        if constexpr (P::kTrim) __asm__ volatile("" : "+v"(t));
+    };
     const uint32_t lane = threadIdx.x & 63u;  // (PROF_FLUSH's, in profile builds)
     (void)lane;
-    for (uint32_t k = t; k < 257; k += NT) s_enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
+    load_enc_table<P::kEnc>(s_enc, NT);
     const uint64_t nch = ((uint64_t)A.n + kSortStr - 1) / kSortStr;
     uint64_t c = blockIdx.x;
     if (c >= nch) return;
@@ -2065,26 +1858,37 @@ void encode_sorted_kernel(EncArgs A) {
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
             __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e), "+v"(q[u].lo), "+v"(q[u].hi) : : "memory");
-            // the chunk's span is the same in every lane: kept in scalar registers from here on
-            q[u].lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)q[u].lo);
-            q[u].hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)q[u].hi);
+            if constexpr (P::kTrim) {  // the chunk's span is the same in every lane: kept in scalar registers from here on
+                q[u].lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)q[u].lo);
+                q[u].hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)q[u].hi);
+            }
         }
     };
-    // In the loop a thread loads its own strings' offsets only (two registers in flight across the encode, not
-    // four): the span is the first string's start and the last one's end (sort_chunk_issue's clamps make
-    // them so in a short last chunk too), handed to the next trip through s_lohi[par].
-    auto issue_strings = [&](SortChunk (&q)[SPT], uint64_t qb) {
+    // The offsets of the chunk after next, issued and waited for in the loop.  Trimmed: a thread loads its own
+    // strings' offsets only (two registers in flight across the encode, not four): the span is the first string's
+    // start and the last one's end (sort_chunk_issue's clamps make them so in a short last chunk too), handed to
+    // the next trip through s_lohi[par].
+    uint32_t par = 0;
+    auto issue_ahead = [&](SortChunk (&q)[SPT], uint64_t qb) {
+        if constexpr (P::kTrim) {
 #pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-            const uint64_t ic = min(qb + t + (uint32_t)u * NT, (uint64_t)A.n - 1u);
-            q[u] = SortChunk{A.in_off[ic], A.in_off[ic + 1], 0u, 0u};
+            for (int u = 0; u < SPT; ++u) {
+                const uint64_t ic = min(qb + t + (uint32_t)u * NT, (uint64_t)A.n - 1u);
+                q[u] = SortChunk{A.in_off[ic], A.in_off[ic + 1], 0u, 0u};
+            }
+        } else {
+            issue_chunk(q, qb);
         }
     };
-    auto land_strings = [&](SortChunk (&q)[SPT], uint32_t par) {
+    auto land_ahead = [&](SortChunk (&q)[SPT]) {
+        if constexpr (P::kTrim) {
 #pragma unroll
-        for (int u = 0; u < SPT; ++u) __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e) : : "memory");
-        if (t == 0) s_lohi[par][0] = q[0].s;
-        if (t == NT - 1u) s_lohi[par][1] = q[SPT - 1].e;
+            for (int u = 0; u < SPT; ++u) __asm__ volatile("" : "+v"(q[u].s), "+v"(q[u].e) : : "memory");
+            if (t == 0) s_lohi[par ^ 1u][0] = q[0].s;
+            if (t == NT - 1u) s_lohi[par ^ 1u][1] = q[SPT - 1].e;
+        } else {
+            land(q);
+        }
     };
     for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // then cleared by each chunk once every wave has read it
     __syncthreads();
@@ -2103,8 +1907,9 @@ void encode_sorted_kernel(EncArgs A) {
         for (int u = 0; u < SPT; ++u) {
             const uint32_t tt = t + (uint32_t)u * NT;
             const uint32_t ln = qb + tt < A.n ? q[u].e - q[u].s : 0u;
-            // (an empty string may start at the span's end, offset CH: it is never read, and is recorded at 0)
-            s_str[tt] = ln ? (q[u].s - (q[0].lo & ~15u)) | ln << 14 : 0u;
+            // (packed: an empty string may start at the span's end, offset CH: it is never read, and is recorded at 0)
+            if constexpr (P::kTrim) s_str[tt] = ln ? (q[u].s - (q[0].lo & ~15u)) | ln << 14 : 0u;
+            else s_str[tt] = make_uint2(q[u].s - (q[0].lo & ~15u), ln);
             // counting sort by the bulk loop's trip count (encode_chunk_v2: dwords from the string's first
             // aligned dword to its end), which the wave's longest string sets
             bin[u] = ln ? min((q[u].s + ln - (q[u].s & ~3u)) >> 2, kSortBins - 1u) : 0u;
@@ -2113,7 +1918,7 @@ void encode_sorted_kernel(EncArgs A) {
     };
     SortChunk cur[SPT];
     issue_chunk(cur, c * kSortStr);
-    land(cur);
+    if constexpr (P::kTrim) land(cur);  // (its span to scalar registers)
     issue_span(pv, cur[0]);
     prepare(cur, c * kSortStr, 0u);
     // the next chunk's offsets are loaded a chunk ahead (after barrier 2) and waited for after barrier 3,
@@ -2121,11 +1926,12 @@ void encode_sorted_kernel(EncArgs A) {
     SortChunk nxt[SPT];
     issue_chunk(nxt, (c + gridDim.x < nch ? c + gridDim.x : c) * kSortStr);
     land(nxt);  // (once)
-    if (t == 0) {
-        s_lohi[0][0] = nxt[0].lo;
-        s_lohi[0][1] = nxt[0].hi;
+    if constexpr (P::kTrim) {
+        if (t == 0) {
+            s_lohi[0][0] = nxt[0].lo;
+            s_lohi[0][1] = nxt[0].hi;
+        }
     }
-    uint32_t par = 0;
     PROF_DECL  // profile builds: barrier 1 / ranks + barrier 2 / encode / barrier 3 + lengths / copy out / prepare
     for (;;) {
         const uint64_t cb = c * kSortStr;
@@ -2134,21 +1940,35 @@ void encode_sorted_kernel(EncArgs A) {
         const uint64_t cn = c + gridDim.x;
         const bool more = cn < nch;
         const uint64_t cn2 = cn + gridDim.x;  // the chunk after next
-        __syncthreads();  // the chunk's stage, strings and ranks are in, and the next chunk's span
+        __syncthreads();  // the chunk's stage, strings and ranks are in (trimmed: and the next chunk's span)
         PROF_MARK(0);
         fresh();
-        const uint32_t nlo = s_lohi[par][0], nhi = s_lohi[par][1];  // read here, used after the next barrier
+        uint32_t nlo = 0, nhi = 0;
+        if constexpr (P::kTrim) nlo = s_lohi[par][0], nhi = s_lohi[par][1];  // read here, used after the next barrier
         auto next_span = [&] {
-            nxt[0].lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nlo);
-            nxt[0].hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)nhi);
+            if constexpr (P::kTrim) {
+                nxt[0].lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nlo);
+                nxt[0].hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)nhi);
+            }
+        };
+        auto advance = [&](const SortChunk (&nn)[SPT]) {
+#pragma unroll
+            for (int u = 0; u < SPT; ++u) {
+                cur[u] = nxt[u];
+                nxt[u] = nn[u];
+            }
+            c = cn;
+            par ^= 1u;
         };
         if (span > (uint32_t)CH) {  // (workgroup-uniform) a chunk larger than the stage: one thread per string
 #pragma unroll
             for (int u = 0; u < SPT; ++u) {
                 const uint64_t i = cb + t + (uint32_t)u * NT;
-                // (a staged chunk's offsets live on in its LDS records only: loaded again on this rare path)
-                const uint32_t s = A.in_off[min(i, (uint64_t)A.n - 1u)];
-                const uint32_t len = i < A.n ? A.in_off[i + 1] - s : 0u;
+                uint32_t s = cur[u].s, len = i < A.n ? cur[u].e - cur[u].s : 0u;
+                if constexpr (P::kTrim) {  // a staged chunk's offsets live on in its LDS records only: loaded again on this rare path
+                    s = A.in_off[min(i, (uint64_t)A.n - 1u)];
+                    len = i < A.n ? A.in_off[i + 1] - s : 0u;
+                }
                 uint32_t ol = kFailLen;
                 if (i < A.n && len <= kMaxStrLen) {
                     RegSink sink;
@@ -2162,18 +1982,10 @@ void encode_sorted_kernel(EncArgs A) {
             next_span();
             issue_span(pv, nxt[0]);
             prepare(nxt, cn * kSortStr, 0u);
-            {
-                SortChunk nn[SPT];
-                issue_strings(nn, (cn2 < nch ? cn2 : cn) * kSortStr);
-                land_strings(nn, par ^ 1u);
-#pragma unroll
-                for (int u = 0; u < SPT; ++u) {
-                    cur[u] = nxt[u];
-                    nxt[u] = nn[u];
-                }
-            }
-            c = cn;
-            par ^= 1u;
+            SortChunk nn[SPT];
+            issue_ahead(nn, (cn2 < nch ? cn2 : cn) * kSortStr);
+            land_ahead(nn);
+            advance(nn);
             continue;
         }
         {  // every wave scans the bin counts (two per lane)
@@ -2183,7 +1995,7 @@ void encode_sorted_kernel(EncArgs A) {
 #pragma unroll
             for (int u = 0; u < SPT; ++u) {
                 const uint32_t eb = (uint32_t)__shfl((int)ex, (int)(bin[u] >> 1)), xb = (uint32_t)__shfl((int)x0, (int)(bin[u] >> 1));
-                s_perm[eb + ((bin[u] & 1u) ? xb : 0u) + rank[u]] = (uint8_t)(t + (uint32_t)u * NT);
+                s_perm[eb + ((bin[u] & 1u) ? xb : 0u) + rank[u]] = (typename P::Rank)(t + (uint32_t)u * NT);
             }
         }
         __syncthreads();
@@ -2193,39 +2005,47 @@ void encode_sorted_kernel(EncArgs A) {
         for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // read by every wave above: cleared for the next chunk
         if (more) issue_span(pv, nxt[0]);     // the next chunk's span: in flight during the encode
         SortChunk nn[SPT];
-        issue_strings(nn, (cn2 < nch ? cn2 : (more ? cn : c)) * kSortStr);
+        issue_ahead(nn, (cn2 < nch ? cn2 : (more ? cn : c)) * kSortStr);
         // sorted position t = 64 wave + lane: wave w encodes the w-th length group (SPT = 2: then also the
         // sorted position NS - 1 - t, so the pair's lengths add up to about twice the mean)
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
             const uint32_t j = s_perm[u == 0 ? t : NS - 1u - t];
-            const uint32_t rj = s_str[j];
-            const uint2 sj = make_uint2(rj & 0x3FFFu, rj >> 14);
+            uint2 sj;
+            if constexpr (P::kTrim) sj = make_uint2(s_str[j] & 0x3FFFu, s_str[j] >> 14);
+            else sj = s_str[j];
             const bool vj = cb + j < A.n;
             const bool act = vj && sj.y != 0 && sj.y <= kMaxStrLen;
             // (DEFER_LONG: the second walk of kept strings with long codes ends before barrier 3 below)
-            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, true, true>(
+            const uint32_t tb = encode_chunk_v2<HHUFF_ENC_SORTED_U, P::kTrim, true>(
                 s_in, span - 4u, sj.x, sj.y, act, lds_addr(s_out), 8u * sj.x, s_enc, act ? 8 * sj.y - 7 : 0xFFFFFFFFu, true);
-            // the encoded length goes back to the string's own thread (shorter than the string: 16 bits hold
-            // it), so the lengths and statuses are stored in string order, coalesced
-            s_olen[j] = (uint16_t)(act && tb != kFailLen ? (tb + 7) >> 3 : kSortFail);
+            // the encoded length goes back to the string's own record (read by its own thread only), so the
+            // lengths and statuses are stored in string order, coalesced (trimmed: it is shorter than the
+            // string, so 16 bits hold it)
+            if constexpr (P::kTrim) s_olen[j] = (uint16_t)(act && tb != kFailLen ? (tb + 7) >> 3 : kSortFail);
+            else s_str[j].x = act && tb != kFailLen ? (tb + 7) >> 3 : kFailLen;
         }
         PROF_MARK(2);
         __syncthreads();
         fresh();
         uint32_t olen[SPT], len[SPT];
 #pragma unroll
-        for (int u = 0; u < SPT; ++u) {  // (the string's length from its record: its offsets are kept no longer)
-            const uint32_t o = s_olen[t + (uint32_t)u * NT];
-            olen[u] = o == kSortFail ? kFailLen : o;
-            len[u] = s_str[t + (uint32_t)u * NT] >> 14;
+        for (int u = 0; u < SPT; ++u) {
+            if constexpr (P::kTrim) {  // (the string's length from its record: its offsets are kept no longer)
+                const uint32_t o = s_olen[t + (uint32_t)u * NT];
+                olen[u] = o == kSortFail ? kFailLen : o;
+                len[u] = s_str[t + (uint32_t)u * NT] >> 14;
+            } else {
+                olen[u] = s_str[t + (uint32_t)u * NT].x;
+                len[u] = cur[u].e - cur[u].s;
+            }
         }
         // the next chunk goes in now, before this chunk's stores: its span loads (in flight since the encode
         // began) are then waited for with no store ahead of them in the memory counter
         if (more) prepare(nxt, cn * kSortStr, span);  // (overwrites this thread's records: read above)
         // the chunk after next's offsets are waited for here too, on every path: `nxt = nn` below then copies
         // registers with no load pending, not behind this chunk's stores
-        land_strings(nn, par ^ 1u);
+        land_ahead(nn);
         PROF_MARK(5);
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
@@ -2237,8 +2057,8 @@ void encode_sorted_kernel(EncArgs A) {
         // the stage's MSB-first words, byte-swapped on the way out (each read chunk is zeroed for the next
         // chunk); the chunk's first and last 16-B chunks are deferred (edge_fix_kernel)
         const uint32_t kl = (span - 1u) & ~15u;
-        // CB chunks' LDS reads first, then their stores: an LDS round trip a batch, not one each (all NV at once,
-        // as in encode_sorted_kernel, takes 8 more registers than five waves a SIMD leave)
+        // CB chunks' LDS reads first, then their stores: an LDS round trip a batch, not one each (wide: all NV at
+        // once, one round trip a chunk; that takes 8 more registers than five waves a SIMD leave)
 #pragma unroll
         for (int j0 = 0; j0 < NV; j0 += CB) {
             uint4 cv[CB];
@@ -2290,14 +2110,19 @@ void encode_sorted_kernel(EncArgs A) {
             PROF_FLUSH(1);
             break;
         }
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-            cur[u] = nxt[u];
-            nxt[u] = nn[u];
-        }
-        c = cn;
-        par ^= 1u;
+        advance(nn);
     }
+}
+template <int NS, int CH, int SPT = 1>
+__global__ __launch_bounds__(NS / SPT) void encode_sorted_kernel(EncArgs A) {
+    encode_sorted_body<SortedWide, NS, CH, SPT>(A);
+}
+namespace five {  // (the kernel keeps its name: profiles and bench.py file it under the sorted encoder)
+template <int NS, int CH, int SPT = 1>
+__global__ __launch_bounds__(NS / SPT) __attribute__((amdgpu_waves_per_eu(5)))
+void encode_sorted_kernel(EncArgs A) {
+    static_assert(NS <= 256 && CH % 16 == 0 && CH <= 13568, "a rank is a byte, a span offset 14 bits; five stages a CU");
+    encode_sorted_body<SortedTrim, NS, CH, SPT>(A);
 }
 }  // namespace five
 
@@ -2363,27 +2188,74 @@ __device__ __forceinline__ void pl_clear_spare_edges(EdgeRec* edges, uint64_t nt
         edges[r].m = make_uint4(0u, 0u, 0u, 0u);
 }
 
-template <int WAVES, int STAGE>
-__global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32_t K, const uint32_t* __restrict__ kplan,
-                                                               uint64_t rec_cap) {
-    struct __attribute__((aligned(16))) Smem {
-        uint2 enc[512];  // 256..511: bytes outside a share
-        uint32_t in[WAVES][STAGE / 4];
-        uint32_t out[WAVES][STAGE / 4 + 4];
-        uint32_t lmap[WAVES][64];
-        uint8_t nb[272];  // code lengths for pass 1 (chunk_code_bits_nb); 256: outside the share
-    };
-    __shared__ Smem sm;
+// What encode_pl_kernel and flatten_pl_kernel share (their software pipelines stay apart: see flatten_pl_kernel).
+//
+// pl_setup: the block's tables -- enc[512] (256..511: bytes outside a share) and nb[272], the code lengths for
+// pass 1 (chunk_code_bits_nb; 256: outside the share) -- and its tile size, behind one barrier.
+template <class Smem>
+__device__ __forceinline__ uint32_t pl_setup(Smem& sm, uint32_t K, const uint32_t* __restrict__ kplan, int nthreads) {
     __shared__ uint32_t s_k;
-    for (uint32_t k = threadIdx.x; k < 512; k += WAVES * 64)
-        sm.enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
-    for (uint32_t k = threadIdx.x; k < 272; k += WAVES * 64) sm.nb[k] = k < 256 ? (uint8_t)g_enc_nbits[k] : (uint8_t)0;
+    load_enc_table<512>(sm.enc, nthreads);
+    for (uint32_t k = threadIdx.x; k < 272; k += nthreads) sm.nb[k] = k < 256 ? (uint8_t)g_enc_nbits[k] : (uint8_t)0;
     if (kplan && threadIdx.x < 64) {  // tile size from encode_plan_kernel's samples (K is then its ceiling)
         const uint32_t k = plan_tile_strings(kplan, K);
         if (threadIdx.x == 0) s_k = k;
     }
     __syncthreads();
-    if (kplan) K = s_k;
+    return kplan ? s_k : K;
+}
+// pl_split: the share of a staged tile that this lane takes.  The tile's kt strings (lane i < kt holds string i:
+// start s, length len; total bytes in all, span from a0) get g lanes each, string i from lane L on; lane -> string
+// through lmap (64 words of the wave's own) and a max-scan.
+struct PlShare {
+    uint32_t j;               // the string this lane works on
+    uint32_t L, used;         // first lane of the lane's own string i; lanes in use
+    uint32_t sj, lj, Lj, gj;  // string j: start, length, first lane, lanes
+    uint32_t c0, c1;          // this lane's share of it: bytes [c0, c1) of the string
+    uint32_t cs, clen;        // ... as an offset in the stage, and its length
+};
+__device__ __forceinline__ PlShare pl_split(int lane, uint32_t kt, uint32_t s, uint32_t len, uint32_t total,
+                                            uint32_t a0, uint32_t* lmap) {
+    PlShare h;
+    // lanes per string, first lane of each string, lane -> string map
+    const uint32_t g = (uint32_t)lane < kt ? 1u + (uint32_t)(((uint64_t)(64u - kt) * len) / (total ? total : 1u)) : 0u;
+    h.L = wave_excl_scan(g, lane);
+    h.used = (uint32_t)__shfl((int)(h.L + g), (int)kt - 1, 64);
+    lmap[lane] = 0;
+    wave_lds_sync();
+    if ((uint32_t)lane < kt) lmap[h.L] = (uint32_t)lane;
+    wave_lds_sync();
+    h.j = lmap[lane];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {  // inclusive max scan: the string whose first lane is at or below
+        const uint32_t y = (uint32_t)__shfl_up((int)h.j, o, 64);
+        if (lane >= o) h.j = max(h.j, y);
+    }
+    h.sj = (uint32_t)__shfl((int)s, (int)h.j, 64);
+    h.lj = (uint32_t)__shfl((int)len, (int)h.j, 64);
+    h.Lj = (uint32_t)__shfl((int)h.L, (int)h.j, 64);
+    h.gj = (uint32_t)__shfl((int)g, (int)h.j, 64);
+    const uint32_t sub = (uint32_t)lane - h.Lj;
+    const uint32_t C = h.gj > 1 ? (((h.lj + h.gj - 1) / h.gj) + 3u) & ~3u : h.lj;
+    h.c0 = min(sub * C, h.lj);
+    h.c1 = min(sub * C + C, h.lj);
+    h.cs = h.sj - a0 + h.c0;
+    h.clen = h.c1 - h.c0;
+    return h;
+}
+
+template <int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32_t K, const uint32_t* __restrict__ kplan,
+                                                               uint64_t rec_cap) {
+    struct __attribute__((aligned(16))) Smem {
+        uint2 enc[512];
+        uint32_t in[WAVES][STAGE / 4];
+        uint32_t out[WAVES][STAGE / 4 + 4];
+        uint32_t lmap[WAVES][64];
+        uint8_t nb[272];
+    };
+    __shared__ Smem sm;
+    K = pl_setup(sm, K, kplan, WAVES * 64);
     const uint2* s_enc = sm.enc;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* stage = sm.in[wave];
@@ -2446,30 +2318,9 @@ __global__ __launch_bounds__(WAVES * 64) void encode_pl_kernel(EncArgs A, uint32
         if (cur.fits) {
             for (uint32_t k = (uint32_t)lane * 16u; k < cur.span + 16u; k += 64u * 16u)
                 *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(obuf32) + k) = make_uint4(0u, 0u, 0u, 0u);
-            // lanes per string, first lane of each string, lane -> string map
-            const uint32_t total = cur.hi - cur.lo;
-            const uint32_t g = own ? 1u + (uint32_t)(((uint64_t)(64u - cur.kt) * len) / (total ? total : 1u)) : 0u;
-            const uint32_t L = wave_excl_scan(g, lane);
-            const uint32_t used = (uint32_t)__shfl((int)(L + g), (int)cur.kt - 1, 64);
-            lmap[lane] = 0;
-            wave_lds_sync();
-            if (own) lmap[L] = (uint32_t)lane;
-            wave_lds_sync();
-            uint32_t j = lmap[lane];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {  // inclusive max scan: the string whose first lane is at or below
-                const uint32_t y = (uint32_t)__shfl_up((int)j, o, 64);
-                if (lane >= o) j = max(j, y);
-            }
-            const bool act = (uint32_t)lane < used;
-            const uint32_t sj = (uint32_t)__shfl((int)cur.s, (int)j, 64);
-            const uint32_t lj = (uint32_t)__shfl((int)len, (int)j, 64);
-            const uint32_t Lj = (uint32_t)__shfl((int)L, (int)j, 64);
-            const uint32_t gj = (uint32_t)__shfl((int)g, (int)j, 64);
-            const uint32_t sub = (uint32_t)lane - Lj;
-            const uint32_t C = gj > 1 ? (((lj + gj - 1) / gj) + 3u) & ~3u : lj;
-            const uint32_t c0 = min(sub * C, lj), c1 = min(sub * C + C, lj);
-            const uint32_t cs = sj - cur.a0 + c0, clen = c1 - c0;
+            const PlShare h = pl_split(lane, cur.kt, cur.s, len, cur.hi - cur.lo, cur.a0, lmap);
+            const uint32_t L = h.L, sj = h.sj, lj = h.lj, Lj = h.Lj, gj = h.gj, c1 = h.c1, cs = h.cs, clen = h.clen;
+            const bool act = (uint32_t)lane < h.used;
             const bool multi = gj > 1;
             const bool big = act && lj <= kMaxStrLen;
             const uint32_t last = cur.span ? cur.span - 4u : 0u;
@@ -2574,10 +2425,10 @@ struct FlatArgs {
     EdgeRec* edges = nullptr;  // flatten_pl_kernel: 2 deferred-edge records per tile
 };
 
-// RFC 7541 5.1 prefix integer (hpack.c:757-772) OR-ed into first byte h0: up to 6 bytes for v < 2^32
-__device__ __forceinline__ void push_prefix_int(RegSink& sink, uint32_t h0, uint32_t v, uint32_t p) {
+// RFC 7541 5.1 prefix integer (hpack.c:757-772) as bytes, OR-ed into first byte h0: up to 6 bytes for v < 2^32;
+// returns the byte count
+__device__ __forceinline__ uint32_t prefix_int_bytes(uint32_t h0, uint32_t v, uint32_t p, uint64_t& hb) {
     const uint32_t pmax = (1u << p) - 1u;
-    uint64_t hb;
     uint32_t hn = 1;
     if (v < pmax) {
         hb = h0 | v;
@@ -2592,8 +2443,39 @@ __device__ __forceinline__ void push_prefix_int(RegSink& sink, uint32_t h0, uint
         hb |= (uint64_t)v << (8 * hn);
         ++hn;
     }
+    return hn;
+}
+__device__ __forceinline__ void push_prefix_int(RegSink& sink, uint32_t h0, uint32_t v, uint32_t p) {
+    uint64_t hb;
+    const uint32_t hn = prefix_int_bytes(h0, v, p, hb);
     sink.push((uint32_t)hb, min(hn, 4u));
     if (hn > 4) sink.push((uint32_t)(hb >> 32), hn - 4);
+}
+
+// One string of at most kMaxStrLen bytes framed from global memory into `sink` (initialised at its slot): the
+// framed length.  `first` is the slot's first byte as given, p the prefix bits, raw the string's raw flag.
+__device__ __forceinline__ uint32_t flatten_one_global(const GlobalSource& src, uint32_t s, uint32_t len, uint32_t first,
+                                                       bool raw, uint32_t p, RegSink& sink, const uint2* s_enc) {
+    const uint32_t bits = (raw || len == 0) ? 0u : count_code_bits(src, s, len, s_enc);
+    const bool huff = !raw && len != 0 && bits <= 8 * len - 8;  // ceil(bits / 8) < len (hpack.c:799-800)
+    if (huff) {
+        push_prefix_int(sink, (first & ~((1u << p) - 1u)) | (1u << p), (bits + 7) >> 3, p);  // qpack.c:1054-1056
+        encode_core(src, s, len, sink, s_enc);
+    } else {
+        push_prefix_int(sink, first & ~((2u << p) - 1u), len, p);  // qpack.c:1048-1049 (hpack.c:806-814)
+        uint32_t a = s & ~3u, rem = len;
+        uint32_t skip = s & 3u;
+        while (rem) {
+            const uint32_t w = src.word(a) >> (8 * skip);
+            const uint32_t k = min(4u - skip, rem);
+            sink.push(w, k);
+            rem -= k;
+            a += 4;
+            skip = 0;
+        }
+        sink.finish();
+    }
+    return sink.count();
 }
 
 template <int WAVES>
@@ -2615,47 +2497,8 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_direct_kernel(FlatArgs A) 
             A.out_len[i] = kFailLen;
             continue;
         }
-        const uint32_t bits = (raw || len == 0) ? 0u : count_code_bits(src, s, len, s_enc);
-        const bool huff = !raw && len != 0 && bits <= 8 * len - 8;  // ceil(bits / 8) < len (hpack.c:799-800)
-        if (huff) {
-            push_prefix_int(sink, (first & ~((1u << p) - 1u)) | (1u << p), (bits + 7) >> 3, p);  // qpack.c:1054-1056
-            encode_core(src, s, len, sink, s_enc);
-        } else {
-            push_prefix_int(sink, first & ~((2u << p) - 1u), len, p);  // qpack.c:1048-1049 (hpack.c:806-814)
-            uint32_t a = s & ~3u, rem = len;
-            uint32_t skip = s & 3u;
-            while (rem) {
-                const uint32_t w = src.word(a) >> (8 * skip);
-                const uint32_t k = min(4u - skip, rem);
-                sink.push(w, k);
-                rem -= k;
-                a += 4;
-                skip = 0;
-            }
-            sink.finish();
-        }
-        A.out_len[i] = sink.count();
+        A.out_len[i] = flatten_one_global(src, s, len, first, raw, p, sink, s_enc);
     }
-}
-
-// Prefix integer (hpack.c:757-772) as bytes, OR-ed into first byte h0; returns the byte count (<= 6).
-__device__ __forceinline__ uint32_t prefix_int_bytes(uint32_t h0, uint32_t v, uint32_t p, uint64_t& hb) {
-    const uint32_t pmax = (1u << p) - 1u;
-    uint32_t hn = 1;
-    if (v < pmax) {
-        hb = h0 | v;
-    } else {
-        hb = h0 | pmax;
-        v -= pmax;
-        while (v >= 128) {
-            hb |= (uint64_t)(0x80u | (v & 127u)) << (8 * hn);
-            ++hn;
-            v >>= 7;
-        }
-        hb |= (uint64_t)v << (8 * hn);
-        ++hn;
-    }
-    return hn;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2675,19 +2518,10 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
         uint32_t in[WAVES][STAGE / 4];
         uint32_t out[WAVES][OSTAGE / 4 + 4];
         uint32_t lmap[WAVES][64];
-        uint8_t nb[272];  // code lengths for pass 1 (chunk_code_bits_nb)
+        uint8_t nb[272];
     };
     __shared__ Smem sm;
-    __shared__ uint32_t s_k;
-    for (uint32_t k = threadIdx.x; k < 512; k += WAVES * 64)
-        sm.enc[k] = k < 256 ? make_uint2(g_enc_code[k], g_enc_nbits[k]) : make_uint2(0u, 0u);
-    for (uint32_t k = threadIdx.x; k < 272; k += WAVES * 64) sm.nb[k] = k < 256 ? (uint8_t)g_enc_nbits[k] : (uint8_t)0;
-    if (kplan && threadIdx.x < 64) {  // tile size from encode_plan_kernel's samples (as encode_pl_kernel)
-        const uint32_t k = plan_tile_strings(kplan, K);
-        if (threadIdx.x == 0) s_k = k;
-    }
-    __syncthreads();
-    if (kplan) K = s_k;
+    K = pl_setup(sm, K, kplan, WAVES * 64);
     const uint2* s_enc = sm.enc;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* stage = sm.in[wave];
@@ -2762,30 +2596,11 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
         if (cur.fits) {
             for (uint32_t k = (uint32_t)lane * 16u; k < cur.ospan + 16u; k += 64u * 16u)
                 *reinterpret_cast<uint4*>(obuf + k) = make_uint4(0u, 0u, 0u, 0u);
-            const uint32_t total = cur.hi - cur.lo;
-            const uint32_t g = own ? 1u + (uint32_t)(((uint64_t)(64u - kt) * len) / (total ? total : 1u)) : 0u;
-            const uint32_t L = wave_excl_scan(g, lane);
-            const uint32_t used = (uint32_t)__shfl((int)(L + g), (int)kt - 1, 64);
-            lmap[lane] = 0;
-            wave_lds_sync();
-            if (own) lmap[L] = (uint32_t)lane;
-            wave_lds_sync();
-            uint32_t j = lmap[lane];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = (uint32_t)__shfl_up((int)j, o, 64);
-                if (lane >= o) j = max(j, y);
-            }
-            const bool act = (uint32_t)lane < used;
-            const uint32_t sj = (uint32_t)__shfl((int)s, (int)j, 64);
-            const uint32_t lj = (uint32_t)__shfl((int)len, (int)j, 64);
-            const uint32_t Lj = (uint32_t)__shfl((int)L, (int)j, 64);
-            const uint32_t gj = (uint32_t)__shfl((int)g, (int)j, 64);
+            const PlShare h = pl_split(lane, kt, s, len, cur.hi - cur.lo, cur.a0, lmap);
+            const uint32_t j = h.j, L = h.L, sj = h.sj, lj = h.lj, Lj = h.Lj, gj = h.gj;
+            const uint32_t c0 = h.c0, c1 = h.c1, cs = h.cs, clen = h.clen;
+            const bool act = (uint32_t)lane < h.used;
             const bool rj = __shfl((int)rawf, (int)j, 64) != 0;
-            const uint32_t sub = (uint32_t)lane - Lj;
-            const uint32_t C = gj > 1 ? (((lj + gj - 1) / gj) + 3u) & ~3u : lj;
-            const uint32_t c0 = min(sub * C, lj), c1 = min(sub * C + C, lj);
-            const uint32_t cs = sj - cur.a0 + c0, clen = c1 - c0;
             const bool ok = act && lj <= kMaxStrLen;
             const uint32_t last = cur.span ? cur.span - 4u : 0u;
             wave_lds_sync();
@@ -2805,7 +2620,7 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
             const uint32_t hn = huff ? prefix_int_bytes((fj & ~((1u << p) - 1u)) | (1u << p), hlen, p, hb)
                                      : prefix_int_bytes(fj & ~((2u << p) - 1u), lj, p, hb);
             const uint32_t orel = (uint32_t)((uint64_t)sj + 11u * (cur.i0 + j) - cur.ob);  // slot start in the out stage
-            if (ok && sub == 0)
+            if (ok && (uint32_t)lane == Lj)
                 for (uint32_t k = 0; k < hn; ++k) obuf[(orel + k) ^ 3u] = (uint8_t)(hb >> (8 * k));
             // pass 2: Huffman shares place their code bits; raw shares copy their bytes
             encode_chunk_v2<HHUFF_ENC_OTHER_U>(stage, last, cs, clen, huff && clen != 0, lds_addr(obuf32), 8u * (orel + hn) + (x - xs), s_enc,
@@ -2831,29 +2646,9 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
         } else {
             __asm__ volatile("" : "+v"(nxi.s), "+v"(nxi.e), "+v"(nxi.first), "+v"(nxi.raww) : : "memory");
             if (own && len <= kMaxStrLen) {  // tile larger than the stage: one string per lane from global
-                const uint64_t O = (uint64_t)s + 11u * i;  // output slot
-                const GlobalSource src{A.in, A.in_size};
                 RegSink sink;
-                sink.init(A.out + O);
-                const uint32_t bits = (rawf || len == 0) ? 0u : count_code_bits(src, s, len, s_enc);
-                const bool huff = !rawf && len != 0 && bits <= 8 * len - 8;
-                if (huff) {
-                    push_prefix_int(sink, (first & ~((1u << p) - 1u)) | (1u << p), (bits + 7) >> 3, p);
-                    encode_core(src, s, len, sink, s_enc);
-                } else {
-                    push_prefix_int(sink, first & ~((2u << p) - 1u), len, p);
-                    uint32_t a = s & ~3u, rem = len, skip = s & 3u;
-                    while (rem) {
-                        const uint32_t w = src.word(a) >> (8 * skip);
-                        const uint32_t k = min(4u - skip, rem);
-                        sink.push(w, k);
-                        rem -= k;
-                        a += 4;
-                        skip = 0;
-                    }
-                    sink.finish();
-                }
-                ol = sink.count();
+                sink.init(A.out + (uint64_t)s + 11u * i);  // output slot
+                ol = flatten_one_global(GlobalSource{A.in, A.in_size}, s, len, first, rawf, p, sink, s_enc);
             }
             if (A.edges && lane < 2) A.edges[2 * t + lane].m = make_uint4(0u, 0u, 0u, 0u);  // direct stores: no edges
             PROF_MARK(6);
@@ -3119,6 +2914,11 @@ __global__ void literal_fix_kernel(LitArgs A) {
 //   encode direct:         4 waves/WG                                      [2 KiB]
 //   encode sorted:         4 waves/WG, 256 strings a chunk, 16 KiB in + out [39.1 KiB, 4 WG/CU]
 //   encode sorted (small): the same with 13 KiB in + out, <= 96 VGPRs       [30.3 KiB, 5 WG/CU]
+//     (both are encode_sorted_body: policies SortedWide and SortedTrim; the entry points keep their two names)
+//   encode / flatten proportional lanes: 16 waves/WG, 3.5 KiB in per wave, 3.5 / 4.2 KiB out
+//                                                                          [120.5 / 132 KiB, 1 WG/CU]
+//     (pl_setup and pl_split are shared; each kernel has its own software pipeline)
+//   flatten direct:        4 waves/WG                                      [2 KiB]
 // The variant is picked from the mean bytes per string (in_size / n).
 // ------------------------------------------------------------------------------------------------
 // (measured shapes, kept for the record: stream kernel waves / window dwords / output bytes per lane, c3 /

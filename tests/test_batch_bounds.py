@@ -246,6 +246,32 @@ def test_flatten(torch_cuda, oracle_codec, batches, kind, prefix_bits):
           "flatten %s p=%d" % (kind, prefix_bits), prefix_bits=prefix_bits)
 
 
+@pytest.mark.parametrize("raw_at", [20, 21])
+def test_flatten_tile_past_the_stage(torch_cuda, oracle_codec, batches, raw_at):
+    """flatten_pl_kernel's tile whose span exceeds its 3,584-B stage: every lane frames its string from global
+    memory.  40 strings at a mean that gives tiles of 16: the second tile holds a 4,000-B text (index 20) behind an
+    empty string and before a short text; the raw flag sits on the long string in one run and on its short
+    neighbour in the other, so the tile frames a raw, a Huffman and an empty string both times"""
+    rng = np.random.default_rng(5)
+    strings = list(batches["plain", "short"][:40])
+    strings[19], strings[20], strings[21] = b"", H.text(rng, 4000), H.text(rng, 33)
+    n = len(strings)
+    flags = np.zeros(n, bool)
+    flags[raw_at] = True
+    for fill, sentinel in H.RUNS:
+        inp = H.place_input(strings, "contiguous", 13, fill, op="flatten")
+        assert 117 <= inp["in_size"] // n <= 160  # kPlFill / mean in 16..21: 16 strings a tile, no sampling (n < 4096)
+        assert inp["in_off"][32] - inp["in_off"][16] > 3584
+        kw = dict(prefix_bits=7, first=rng.integers(1, 256, n + H.EXTRA).astype(np.uint8), raw=H.name_bits(flags, fill))
+        _, exp = H.oracle_run(oracle_codec, "flatten", inp, sentinel, **kw)
+        assert (exp["out_len"][20] < 4000) == (raw_at != 20) and exp["out_len"][19] == 1  # Huffman unless raw
+        for defer in (DEFAULT_DEFER, 0):
+            with edge_defer(defer):
+                res = gpu_run(torch_cuda, "flatten", inp, sentinel, **kw)
+            H.check(res, exp, H.mask_of("flatten", inp), sentinel, starts=H.out_starts("flatten", inp),
+                    label="flatten past the stage raw_at=%d defer_min=%#x fill=%#x" % (raw_at, defer, fill))
+
+
 @pytest.mark.parametrize("op", ["decode", "encode", "flatten"])
 def test_last_string_at_every_alignment(torch_cuda, oracle_codec, batches, op):
     """In the contiguous layout every region borders the next one, so a store that runs past a region lands in a
