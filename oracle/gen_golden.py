@@ -33,6 +33,10 @@ Fixture sets (numpy .npz, arrays only, no pickles):
                    short output regions
   block_edges.npz  the hand-built table, arena and literal edge corpora (tests/blocks_corpora.py, qpack_corpora.py)
                    through the reference's HPACK and QPACK decoders: statuses, fields, records
+  rule_edges.npz   the hand-built request / response rule corpus (tests/rules_corpora.py): every case by every byte
+                   route through the reference's h2o_hpack_parse_request / _response (a plain-mode call's blocks
+                   through h2o_hpack_decode_header alone, ref_hpack_parse_mixed) and h2o_qpack_parse_request /
+                   _response: verdicts, field counts, header flags, soft codes and records
   qpenc.npz        HTTP/3 response HEADERS frames (f4, QPACK encode half): synthetic responses (datagram flow ids,
                    statuses outside the static table, dont_compress, names added without their token) flattened by
                    the real h2o_qpack_flatten_response as h2o's HTTP/3 server calls it (ref_shim.c ref_qpe_step),
@@ -959,7 +963,21 @@ def block_edges_set():
     return out
 
 
+def rule_edges_set():
+    """tests/golden/rule_edges.npz: the rule corpus of tests/rules_corpora.py through the reference, next to
+    block_edges_set(): per batch the statuses, field counts, header flags, soft codes and records (no field bytes)"""
+    sys.path.insert(1, os.path.join(ROOT, "tests"))
+    import rules_corpora as RC
+
+    out = RC.reference_results(O.ref())
+    print("rule_edges: %d arrays, %d bytes" % (len(out), sum(v.nbytes for v in out.values())))
+    return out
+
+
 def main():
+    if "--only-rule-edges" in sys.argv:
+        np.savez_compressed(os.path.join(GOLDEN, "rule_edges.npz"), **rule_edges_set())
+        return
     if "--only-block-edges" in sys.argv:
         np.savez_compressed(os.path.join(GOLDEN, "block_edges.npz"), **block_edges_set())
         return
@@ -1007,6 +1025,7 @@ def main():
     sets["qpenc"] = qpenc_set()
     sets["resp"] = resp_set()
     sets["block_edges"] = block_edges_set()
+    sets["rule_edges"] = rule_edges_set()
     for name, arrays in sets.items():
         path = os.path.join(GOLDEN, name + ".npz")
         np.savez_compressed(path, **arrays)

@@ -444,6 +444,7 @@ typedef struct {
     uint32_t *req; /* request mode: 12 words per block, else NULL */
     uint32_t *res; /* response mode: 4 words per block, else NULL */
     const uint8_t *trailers; /* response mode: nonzero = a trailers block (NULL: none) */
+    const uint8_t *plain;    /* nonzero = a block of a plain-mode call: decoded, no rules, a reset record (NULL: none) */
 } orc_blk_job_t;
 
 static void orc_hpack_connection(const orc_blk_job_t *j, uint32_t c)
@@ -469,7 +470,8 @@ static void orc_hpack_connection(const orc_blk_job_t *j, uint32_t c)
         orc_arena_t A = {j->arena, j->arena_off[b], j->arena_off[b + 1] < (1ull << 32) ? j->arena_off[b + 1] : (1ull << 32)};
         uint32_t nf = 0, slot = j->blk_off[b];
         int st = 0;
-        if (j->res && p == end) { /* a head needs :status (hpack.c:652-655); empty trailers: decode_header (:328-329) */
+        const int rules = !(j->plain != NULL && j->plain[b] != 0);
+        if (rules && j->res && p == end) { /* a head needs :status (hpack.c:652-655); empty trailers: decode_header (:328-329) */
             if (!rs.trailers)
                 rs.err = 9;
             st = rs.trailers ? ORC_ERR_COMPRESSION : ORC_ERR_PROTOCOL;
@@ -480,14 +482,16 @@ static void orc_hpack_connection(const orc_blk_job_t *j, uint32_t c)
             int rc = orc_block_field(&t, &p, end, &A, &no, &nl, &vo, &vl, &soft);
             if (rc != 0 && rc != ORC_ERR_INVALID_CHAR) {
                 st = rc;
-                rq.err = rc == ORC_ERR_PROTOCOL ? 7 : 0; /* *err_desc = decode_err (hpack.c:523-525, :663-665) */
-                rs.err = rq.err;
+                if (rules) {
+                    rq.err = rc == ORC_ERR_PROTOCOL ? 7 : 0; /* *err_desc = decode_err (hpack.c:523-525, :663-665) */
+                    rs.err = rq.err;
+                }
                 break;
             }
             int header = 0, rr = 0;
-            if (j->req)
+            if (rules && j->req)
                 rr = orc_rq_field(&rq, j->arena + no, nl, j->arena + vo, vl, soft, (int32_t)nf, &header, 0);
-            if (j->res)
+            if (rules && j->res)
                 rr = orc_rs_field(&rs, j->arena + no, nl, j->arena + vo, vl, soft, (int32_t)nf, &header, 0);
             j->name_off[slot + nf] = no;
             j->name_len[slot + nf] = nl;
@@ -501,12 +505,12 @@ static void orc_hpack_connection(const orc_blk_job_t *j, uint32_t c)
             }
         }
         if (j->req) {
-            if (st == 0 && rq.err != 0)
+            if (rules && st == 0 && rq.err != 0)
                 st = ORC_ERR_INVALID_CHAR; /* hpack.c:636-637 */
             orc_rq_store(j->req + 12 * (size_t)b, &rq);
         }
         if (j->res) {
-            if (st == 0 && rs.err != 0)
+            if (rules && st == 0 && rs.err != 0)
                 st = ORC_ERR_INVALID_CHAR; /* hpack.c:745-747 */
             orc_rs_store(j->res + 4 * (size_t)b, &rs);
         }
@@ -529,7 +533,7 @@ static int orc_hpack_blocks(const uint8_t *in, const uint32_t *blk_off, const ui
                             uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
                             uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
                             uint32_t *nfields, int32_t *bstatus, uint32_t *req, uint32_t *res, const uint8_t *trailers,
-                            int nthreads)
+                            const uint8_t *plain, int nthreads)
 {
     if (nthreads < 1)
         nthreads = 1;
@@ -547,7 +551,7 @@ static int orc_hpack_blocks(const uint8_t *in, const uint32_t *blk_off, const ui
         j->in = in, j->blk_off = blk_off, j->conn_first = conn_first, j->table_size = table_size;
         j->arena = arena, j->arena_off = arena_off, j->name_off = name_off, j->name_len = name_len;
         j->value_off = value_off, j->value_len = value_len, j->fflags = fflags, j->nfields = nfields;
-        j->bstatus = bstatus, j->req = req, j->res = res, j->trailers = trailers;
+        j->bstatus = bstatus, j->req = req, j->res = res, j->trailers = trailers, j->plain = plain;
         j->c_begin = (uint32_t)(((uint64_t)nconn * k) / nthreads);
         j->c_end = (uint32_t)(((uint64_t)nconn * (k + 1)) / nthreads);
     }
@@ -567,7 +571,7 @@ int orc_hpack_decode_blocks(const uint8_t *in, const uint32_t *blk_off, const ui
                             uint32_t *nfields, int32_t *bstatus, int nthreads)
 {
     return orc_hpack_blocks(in, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-                            value_len, fflags, nfields, bstatus, NULL, NULL, NULL, nthreads);
+                            value_len, fflags, nfields, bstatus, NULL, NULL, NULL, NULL, nthreads);
 }
 
 int orc_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
@@ -576,7 +580,7 @@ int orc_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off, const u
                              uint32_t *nfields, int32_t *bstatus, uint32_t *req, int nthreads)
 {
     return orc_hpack_blocks(in, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-                            value_len, fflags, nfields, bstatus, req, NULL, NULL, nthreads);
+                            value_len, fflags, nfields, bstatus, req, NULL, NULL, NULL, nthreads);
 }
 
 int orc_hpack_parse_responses(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
@@ -585,5 +589,17 @@ int orc_hpack_parse_responses(const uint8_t *in, const uint32_t *blk_off, const 
                               uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *res, int nthreads)
 {
     return orc_hpack_blocks(in, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-                            value_len, fflags, nfields, bstatus, NULL, res, trailers, nthreads);
+                            value_len, fflags, nfields, bstatus, NULL, res, trailers, NULL, nthreads);
+}
+
+/* a continuation whose calls differ in mode (HHUFF_BLK_CONTINUE over one scratch), as one run: exactly one of req / res;
+ * plain[b] != 0: block b belongs to a hhuff_hpack_decode_blocks call -- decoded into the connection's table, no rules */
+int orc_hpack_parse_mixed(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                          uint32_t table_size, const uint8_t *trailers, const uint8_t *plain, uint8_t *arena,
+                          const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len, uint32_t *value_off,
+                          uint32_t *value_len, uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *req,
+                          uint32_t *res, int nthreads)
+{
+    return orc_hpack_blocks(in, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
+                            value_len, fflags, nfields, bstatus, req, res, res ? trailers : NULL, plain, nthreads);
 }

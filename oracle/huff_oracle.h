@@ -72,3 +72,10 @@ int orc_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off, const u
                              uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
                              uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
                              uint32_t *nfields, int32_t *bstatus, uint32_t *req, int nthreads);
+/* calls of different modes over one connection state, as one run: exactly one of req / res; plain[b] != 0: block b is
+ * decoded without the rules (a block of a hhuff_hpack_decode_blocks call) */
+int orc_hpack_parse_mixed(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                          uint32_t table_size, const uint8_t *trailers, const uint8_t *plain, uint8_t *arena,
+                          const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len, uint32_t *value_off,
+                          uint32_t *value_len, uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *req,
+                          uint32_t *res, int nthreads);

@@ -95,6 +95,17 @@ class _Codec:
         f.argtypes = [_u8p, _u32p, _u32p, ctypes.c_uint32, ctypes.c_uint, ctypes.c_uint, _u32p, _u8p, _u32p, _u32p,
                       _u32p, _u8p, ctypes.c_int]
 
+    def _parse_mixed(self):
+        """<prefix>_hpack_parse_mixed, bound on first use: only the rule-edge tests need it, and a library built before
+        it existed (an oracle/_ref that travelled with an older tree) still serves every other caller"""
+        f = getattr(self.lib, self.prefix + "_hpack_parse_mixed", None)
+        assert f is not None, "%s has no %s_hpack_parse_mixed: rebuild it (make -C oracle)" % (self.lib._name, self.prefix)
+        f.restype = ctypes.c_int
+        f.argtypes = [_u8p, _u32p, _u32p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p,
+                      ctypes.POINTER(ctypes.c_uint64), _u32p, _u32p, _u32p, _u32p, _u8p, _u32p,
+                      ctypes.POINTER(ctypes.c_int32), _u32p, _u32p, ctypes.c_int]
+        return f
+
     # ---- per-string (h2o signatures) ----
     def decode(self, src: bytes, is_name: bool = False, soft_in: int = 0):
         """-> (bytes or None on SIZE_MAX, soft_errors word)"""
@@ -198,12 +209,14 @@ class _Codec:
 
 
     def hpack_decode_blocks(self, data, blk_off, conn_first, table_size=4096, arena_off=None, nthreads=1,
-                            requests=False, responses=False, trailers=None):
+                            requests=False, responses=False, trailers=None, plain=None):
         """HPACK header blocks (include/hhuff.h hhuff_hpack_decode_blocks contract) -> dict of arrays:
         arena, name_off, name_len, value_off, value_len, fflags (per field slot), nfields, bstatus (per block);
         requests=True: hhuff_hpack_parse_requests (h2o_hpack_parse_request per block), plus req (REQ_DTYPE);
         responses=True: hhuff_hpack_parse_responses (h2o_hpack_parse_response per block; trailers = u8 per
-        block, nonzero for a trailers block), plus res (RES_DTYPE)"""
+        block, nonzero for a trailers block), plus res (RES_DTYPE);
+        plain (with either; u8 per block): nonzero for a block that belongs to a plain-mode call of a continuation
+        whose later calls parse requests / responses -- decoded into the connection's table without the rules"""
         data = np.ascontiguousarray(data, dtype=np.uint8)
         blk_off = np.ascontiguousarray(blk_off, dtype=np.uint32)
         conn_first = np.ascontiguousarray(conn_first, dtype=np.uint32)
@@ -222,7 +235,15 @@ class _Codec:
                 _ptr(r["name_off"], _u32p), _ptr(r["name_len"], _u32p), _ptr(r["value_off"], _u32p),
                 _ptr(r["value_len"], _u32p), _ptr(r["fflags"], _u8p), _ptr(r["nfields"], _u32p),
                 r["bstatus"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))]
-        if responses:
+        if plain is not None and (requests or responses):
+            tr = None if trailers is None else np.ascontiguousarray(trailers, dtype=np.uint8)
+            pl = np.ascontiguousarray(plain, dtype=np.uint8)
+            words = np.zeros((max(1, nb), 4 if responses else 12), np.uint32)
+            rc = self._parse_mixed()(
+                *args[:5], _ptr(tr, _u8p), _ptr(pl, _u8p), *args[5:], None if responses else _ptr(words, _u32p),
+                _ptr(words, _u32p) if responses else None, nthreads)
+            r["res" if responses else "req"] = words.view(RES_DTYPE if responses else REQ_DTYPE).reshape(-1)
+        elif responses:
             tr = None if trailers is None else np.ascontiguousarray(trailers, dtype=np.uint8)
             words = np.zeros((max(1, nb), 4), np.uint32)
             rc = getattr(self.lib, self.prefix + "_hpack_parse_responses")(*args[:5], _ptr(tr, _u8p), *args[5:],

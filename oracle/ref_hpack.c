@@ -34,6 +34,47 @@
 #define REF_BLK_ARENA (-300)
 #define REF_BLK_SKIPPED (-301)
 
+/* one block through h2o_hpack_decode_header, field after field -> its status */
+static int ref_plain_block(h2o_hpack_header_table_t *table, const uint8_t *in, const uint32_t *blk_off, uint32_t b,
+                           uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len,
+                           uint32_t *value_off, uint32_t *value_len, uint8_t *fflags, uint32_t *nfields)
+{
+    h2o_mem_pool_t pool;
+    h2o_mem_init_pool(&pool);
+    const uint8_t *src = in + blk_off[b], *end = in + blk_off[b + 1];
+    uint64_t cur = arena_off[b], aend = arena_off[b + 1] < (1ull << 32) ? arena_off[b + 1] : (1ull << 32);
+    uint32_t nf = 0, slot = blk_off[b];
+    int st = 0;
+    while (src != end) {
+        h2o_iovec_t *name, value;
+        const char *err_desc = NULL;
+        int ret = h2o_hpack_decode_header(&pool, table, &name, &value, &src, end, &err_desc);
+        if (ret != 0 && ret != H2O_HTTP2_ERROR_INVALID_HEADER_CHAR) {
+            st = ret;
+            break;
+        }
+        if (cur + name->len + value.len > aend) {
+            st = REF_BLK_ARENA;
+            break;
+        }
+        memcpy(arena + cur, name->base, name->len);
+        name_off[slot + nf] = (uint32_t)cur;
+        name_len[slot + nf] = (uint32_t)name->len;
+        cur += name->len;
+        memcpy(arena + cur, value.base, value.len);
+        value_off[slot + nf] = (uint32_t)cur;
+        value_len[slot + nf] = (uint32_t)value.len;
+        cur += value.len;
+        /* the field's soft errors are what decode_header reports as INVALID_HEADER_CHAR
+         * (hpack.c:427-431); which bit is recovered from err_desc */
+        fflags[slot + nf] = ret == 0 ? 0 : (err_desc == h2o_hpack_soft_err_found_invalid_char_in_header_name ? 1 : 2);
+        ++nf;
+    }
+    h2o_mem_clear_pool(&pool);
+    nfields[b] = nf;
+    return st;
+}
+
 REF_API int ref_hpack_decode_blocks(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
                                     uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
                                     uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
@@ -51,39 +92,8 @@ REF_API int ref_hpack_decode_blocks(const uint8_t *in, const uint32_t *blk_off, 
                 bstatus[b] = REF_BLK_SKIPPED;
                 continue;
             }
-            h2o_mem_pool_t pool;
-            h2o_mem_init_pool(&pool);
-            const uint8_t *src = in + blk_off[b], *end = in + blk_off[b + 1];
-            uint64_t cur = arena_off[b], aend = arena_off[b + 1] < (1ull << 32) ? arena_off[b + 1] : (1ull << 32);
-            uint32_t nf = 0, slot = blk_off[b];
-            int st = 0;
-            while (src != end) {
-                h2o_iovec_t *name, value;
-                const char *err_desc = NULL;
-                int ret = h2o_hpack_decode_header(&pool, &table, &name, &value, &src, end, &err_desc);
-                if (ret != 0 && ret != H2O_HTTP2_ERROR_INVALID_HEADER_CHAR) {
-                    st = ret;
-                    break;
-                }
-                if (cur + name->len + value.len > aend) {
-                    st = REF_BLK_ARENA;
-                    break;
-                }
-                memcpy(arena + cur, name->base, name->len);
-                name_off[slot + nf] = (uint32_t)cur;
-                name_len[slot + nf] = (uint32_t)name->len;
-                cur += name->len;
-                memcpy(arena + cur, value.base, value.len);
-                value_off[slot + nf] = (uint32_t)cur;
-                value_len[slot + nf] = (uint32_t)value.len;
-                cur += value.len;
-                /* the field's soft errors are what decode_header reports as INVALID_HEADER_CHAR
-                 * (hpack.c:427-431); which bit is recovered from err_desc */
-                fflags[slot + nf] = ret == 0 ? 0 : (err_desc == h2o_hpack_soft_err_found_invalid_char_in_header_name ? 1 : 2);
-                ++nf;
-            }
-            h2o_mem_clear_pool(&pool);
-            nfields[b] = nf;
+            int st = ref_plain_block(&table, in, blk_off, b, arena, arena_off, name_off, name_len, value_off, value_len,
+                                     fflags, nfields);
             bstatus[b] = st;
             failed = st != 0;
         }
@@ -187,12 +197,11 @@ static uint32_t rq_err_code(const char *e)
     return 99;
 }
 
-REF_API int ref_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
-                                     uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
-                                     uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
-                                     uint32_t *nfields, int32_t *bstatus, uint32_t *req, int nthreads)
+static int parse_requests(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                          uint32_t table_size, const uint8_t *plain, uint8_t *arena, const uint64_t *arena_off,
+                          uint32_t *name_off, uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
+                          uint32_t *nfields, int32_t *bstatus, uint32_t *req)
 {
-    (void)nthreads;
     for (uint32_t c = 0; c < nconn; ++c) {
         h2o_hpack_header_table_t table;
         memset(&table, 0, sizeof(table));
@@ -211,7 +220,11 @@ REF_API int ref_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off,
             memset(&x, 0, sizeof(x));
             for (int i = 0; i < 6; ++i)
                 x.taken[i] = -1;
-            if (!failed) {
+            if (!failed && plain != NULL && plain[b] != 0) { /* a block of a plain-mode call: no rules, a reset record */
+                bstatus[b] = ref_plain_block(&table, in, blk_off, b, arena, arena_off, name_off, name_len, value_off,
+                                             value_len, fflags, nfields);
+                failed = bstatus[b] != 0;
+            } else if (!failed) {
                 h2o_mem_pool_t pool;
                 h2o_mem_init_pool(&pool);
                 h2o_cache_digests_t *digests = NULL;
@@ -248,13 +261,22 @@ REF_API int ref_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off,
     return 0;
 }
 
-/* ---- h2o_hpack_parse_response ---- */
-REF_API int ref_hpack_parse_responses(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
-                                      uint32_t table_size, const uint8_t *trailers, uint8_t *arena, const uint64_t *arena_off,
-                                      uint32_t *name_off, uint32_t *name_len, uint32_t *value_off, uint32_t *value_len,
-                                      uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *res, int nthreads)
+REF_API int ref_hpack_parse_requests(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                                     uint32_t table_size, uint8_t *arena, const uint64_t *arena_off, uint32_t *name_off,
+                                     uint32_t *name_len, uint32_t *value_off, uint32_t *value_len, uint8_t *fflags,
+                                     uint32_t *nfields, int32_t *bstatus, uint32_t *req, int nthreads)
 {
     (void)nthreads;
+    return parse_requests(in, blk_off, conn_first, nconn, table_size, NULL, arena, arena_off, name_off, name_len, value_off,
+                          value_len, fflags, nfields, bstatus, req);
+}
+
+/* ---- h2o_hpack_parse_response ---- */
+static int parse_responses(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                           uint32_t table_size, const uint8_t *trailers, const uint8_t *plain, uint8_t *arena,
+                           const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len, uint32_t *value_off,
+                           uint32_t *value_len, uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *res)
+{
     for (uint32_t c = 0; c < nconn; ++c) {
         h2o_hpack_header_table_t table;
         memset(&table, 0, sizeof(table));
@@ -272,7 +294,11 @@ REF_API int ref_hpack_parse_responses(const uint8_t *in, const uint32_t *blk_off
             for (int i = 0; i < 6; ++i)
                 x.taken[i] = -1, x.out[i] = &unused;
             x.scheme = (const h2o_url_scheme_t **)&x.scheme_snap; /* unchanging: rq_settle sees no scheme */
-            if (!failed) {
+            if (!failed && plain != NULL && plain[b] != 0) {
+                bstatus[b] = ref_plain_block(&table, in, blk_off, b, arena, arena_off, name_off, name_len, value_off,
+                                             value_len, fflags, nfields);
+                failed = bstatus[b] != 0;
+            } else if (!failed) {
                 h2o_mem_pool_t pool;
                 h2o_mem_init_pool(&pool);
                 x.table = &table, x.arena = arena, x.cur = arena_off[b];
@@ -299,4 +325,30 @@ REF_API int ref_hpack_parse_responses(const uint8_t *in, const uint32_t *blk_off
         h2o_hpack_dispose_header_table(&table);
     }
     return 0;
+}
+
+REF_API int ref_hpack_parse_responses(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                                      uint32_t table_size, const uint8_t *trailers, uint8_t *arena, const uint64_t *arena_off,
+                                      uint32_t *name_off, uint32_t *name_len, uint32_t *value_off, uint32_t *value_len,
+                                      uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *res, int nthreads)
+{
+    (void)nthreads;
+    return parse_responses(in, blk_off, conn_first, nconn, table_size, trailers, NULL, arena, arena_off, name_off, name_len,
+                           value_off, value_len, fflags, nfields, bstatus, res);
+}
+
+/* calls of different modes over one connection state, as one run (oracle/huff_oracle.h orc_hpack_parse_mixed): exactly
+ * one of req / res; plain[b] != 0: block b is decoded without the rules */
+REF_API int ref_hpack_parse_mixed(const uint8_t *in, const uint32_t *blk_off, const uint32_t *conn_first, uint32_t nconn,
+                                  uint32_t table_size, const uint8_t *trailers, const uint8_t *plain, uint8_t *arena,
+                                  const uint64_t *arena_off, uint32_t *name_off, uint32_t *name_len, uint32_t *value_off,
+                                  uint32_t *value_len, uint8_t *fflags, uint32_t *nfields, int32_t *bstatus, uint32_t *req,
+                                  uint32_t *res, int nthreads)
+{
+    (void)nthreads;
+    if (req != NULL)
+        return parse_requests(in, blk_off, conn_first, nconn, table_size, plain, arena, arena_off, name_off, name_len,
+                              value_off, value_len, fflags, nfields, bstatus, req);
+    return parse_responses(in, blk_off, conn_first, nconn, table_size, trailers, plain, arena, arena_off, name_off, name_len,
+                           value_off, value_len, fflags, nfields, bstatus, res);
 }

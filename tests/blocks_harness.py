@@ -26,7 +26,8 @@ ARENA, SKIPPED, COMPRESSION, PROTOCOL, INVALID_CHAR = -300, -301, -9, -1, -254
 SPACER_SLICE = 48  # arena bytes of a spacer connection's empty block: written by nobody
 SLOT_ARRAYS = (("name_off", np.uint32), ("name_len", np.uint32), ("value_off", np.uint32), ("value_len", np.uint32),
                ("fflags", np.uint8))
-RECORD_WORDS = {"req": 12, "res": 4, "qreq": 18}  # hhuff_request_t / _response_t / _qpack_request_t as u32 words
+RECORD_WORDS = {"req": 12, "res": 4, "qreq": 18, "qres": 10}  # hhuff_request_t / _response_t / _qpack_request_t /
+# _qpack_response_head_t as u32 words
 DTYPES = {"arena": np.uint8, "bstatus": np.int32, "sstatus": np.int32, "enc_status": np.int32,
           "req_insert_count": np.uint64, "insert_count": np.uint64}  # every other output array is u32
 
@@ -117,16 +118,18 @@ def huff_variants(rng, L):
 # ------------------------------------------------------------------------------------------------
 # cases and batches
 # ------------------------------------------------------------------------------------------------
-def case(name, *conns, arena=None, ent=64, room=0):
-    """one call: every connection is a list of blocks.  arena: {(conn, call, block): bytes} overrides of the
+def case(name, *conns, arena=None, ent=64, room=0, trailers=()):
+    """one call: every connection is a list of blocks.  trailers: the (conn, call, block) that are trailers blocks in
+    response mode (hhuff_hpack_parse_responses' trailers array; no case with any: the call passes NULL).  arena: {(conn, call, block): bytes} overrides of the
     default slice (floor(8 L / 5) + L * ent + 64 + room for a block of L bytes: a field takes at least one byte and
     an indexed one copies at most ent bytes; room: for the few fields that copy more)"""
-    return dict(name=name, conns=[[list(c)] for c in conns], arena=arena or {}, ent=ent, room=room)
+    return dict(name=name, conns=[[list(c)] for c in conns], arena=arena or {}, ent=ent, room=room, trailers=set(trailers))
 
 
-def ccase(name, *conns, arena=None, ent=64, room=0):
+def ccase(name, *conns, arena=None, ent=64, room=0, trailers=()):
     """several calls: every connection is a list (one entry per call) of lists of blocks"""
-    return dict(name=name, conns=[[list(b) for b in c] for c in conns], arena=arena or {}, ent=ent, room=room)
+    return dict(name=name, conns=[[list(b) for b in c] for c in conns], arena=arena or {}, ent=ent, room=room,
+                trailers=set(trailers))
 
 
 def default_slice(L, ent, room=0):
@@ -138,10 +141,11 @@ def batch(cases, table_size, nconn=None, seed=0, spacers=True, arena_base=0, tai
     each round until there are nconn connections; with spacers, every second connection is a one-block connection
     whose block is empty: it owns an arena slice (SPACER_SLICE bytes) that nothing may write.  arena_base =
     arena_off[0]; tail = input bytes behind the last block (in_size - blk_off[nblk]).
-    -> dict(table_size, nconn, calls=[dict(data, in_size, blk_off, conn_first, arena_off, labels, nblk)])"""
+    -> dict(table_size, nconn, calls=[dict(data, in_size, blk_off, conn_first, arena_off, labels, nblk[, trailers])])"""
     rng = np.random.default_rng(seed)
     ncalls = max(len(c) for k in cases for c in k["conns"])
-    conns = []  # (label, per-call block lists, per-call slice lists)
+    conns = []  # (label, per-call block lists, per-call slice lists, per-call trailers flags)
+    any_trailers = any(k.get("trailers") for k in cases)
     rounds = 0
     while True:
         order = np.arange(len(cases)) if rounds == 0 else rng.permutation(len(cases))
@@ -151,9 +155,10 @@ def batch(cases, table_size, nconn=None, seed=0, spacers=True, arena_base=0, tai
                 per_call = [list(c[i]) if i < len(c) else [] for i in range(ncalls)]
                 slices = [[k["arena"].get((j, i, b), default_slice(len(blk), k["ent"], k["room"]))
                            for b, blk in enumerate(bl)] for i, bl in enumerate(per_call)]
-                conns.append((k["name"], per_call, slices))
+                tr = [[int((j, i, b) in k.get("trailers", ())) for b in range(len(bl))] for i, bl in enumerate(per_call)]
+                conns.append((k["name"], per_call, slices, tr))
                 if spacers:
-                    conns.append(("spacer", [[b""]] * ncalls, [[SPACER_SLICE]] * ncalls))
+                    conns.append(("spacer", [[b""]] * ncalls, [[SPACER_SLICE]] * ncalls, [[0]] * ncalls))
         rounds += 1
         if nconn is None or len(conns) >= nconn:
             break
@@ -161,10 +166,11 @@ def batch(cases, table_size, nconn=None, seed=0, spacers=True, arena_base=0, tai
         conns = conns[:nconn]
     calls = []
     for i in range(ncalls):
-        blocks, labels, sizes, conn_first = [], [], [], [0]
-        for label, per_call, slices in conns:
+        blocks, labels, sizes, conn_first, trailers = [], [], [], [0], []
+        for label, per_call, slices, tr in conns:
             blocks += per_call[i]
             sizes += slices[i]
+            trailers += tr[i]
             labels += ["%s[call %d block %d]" % (label, i, b) for b in range(len(per_call[i]))]
             conn_first.append(len(blocks))
         blk_off = np.zeros(len(blocks) + 1, np.uint64)
@@ -176,6 +182,8 @@ def batch(cases, table_size, nconn=None, seed=0, spacers=True, arena_base=0, tai
         calls.append(dict(data=data, in_size=int(data.size), blk_off=blk_off.astype(np.uint32),
                           conn_first=np.asarray(conn_first, np.uint32), arena_off=arena_off, labels=labels,
                           nblk=len(blocks)))
+        if any_trailers:
+            calls[-1]["trailers"] = np.asarray(trailers, np.uint8)
     return dict(table_size=table_size, nconn=len(conns), calls=calls)
 
 
@@ -195,17 +203,20 @@ def _empty_result(cl, mode):
 
 def combined_run(codec, calls, table_size, modes, extra=0):
     """The calls' blocks decoded connection by connection in one oracle run per mode (the oracle keeps no tables
-    between runs), every block with an arena slice of its own call's size (+ extra), and the results put back into
+    between runs; the blocks of a plain-mode call take no part in a request / response run's rules, as in the
+    continuation they stand for), every block with an arena slice of its own call's size (+ extra), and the results put back into
     each call's layout: offsets relative to the call's arena_off, slots at the call's blk_off.  "used" = bytes of
     each block's slice its fields take."""
     ncalls, nconn = len(calls), len(calls[0]["conn_first"]) - 1
-    blocks, where, conn_first = [], [], [0]
+    blocks, where, conn_first, trailers, plain = [], [], [0], [], []
     for c in range(nconn):
         for i, cl in enumerate(calls):
             cf, bo = cl["conn_first"], cl["blk_off"]
             for b in range(int(cf[c]), int(cf[c + 1])):
                 blocks.append(cl["data"][int(bo[b]):int(bo[b + 1])].tobytes())
                 where.append((i, b))
+                trailers.append(int(cl["trailers"][b]) if cl.get("trailers") is not None else 0)
+                plain.append(int(modes[i] in (None, "plain")))
         conn_first.append(len(blocks))
     pk = HS.pack_connections([blocks[conn_first[c]:conn_first[c + 1]] for c in range(nconn)])
     sizes = np.asarray([int(calls[i]["arena_off"][b + 1]) - int(calls[i]["arena_off"][b]) + extra for i, b in where],
@@ -216,7 +227,11 @@ def combined_run(codec, calls, table_size, modes, extra=0):
     runs = {}
     for m in set(modes):
         runs[m] = codec.hpack_decode_blocks(pk["data"], pk["blk_off"], pk["conn_first"], table_size, arena_off=cao,
-                                            nthreads=8, requests=m == "req", responses=m == "res")
+                                            nthreads=8, requests=m == "req", responses=m == "res",
+                                            trailers=np.asarray(trailers, np.uint8) if m == "res" and any(trailers)
+                                            else None,
+                                            plain=np.asarray(plain, np.uint8) if m in ("req", "res") and any(plain)
+                                            else None)
     out = [_empty_result(cl, modes[i]) for i, cl in enumerate(calls)]
     for g, (i, b) in enumerate(where):
         r, o, cl = runs[modes[i]], out[i], calls[i]
@@ -273,6 +288,7 @@ def call_args(cl, table_size, nconn, mode, cont, fill, sentinel):
                 blk_off=_poisoned(cl["blk_off"], np.uint32, 0, n),
                 conn_first=_poisoned(cl["conn_first"], np.uint32, 0, nblk),
                 arena_off=_poisoned(cl["arena_off"], np.uint64, int(cl["arena_off"][0]), int(cl["arena_off"][-1])),
+                trailers=_poisoned(cl["trailers"], np.uint8, 0, 1) if cl.get("trailers") is not None else None,
                 out=out, scratch_guards=None)
 
 
@@ -415,7 +431,8 @@ class OracleBlocks:
         data = a["data"] if self.fault == "stale" else a["data"].copy()
         self.history.append(dict(data=data, blk_off=a["blk_off"][:nblk + 1].copy(), in_size=a["in_size"], nblk=nblk,
                                  conn_first=a["conn_first"][:nconn + 1].copy(),
-                                 arena_off=a["arena_off"][:nblk + 1].copy(), mode=a["mode"]))
+                                 arena_off=a["arena_off"][:nblk + 1].copy(), mode=a["mode"],
+                                 trailers=None if a.get("trailers") is None else a["trailers"][:nblk].copy()))
         modes = [h["mode"] for h in self.history]
         if self.fault == "huff_len":
             r = self._by_decoded_length(a)
@@ -508,7 +525,9 @@ class GpuBlocks:
                 o("bstatus")]
         tail = [_inner(self.scratch), ss, 1 if a["cont"] else 0, None]
         if a["mode"] == "res":
-            rc = L.hhuff_hpack_parse_responses(*args[:6], None, *args[6:], o("res"), *tail)
+            trailers = None if a.get("trailers") is None else dev(a["trailers"])
+            rc = L.hhuff_hpack_parse_responses(*args[:6], None if trailers is None else _vp(trailers), *args[6:],
+                                               o("res"), *tail)
         elif a["mode"] == "req":
             rc = L.hhuff_hpack_parse_requests(*args, o("req"), *tail)
         else:
@@ -520,7 +539,7 @@ class GpuBlocks:
         w = self.scratch[0].cpu().numpy()
         a["scratch_guards"] = np.concatenate([w[:GUARD], w[w.size - GUARD:]])
         self.last = [in_whole] + [out[k][0] for k in ("arena",) + tuple(k for k, _ in SLOT_ARRAYS)]
-        self.keep.append((blk_off, conn_first, arena_off, out))
+        self.keep.append((blk_off, conn_first, arena_off, out, trailers if a["mode"] == "res" else None))
 
     def poison(self):
         for t in self.last:  # overwritten in place: they stay allocated, a stale offset would read the pattern
@@ -694,9 +713,16 @@ Q_SECTION = ("nfields", "sstatus", "req_insert_count")
 Q_CONN = ("enc_status", "enc_consumed", "insert_count")
 
 
+def _qwords(r, mode, nsec):
+    """the oracle's records of a step as u32 words"""
+    rec = r["req" if mode == "qreq" else "res"][:nsec]
+    return np.ascontiguousarray(rec).view(np.uint8).reshape(nsec, 4 * RECORD_WORDS[mode]).view(np.uint32)
+
+
 def qexpected(codec, bt, mode="plain"):
     """the oracle's session over the steps -> per step the arrays of expected(), QPACK's per-section and
-    per-connection arrays and, in mode "qreq" (hhuff_qpack_parse_requests), the request records"""
+    per-connection arrays and, in mode "qreq" (hhuff_qpack_parse_requests) / "qres" (hhuff_qpack_parse_responses),
+    the request / response records"""
     from oracle import oracle as O
 
     s = O.QpackSession(codec, bt["nconn"], bt["table_size"], bt["max_blocked"])
@@ -704,15 +730,15 @@ def qexpected(codec, bt, mode="plain"):
     try:
         for cl in bt["calls"]:
             r = s.step(cl["data"], cl["enc_off"], cl["enc_len"], cl["blk_off"], cl["conn_first"], cl["arena_off"],
-                       bt["num_blocked"], stream_id=cl["stream_id"] if mode == "qreq" else None)
+                       bt["num_blocked"], stream_id=cl["stream_id"] if mode != "plain" else None,
+                       responses=mode == "qres")
             e = {k: r[k][:cl["nblk"]] for k in Q_SECTION}
             e.update({k: r[k][:bt["nconn"]] for k in Q_CONN})
             e["arena"] = r["arena"][:int(cl["arena_off"][-1])]
             for k, _ in SLOT_ARRAYS:
                 e[k] = r[k][:cl["in_size"]]
-            if mode == "qreq":
-                e["qreq"] = np.ascontiguousarray(r["req"][:cl["nblk"]]).view(np.uint8).reshape(
-                    cl["nblk"], 72).view(np.uint32)
+            if mode != "plain":
+                e[mode] = _qwords(r, mode, cl["nblk"])
             out.append(e)
     finally:
         s.close()
@@ -728,8 +754,8 @@ def qcall_args(cl, bt, mode, cont, fill, sentinel):
             "enc_status": 4 * nconn, "enc_consumed": 4 * nconn, "insert_count": 8 * nconn}
     for k, dt in SLOT_ARRAYS:
         size[k] = n * np.dtype(dt).itemsize
-    if mode == "qreq":
-        size["qreq"] = 72 * nsec
+    if mode != "plain":
+        size[mode] = 4 * RECORD_WORDS[mode] * nsec
     return dict(in_whole=whole, data=inner, in_size=n, nblk=nsec, nconn=nconn, table_size=bt["table_size"],
                 max_blocked=bt["max_blocked"], mode=mode, cont=cont, labels=cl["labels"], sentinel=sentinel,
                 exact=Q_SECTION + Q_CONN, blk_off=_poisoned(cl["blk_off"], np.uint32, 0, n),
@@ -781,7 +807,8 @@ class OracleQpack:
         nsec, nconn = a["nblk"], a["nconn"]
         r = self.s.step(a["data"].copy(), a["enc_off"][:nconn], a["enc_len"][:nconn], a["blk_off"][:nsec + 1],
                         a["conn_first"][:nconn + 1], a["arena_off"][:nsec + 1], a["num_blocked"][:nconn],
-                        stream_id=a["stream_id"][:nsec] if a["mode"] == "qreq" else None)
+                        stream_id=a["stream_id"][:nsec] if a["mode"] != "plain" else None,
+                        responses=a["mode"] == "qres")
         bo = a["blk_off"][:nsec + 1].astype(np.int64)
         slots = _ranges(bo[:-1], r["nfields"][:nsec].astype(np.int64))
         for k, _ in SLOT_ARRAYS:
@@ -794,12 +821,12 @@ class OracleQpack:
             out_view(a, k)[:] = r[k][:nsec]
         for k in Q_CONN:
             out_view(a, k)[:] = r[k][:nconn]
-        if a["mode"] == "qreq":
-            a["out"]["qreq"][GUARD:GUARD + 72 * nsec] = np.ascontiguousarray(r["req"][:nsec]).view(np.uint8).reshape(-1)
+        if a["mode"] != "plain":
+            entries(a["out"][a["mode"]], np.uint32)[:] = _qwords(r, a["mode"], nsec).reshape(-1)
 
 
 class GpuQpack:
-    """hhuff_qpack_decode / hhuff_qpack_parse_requests on guarded device arrays, the scratch of exactly
+    """hhuff_qpack_decode / hhuff_qpack_parse_requests / _parse_responses on guarded device arrays, the scratch of exactly
     hhuff_qpack_scratch_size bytes between guards, moved in poison()"""
 
     def __init__(self, torch, sentinel):
@@ -830,6 +857,8 @@ class GpuQpack:
         tail = [_inner(self.scratch), ss, 1 if a["cont"] else 0, None]
         if a["mode"] == "qreq":
             rc = L.hhuff_qpack_parse_requests(*args, i("stream_id"), o("qreq"), *tail)
+        elif a["mode"] == "qres":
+            rc = L.hhuff_qpack_parse_responses(*args, i("stream_id"), o("qres"), *tail)
         else:
             rc = L.hhuff_qpack_decode(*args, *tail)
         assert rc == 0, "the call returned %d: %s" % (rc, L.hhuff_last_error_string())
@@ -855,6 +884,6 @@ def qsummary(results, bt, mode="plain"):
 
 def qresult_of(a):
     r = {k: out_view(a, k) for k in ("arena",) + Q_SECTION + Q_CONN + tuple(k for k, _ in SLOT_ARRAYS)}
-    if a["mode"] == "qreq":
-        r["qreq"] = entries(a["out"]["qreq"], np.uint32).reshape(a["nblk"], 18)
+    if a["mode"] != "plain":
+        r[a["mode"]] = entries(a["out"][a["mode"]], np.uint32).reshape(a["nblk"], RECORD_WORDS[a["mode"]])
     return r
