@@ -216,6 +216,9 @@ def lib():
         L.hhuff_intern_headers.restype = ctypes.c_int
         L.hhuff_intern_headers.argtypes = [_vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, ctypes.c_uint32,
                                            ctypes.c_uint32, _vp, _vp]
+        L.hhuff_h2_deframe.restype = ctypes.c_int
+        L.hhuff_h2_deframe.argtypes = ([_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp] + [ctypes.c_uint32] * 3 +
+                                       [ctypes.c_uint] + [_vp] * 11 + [ctypes.c_uint64, ctypes.c_uint32, _vp])
         _lib = L
     return _lib
 
@@ -238,7 +241,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_qpack_parse_responses_sessions", "hhuff_qpack_dsession_state_size",
             "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
             "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers", "hhuff_tokens_table_size", "hhuff_tokens_build",
-            "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers") + SLOTS_SYMBOLS
+            "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -920,6 +923,51 @@ def qpack_flatten_sessions(data, hdr, res, conn_first, nres, stream_id, out_off,
         _check(lib().hhuff_qpack_flatten_sessions_peers(_dp(peers), None if st is None else ctypes.byref(st), *args),
                "hhuff_qpack_flatten_sessions_peers")
     r["scratch"] = scratch
+    return r
+
+
+# include/hhuff.h (2k): hhuff_h2_frame_t / hhuff_h2_block_t as numpy records, and the section's constants
+H2_FRAME_DTYPE = np.dtype([("payload_off", "<u4"), ("length", "<u4"), ("stream_id", "<u4"), ("type", "u1"), ("flags", "u1"),
+                           ("rsv", "<u2"), ("frag_off", "<u4"), ("frag_len", "<u4"), ("block", "<u4"), ("rsv2", "<u4")])
+H2_BLOCK_DTYPE = np.dtype([("stream_id", "<u4"), ("end_stream_id", "<u4"), ("flags", "<u4"), ("dependency", "<u4"),
+                           ("weight", "<u4"), ("promised_stream_id", "<u4"), ("first_frame", "<u4"), ("nframes", "<u4")])
+H2F_ACCEPT_PUSH = 1
+H2F_REFUSED, H2F_FRAMES = -310, -311
+ERR_FRAME_SIZE = -6
+(H2F_ERR_NONE, H2F_ERR_HEADERS_STREAM_ID, H2F_ERR_HEADERS_FRAME, H2F_ERR_HEADERS_PRIORITY, H2F_ERR_EXPECTED_CONTINUATION,
+ H2F_ERR_INVALID_CONTINUATION, H2F_ERR_PUSH_PROMISE, H2F_ERR_PROMISE_STREAM_ID, H2F_ERR_PROMISE_FRAME) = range(9)
+H2B_END_STREAM, H2B_PRIORITY, H2B_EXCLUSIVE, H2B_CONTINUED, H2B_PROMISE, H2B_SELF_DEPENDENCY = 1, 2, 4, 8, 16, 32
+H2O_MAX_REQLEN = 417792  # the server's max_block_bytes (8192 + 4096 * H2O_MAX_HEADERS); the client passes 0
+
+
+def h2_deframe(data, in_off, frm_first, frm_cap, max_frame_size=16384, max_block_bytes=0, flags=0, in_size=None,
+               arena_fixed=None, arena_per_byte=0, stream=None, out=None):
+    """HTTP/2 de-framer (include/hhuff.h hhuff_h2_deframe) on device tensors: data uint8, in_off / frm_first int32 (u32
+    bits) of nconn + 1 entries, frm_cap = frm_first[-1] as a host int.  Returns a dict of device tensors: frames (uint8,
+    H2_FRAME_DTYPE records), nframes, consumed, cstatus, cerr (per connection), blk, blk_off [frm_cap + 1], conn_first,
+    blocks (uint8, H2_BLOCK_DTYPE records), totals [2] and, with arena_fixed given, arena_off (int64 [frm_cap + 1]).
+    blk, blk_off and conn_first go to hpack_decode_blocks as they are (in_size = blk.numel()).  out: a dict with
+    some of these tensors preallocated.  No host synchronisation."""
+    import torch
+
+    dev = data.device
+    in_size = data.numel() if in_size is None else in_size
+    nconn = in_off.numel() - 1
+    out = dict(out or {})
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32 = torch.int32
+    r = dict(frames=new("frames", frm_cap * 32, torch.uint8), nframes=new("nframes", nconn, i32),
+             consumed=new("consumed", nconn, i32), cstatus=new("cstatus", nconn, i32), cerr=new("cerr", nconn, i32),
+             blk=new("blk", in_size, torch.uint8), blk_off=new("blk_off", frm_cap + 1, i32),
+             conn_first=new("conn_first", nconn + 1, i32), blocks=new("blocks", frm_cap * 32, torch.uint8),
+             totals=new("totals", 2, i32))
+    if arena_fixed is not None:
+        r["arena_off"] = new("arena_off", frm_cap + 1, torch.int64)
+    _check(lib().hhuff_h2_deframe(_dp(data), in_size, _dp(in_off), nconn, _dp(frm_first), frm_cap, max_frame_size,
+                                  max_block_bytes, flags, _dp(r["frames"]), _dp(r["nframes"]), _dp(r["consumed"]),
+                                  _dp(r["cstatus"]), _dp(r["cerr"]), _dp(r["blk"]), _dp(r["blk_off"]), _dp(r["conn_first"]),
+                                  _dp(r["blocks"]), _dp(r["totals"]), _dp(r.get("arena_off")), arena_fixed or 0,
+                                  arena_per_byte, _stream(stream)), "hhuff_h2_deframe")
     return r
 
 

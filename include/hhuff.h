@@ -1098,6 +1098,123 @@ int hhuff_intern_fields(const void *table, uint64_t table_size, const uint8_t *a
 int hhuff_intern_headers(const void *table, uint64_t table_size, const uint8_t *in, uint64_t in_size,
                          hhuff_hpack_header_t *hdr, uint32_t nhdr, uint32_t keep_mask, int32_t *token, void *stream);
 
+/* (2k) HTTP/2 frames on the receive side: each connection's raw frame bytes -> the header blocks the decoders of
+ *      (2c) take.  h2o_http2_decode_frame and h2o_http2_decode_headers_payload (lib/http2/frame.c:130-224) and the
+ *      HEADERS -> CONTINUATION sequencing of both h2o sides (lib/http2/connection.c:757-803, 1023-1095, 1288-1325;
+ *      lib/common/http2client.c:448-491, 607-659, 873-925), for many connections at once.
+ *        connection c   in[in_off[c] .. in_off[c+1]): the bytes the previous call did not consume, then the new
+ *                       ones (behind the 24-byte preface, which is the caller's); frame slots frm_first[c] ..
+ *                       frm_first[c+1] - 1 of `frames` (frm_first[nconn] = frm_cap, host copy)
+ *        frames         frames[frm_first[c] + i], i < nframes[c]: the frames walked, in wire order; payload_off and
+ *                       frag_off are offsets in `in`; the other slots are not written
+ *        blk, blk_off,  the completed header blocks, their fragments copied together, packed back to back in
+ *        conn_first     connection order, then wire order: block b = blk[blk_off[b] .. blk_off[b+1]); connection c's
+ *                       blocks are conn_first[c] .. conn_first[c+1] - 1.  blk has in_size bytes (de-framed bytes
+ *                       never exceed the input), blk_off frm_cap + 1 entries -- those past nblk all hold the total,
+ *                       so they read as empty blocks --, conn_first nconn + 1, blocks frm_cap (blocks[b] for
+ *                       b < nblk is written).  blk, blk_off, conn_first and nconn are, as they are and on the same
+ *                       stream, the in, blk_off, conn_first and nconn of hhuff_hpack_decode_blocks,
+ *                       _parse_requests, _parse_responses and their _slots variants (in_size = this call's)
+ *        totals         [0] = nblk, [1] = the block bytes
+ *        arena_off      NULL, or frm_cap + 1 u64: arena_off[b] = the running sum of arena_fixed + arena_per_byte *
+ *                       (block length) over the blocks before b (entries past nblk hold the total), which sizes
+ *                       the decoders' arena slices without reading a length back
+ *      The call keeps no state.  consumed[c] (relative to in_off[c]) is the end of the last frame after which no
+ *      header block is open: a trailing partial frame is not consumed, nor is a HEADERS / PUSH_PROMISE frame whose
+ *      END_HEADERS has not arrived, nor its CONTINUATIONs, and such frames are not listed in `frames`.  The caller
+ *      keeps in[in_off[c] + consumed[c] ..) and presents it again in front of the next bytes.
+ *      Per connection the frames are walked by these rules, in h2o's order.  The first failing rule stops the
+ *      walk: cstatus[c] = h2o's return value, cerr[c] = the HHUFF_H2F_ERR_* that names h2o's err_desc; the blocks
+ *      and frames completed before stand, and consumed[c] is the end of the last completed unit (a frame that is
+ *      no header frame, or a whole header block).
+ *      1. Fewer than 9 bytes left: cstatus 0 (h2o: H2O_HTTP2_ERROR_INCOMPLETE, wait for more).
+ *      2. length > max_frame_size: -6 (H2O_HTTP2_ERROR_FRAME_SIZE), decided by the header alone.  h2o passes
+ *         16384 on both sides.
+ *      3. Fewer than 9 + length bytes left: cstatus 0.
+ *      4. While a block is open: any type but CONTINUATION is -1 (HHUFF_H2F_ERR_EXPECTED_CONTINUATION).  A
+ *         CONTINUATION appends its whole payload; its stream id is not compared with the opener's (h2o looks the
+ *         stream up, which is the caller's) and that of the frame with END_HEADERS is the block's end_stream_id.
+ *         With max_block_bytes != 0, a CONTINUATION whose length added to the block's size so far exceeds
+ *         max_block_bytes stops the walk with HHUFF_H2F_REFUSED.  h2o's server (max_block_bytes =
+ *         H2O_MAX_REQLEN = 417792) at that point sends RST_STREAM with REFUSED_STREAM, resets the stream and goes
+ *         on expecting CONTINUATION frames, which it drops (connection.c:796-800); that is the caller's to do
+ *         with the bytes from consumed[c] on.  h2o's client has no limit: pass 0.
+ *      5. No block open, HEADERS: stream id 0 is -1 (_HEADERS_STREAM_ID); PADDED with length 0 or a pad length
+ *         above the bytes behind the pad byte is -1 (_HEADERS_FRAME); PRIORITY with fewer than 5 bytes left is -1
+ *         (_HEADERS_PRIORITY: h2o sets no err_desc); an even stream id is -1 (_HEADERS_STREAM_ID).  dependency ==
+ *         stream_id sets HHUFF_H2B_SELF_DEPENDENCY and is no error here: h2o's server ignores it on trailers and
+ *         rejects it elsewhere ("stream cannot depend on itself"), and only the caller knows which streams are
+ *         open.  END_HEADERS completes the block, otherwise the frame opens it.
+ *      6. No block open, CONTINUATION: -1 (_INVALID_CONTINUATION).
+ *      7. No block open, PUSH_PROMISE: -1 (_PUSH_PROMISE, both h2o sides) unless flags has HHUFF_H2F_ACCEPT_PUSH.
+ *         With it, RFC 9113 6.6: stream id 0 is -1 (_PROMISE_STREAM_ID); padding as for HEADERS and fewer than 4
+ *         bytes for the promised id are -1 (_PROMISE_FRAME); the promised id is those bytes & 0x7fffffff, the rest
+ *         is the fragment; the block is flagged HHUFF_H2B_PROMISE; END_HEADERS and CONTINUATION as for HEADERS.
+ *      8. Every other type, unknown ones included, gets a frame record and is stepped over unexamined: the payload
+ *         rules of those types and every check that needs stream state stay with the caller.
+ *      9. A unit that needs more frame slots than the connection has left: HHUFF_H2F_FRAMES.  A unit is checked to
+ *         its end by rules 1-8 first, so the stop is at a `consumed` boundary and a block whose frames do not all
+ *         fit is not started.
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array (arena_off may be NULL),
+ *      in_size >= 2^32, max_frame_size outside 16384 .. 2^24 - 1 or an unknown flag bit; nconn == 0 returns
+ *      HHUFF_OK.  Asynchronous on `stream`, no host synchronisation and no copy to the host; bitwise deterministic.
+ *      Stream-ordered pool workspace of 8 bytes per connection (and 8 per 256 of them) and 16 per frame slot
+ *      (hhuff_pool_trim).  A connection's range is clamped to in_size and its slots to frm_cap.  Of `in` the call
+ *      reads the connections' bytes and, with them, the aligned dwords (by address) that hold a fragment's bytes: up
+ *      to 3 bytes in front of a fragment's first byte and up to 3 behind its last, so behind in + in_size too where a
+ *      fragment ends there and that address is no multiple of 4 (never across a 4-byte boundary, so never into
+ *      another page). */
+typedef struct hhuff_h2_frame {      /* 32 bytes: one per frame walked */
+    uint32_t payload_off, length;    /* payload at in[payload_off .. + length) */
+    uint32_t stream_id;              /* 31 bits */
+    uint8_t  type, flags; uint16_t rsv;
+    uint32_t frag_off, frag_len;     /* header frames: the block fragment inside the payload
+                                        (padding, priority, promised id stripped); else 0, 0 */
+    uint32_t block;                  /* header frames: index of the block it belongs to; else ~0u */
+    uint32_t rsv2;
+} hhuff_h2_frame_t;
+typedef struct hhuff_h2_block {      /* 32 bytes: one per completed header block */
+    uint32_t stream_id;              /* of the opening HEADERS / PUSH_PROMISE frame */
+    uint32_t end_stream_id;          /* of the frame that carried END_HEADERS (h2o hands the block to THAT stream) */
+    uint32_t flags;                  /* HHUFF_H2B_* */
+    uint32_t dependency; uint32_t weight;   /* 1..256; h2o_http2_default_priority (0, 16) when no PRIORITY flag */
+    uint32_t promised_stream_id;     /* HHUFF_H2B_PROMISE only */
+    uint32_t first_frame, nframes;   /* its frames in frames[] */
+} hhuff_h2_block_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h2_frame_t) == 32 && sizeof(hhuff_h2_block_t) == 32, "record sizes");
+#else /* (C99 has no static assertion: an array type of negative size does not compile) */
+typedef char hhuff_h2_records_are_32_bytes[sizeof(hhuff_h2_frame_t) == 32 && sizeof(hhuff_h2_block_t) == 32 ? 1 : -1];
+#endif
+#define HHUFF_H2F_ACCEPT_PUSH 1u      /* flags: PUSH_PROMISE opens a block (beyond h2o, which refuses it) */
+#define HHUFF_H2F_REFUSED (-310)      /* cstatus: the block outgrew max_block_bytes */
+#define HHUFF_H2F_FRAMES (-311)       /* cstatus: out of frame slots */
+#define HHUFF_H2F_ERR_NONE 0u                  /* *err_desc untouched */
+#define HHUFF_H2F_ERR_HEADERS_STREAM_ID 1u     /* "invalid stream id in HEADERS frame" */
+#define HHUFF_H2F_ERR_HEADERS_FRAME 2u         /* "invalid HEADERS frame" */
+#define HHUFF_H2F_ERR_HEADERS_PRIORITY 3u      /* priority field cut short (h2o: -1 without err_desc) */
+#define HHUFF_H2F_ERR_EXPECTED_CONTINUATION 4u /* "expected CONTINUATION frame" */
+#define HHUFF_H2F_ERR_INVALID_CONTINUATION 5u  /* "received invalid CONTINUATION frame" */
+#define HHUFF_H2F_ERR_PUSH_PROMISE 6u          /* "received PUSH_PROMISE frame" */
+#define HHUFF_H2F_ERR_PROMISE_STREAM_ID 7u     /* ACCEPT_PUSH: PUSH_PROMISE on stream 0 */
+#define HHUFF_H2F_ERR_PROMISE_FRAME 8u         /* ACCEPT_PUSH: bad padding or no room for the promised id */
+#define HHUFF_H2B_END_STREAM 1u       /* the opening HEADERS frame had END_STREAM */
+#define HHUFF_H2B_PRIORITY 2u         /* it had PRIORITY: dependency and weight are the frame's */
+#define HHUFF_H2B_EXCLUSIVE 4u
+#define HHUFF_H2B_CONTINUED 8u        /* the block has CONTINUATION frames */
+#define HHUFF_H2B_PROMISE 16u         /* opened by PUSH_PROMISE */
+#define HHUFF_H2B_SELF_DEPENDENCY 32u /* dependency == stream_id */
+int hhuff_h2_deframe(const uint8_t *in, uint64_t in_size,            /* in_size < 2^32 */
+                     const uint32_t *in_off, uint32_t nconn,         /* connection c: in[in_off[c] .. in_off[c+1]) */
+                     const uint32_t *frm_first,                      /* frame capacity: slots frm_first[c] .. frm_first[c+1] */
+                     uint32_t frm_cap,                               /* host copy of frm_first[nconn] */
+                     uint32_t max_frame_size, uint32_t max_block_bytes, unsigned flags,
+                     hhuff_h2_frame_t *frames, uint32_t *nframes, uint32_t *consumed,
+                     int32_t *cstatus, uint32_t *cerr,
+                     uint8_t *blk, uint32_t *blk_off, uint32_t *conn_first, hhuff_h2_block_t *blocks,
+                     uint32_t *totals /* [2]: nblk, block bytes */,
+                     uint64_t *arena_off, uint64_t arena_fixed, uint32_t arena_per_byte, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
