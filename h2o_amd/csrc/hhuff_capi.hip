@@ -1033,6 +1033,16 @@ using hhuff::Carve;  // the device buffer's pieces (hhuff_launch.h)
 size_t in_off_count(const uint32_t* in_len, uint32_t n) { return in_len ? n : (size_t)n + 1; }
 
 constexpr uint64_t kDefaultChunk = 64ull << 20;  // pipelined host path: input bytes per chunk
+
+// the contiguous layout with implicit output slots: the strings lie inside `in` and the last slot ends inside `out`
+// (as host_packed and multi_device refuse; checked before any device call)
+int check_implicit(bool decode, uint64_t in_size, const uint32_t* in_off, uint32_t n, uint64_t out_size) {
+    if (in_off[n] > in_size) return arg_fail("in_off[n] > in_size");
+    const uint64_t slot_end = decode ? ((uint64_t)in_off[n] * 8) / 5 : in_off[n];
+    if (out_size < slot_end) return arg_fail("out_size below the output slots of the batch");
+    return HHUFF_OK;
+}
+
 int pipelined(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t* in_off, uint32_t n,
               const uint32_t* is_name_bits, uint8_t* out, uint64_t out_size, uint32_t* out_len, uint8_t* status,
               int device, uint64_t chunk_bytes);
@@ -1042,7 +1052,12 @@ int host_batch(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t*
                uint32_t* out_len, uint8_t* status, int device) {
     if (n == 0) return HHUFF_OK;
     if (!in || !in_off || !out || !out_len || (decode && !status)) return arg_fail("NULL array");
-    if (!in_len && !out_off && in_size >= 2 * kDefaultChunk && in_off[n] <= in_size)  // large contiguous batch
+    if (!in_len && !out_off) {
+        // (a short `out` used to size the device piece the kernels' slots are addressed in: they wrote past it)
+        const int bad = check_implicit(decode, in_size, in_off, n, out_size);
+        if (bad) return bad;
+    }
+    if (!in_len && !out_off && in_size >= 2 * kDefaultChunk)  // large contiguous batch
         return pipelined(decode, in, in_size, in_off, n, is_name_bits, out, out_size, out_len, status, device, 0);
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
@@ -1173,6 +1188,7 @@ int grow(Slot& x, size_t dneed, size_t hneed) {
 int pipelined(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t* in_off, uint32_t n,
               const uint32_t* is_name_bits, uint8_t* out, uint64_t out_size, uint32_t* out_len, uint8_t* status,
               int device, uint64_t chunk_bytes) {
+    (void)out_size;  // every caller has checked it against the slots' end (check_implicit)
     if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
@@ -1180,6 +1196,20 @@ int pipelined(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t* 
     int rc = c.bind(device);
     if (rc) return rc;
     Pipe& P = t_pipe;
+    // No way out leaves a slot busy.  A return on an error used to: the chunks in flight could still DMA into the
+    // caller's pinned arrays after the call had returned, and the next call on the thread drained those slots --
+    // bookkeeping that points into the failed call's arrays -- into its own out, out_len and status.  Their work is
+    // waited for and forgotten, nothing is copied.  (After a call that succeeds every slot is drained: no-op.)
+    struct Quiesce {
+        Pipe& P;
+        ~Quiesce() {
+            for (auto& x : P.slot)
+                if (x.busy) {
+                    (void)hipStreamSynchronize(x.s);
+                    x.busy = false;
+                }
+        }
+    } quiesce{P};
     rc = P.bind(c.dev);
     if (rc) return rc;
     const bool pin_in = is_pinned(in), pin_out = is_pinned(out);
@@ -1190,7 +1220,7 @@ int pipelined(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t* 
     // output across PCIe themselves, one launch, no DMA staging -- both link directions in use at once (the
     // chunked DMA pipeline below moved ~55 GB/s in all).  HHUFF_HOST_COPY=1 keeps the pipeline.
     const char* hc = getenv("HHUFF_HOST_COPY");
-    if (pin_in && pin_out && pin_meta && !(hc && *hc && *hc != '0') && out_size >= slot_of(in_off[n])) {
+    if (pin_in && pin_out && pin_meta && !(hc && *hc && *hc != '0')) {  // (out_size: checked by every caller)
         auto dev_ptr = [](const void* p) -> void* {
             if (!p) return nullptr;
             hipPointerAttribute_t a;
@@ -1252,7 +1282,7 @@ int pipelined(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t* 
         const uint64_t s0 = in_off[i0], e0 = in_off[i1];
         const uint64_t base = (s0 / 80) * 80;
         const uint64_t nbytes = e0 - base;
-        const uint64_t olo = slot_of(s0), ohi = std::min<uint64_t>(slot_of(e0), out_size);
+        const uint64_t olo = slot_of(s0), ohi = slot_of(e0);  // (<= out_size: check_implicit)
         const uint64_t obase = slot_of(base);
         const uint64_t ocap = slot_of(e0) - obase + 16;
         const size_t nw = decode && is_name_bits ? (size_t)(m + 31) / 32 : 0;
@@ -1449,7 +1479,8 @@ HHUFF_API int hhuff_decode_batch_host_pipelined(const uint8_t* in, uint64_t in_s
                                                 uint32_t* out_len, uint8_t* status, int device, uint64_t chunk_bytes) {
     if (n == 0) return HHUFF_OK;
     if (!in || !in_off || !out || !out_len || !status) return arg_fail("NULL array");
-    if (in_off[n] > in_size) return arg_fail("in_off[n] > in_size");
+    const int bad = check_implicit(true, in_size, in_off, n, out_size);
+    if (bad) return bad;
     return pipelined(true, in, in_size, in_off, n, is_name_bits, out, out_size, out_len, status, device, chunk_bytes);
 }
 
@@ -1458,7 +1489,8 @@ HHUFF_API int hhuff_encode_batch_host_pipelined(const uint8_t* in, uint64_t in_s
                                                 int device, uint64_t chunk_bytes) {
     if (n == 0) return HHUFF_OK;
     if (!in || !in_off || !out || !out_len) return arg_fail("NULL array");
-    if (in_off[n] > in_size) return arg_fail("in_off[n] > in_size");
+    const int bad = check_implicit(false, in_size, in_off, n, out_size);
+    if (bad) return bad;
     return pipelined(false, in, in_size, in_off, n, nullptr, out, out_size, out_len, status, device, chunk_bytes);
 }
 
@@ -1577,7 +1609,8 @@ DevWorker* g_workers[kMaxDev] = {};          // created on first use, never dest
 
 int multi_host(bool decode, int ndev, const int* dv, const uint8_t* in, uint64_t in_size, const uint32_t* in_off,
                uint32_t n, const uint32_t* names, uint8_t* out, uint64_t out_size, uint32_t* out_len, uint8_t* status) {
-    if (in_off[n] > in_size) return arg_fail("in_off[n] > in_size");
+    const int bad = check_implicit(decode, in_size, in_off, n, out_size);
+    if (bad) return bad;
     std::vector<uint32_t> b(ndev + 1);
     for (int k = 0; k <= ndev; ++k) b[k] = shard_bound(in_off, n, (uint32_t)k, (uint32_t)ndev, kShardAlign);
     std::lock_guard<std::mutex> g(g_multi_mu);

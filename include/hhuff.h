@@ -137,6 +137,9 @@ int hhuff_flatten_batch(const uint8_t *in, uint64_t in_size, const uint32_t *in_
  *     Synchronous.  Same array contract; `out` is a host buffer sized for the implicit layout
  *     (decode: floor(8 * in_size / 5) bytes, encode: in_size bytes) when out_off is NULL.  The results are
  *     copied back in one piece: bytes of `out` that belong to no string's region are unspecified.
+ *     In the contiguous layout with implicit slots (in_len and out_off NULL) the call refuses, before any device
+ *     work, a batch whose strings leave `in` (in_off[n] > in_size) or whose slots leave `out` (out_size below
+ *     decode floor(8 * in_off[n] / 5), encode in_off[n]): HHUFF_EINVAL.
  * ------------------------------------------------------------------------------------------- */
 int hhuff_decode_batch_host(const uint8_t *in, uint64_t in_size, const uint32_t *in_off, const uint32_t *in_len,
                             uint32_t n, const uint32_t *is_name_bits, uint8_t *out, uint64_t out_size,
@@ -1222,7 +1225,9 @@ int hhuff_h2_deframe(const uint8_t *in, uint64_t in_size,            /* in_size 
  *     streams so that host staging copies, H2D, kernels and D2H of different chunks overlap.  Caller
  *     buffers already pinned (hipHostMalloc / hipHostRegister) are DMA'd directly.  Synchronous; the
  *     results equal hhuff_*_batch_host's.  hhuff_*_batch_host take this path by themselves for
- *     contiguous batches of 128 MiB and more. */
+ *     contiguous batches of 128 MiB and more.  in_off[n] <= in_size, and out_size reaches the slots' end (decode
+ *     floor(8 * in_off[n] / 5), encode in_off[n]): anything else is HHUFF_EINVAL before any device work (3d's host
+ *     mode likewise).  Only bytes of `out` inside the batch's slot range are written. */
 int hhuff_decode_batch_host_pipelined(const uint8_t *in, uint64_t in_size, const uint32_t *in_off, uint32_t n,
                                       const uint32_t *is_name_bits, uint8_t *out, uint64_t out_size,
                                       uint32_t *out_len, uint8_t *status, int device, uint64_t chunk_bytes);

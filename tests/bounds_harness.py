@@ -2,7 +2,7 @@
 no GPU.  A batch call gets `out`, `out_len` and `status` of exactly the documented size, each between two guard
 zones filled with a sentinel; every input byte that belongs to no string holds a fill pattern.  check() compares a
 result with the oracle's and asserts that nothing outside the call's footprint -- the bytes include/hhuff.h lets
-it write -- changed.
+it write -- changed.  Arena carves such buffers out of one host array (a pinned tensor's: the guards are pinned too).
 
 Every case runs twice (RUNS): input fill 0x00 with output sentinel 0xA5, then 0xFF with 0x5A.  0xFF behind a
 Huffman string reads as padding / EOS and 0x00 as further symbols, so a kernel that looks a byte too far
@@ -36,6 +36,36 @@ def guarded(xp, nbytes, fill, guard=GUARD):
         whole = xp.full((total,), fill, dtype=xp.uint8, device="cuda")
         assert (whole.data_ptr() + guard) % 16 == 0
     return whole, whole[guard:guard + nbytes]
+
+
+class Arena:
+    """Guarded buffers carved out of one host array, for pinned memory: `buf` is the numpy view of a uint8 tensor
+    made with pin_memory=True, so a buffer's guards are pinned too (and one allocation serves a whole test).
+    guarded(nbytes, fill, offset) -> (whole, inner) as guarded(); inner starts `offset` bytes past a multiple of 16."""
+
+    def __init__(self, buf):
+        assert buf.dtype == np.uint8 and buf.ndim == 1 and buf.flags["C_CONTIGUOUS"]
+        self.buf, self.pos = buf, 0
+
+    def reset(self):
+        self.pos = 0
+
+    def guarded(self, nbytes, fill, offset=0, guard=GUARD):
+        assert guard % 16 == 0 and nbytes >= 0 and 0 <= offset < 16
+        start = self.pos + (offset - (self.buf.ctypes.data + self.pos + guard)) % 16
+        total = 2 * guard + nbytes
+        assert start + total <= self.buf.size, "arena of %d bytes exhausted" % self.buf.size
+        whole = self.buf[start:start + total]
+        whole[:] = fill
+        self.pos = start + total
+        assert (whole.ctypes.data + guard) % 16 == offset
+        return whole, whole[guard:guard + nbytes]
+
+    def copy(self, whole_np, offset=0, guard=GUARD):
+        """a guarded numpy buffer copied into the arena with its guards"""
+        whole, inner = self.guarded(whole_np.size - 2 * guard, 0, offset, guard)
+        whole[:] = whole_np
+        return whole, inner
 
 
 def to_device(torch, whole_np, guard=GUARD):
