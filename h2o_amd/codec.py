@@ -219,6 +219,9 @@ def lib():
         L.hhuff_h2_deframe.restype = ctypes.c_int
         L.hhuff_h2_deframe.argtypes = ([_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp] + [ctypes.c_uint32] * 3 +
                                        [ctypes.c_uint] + [_vp] * 11 + [ctypes.c_uint64, ctypes.c_uint32, _vp])
+        L.hhuff_h3_deframe.restype = ctypes.c_int
+        L.hhuff_h3_deframe.argtypes = ([_vp, ctypes.c_uint64] + [_vp, ctypes.c_uint32] * 3 + [ctypes.c_uint64, ctypes.c_uint] +
+                                       [_vp] * 19 + [ctypes.c_uint64, ctypes.c_uint32, _vp])
         _lib = L
     return _lib
 
@@ -241,7 +244,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_qpack_parse_responses_sessions", "hhuff_qpack_dsession_state_size",
             "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
             "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers", "hhuff_tokens_table_size", "hhuff_tokens_build",
-            "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe") + SLOTS_SYMBOLS
+            "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
+            "hhuff_h3_deframe") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -968,6 +972,62 @@ def h2_deframe(data, in_off, frm_first, frm_cap, max_frame_size=16384, max_block
                                   _dp(r["cstatus"]), _dp(r["cerr"]), _dp(r["blk"]), _dp(r["blk_off"]), _dp(r["conn_first"]),
                                   _dp(r["blocks"]), _dp(r["totals"]), _dp(r.get("arena_off")), arena_fixed or 0,
                                   arena_per_byte, _stream(stream)), "hhuff_h2_deframe")
+    return r
+
+
+# include/hhuff.h (2l): hhuff_h3_stream_t / hhuff_h3_frame_t / hhuff_h3_settings_t as numpy records (peers: QPACK_PEER), and
+# the section's constants
+H3_STREAM_DTYPE = np.dtype([("stream_id", "<u8"), ("data_left", "<u8"), ("kind", "u1"), ("phase", "u1"), ("flags", "u1"),
+                            ("rsv", "u1", (13,))])
+H3_FRAME_DTYPE = np.dtype([("type", "<u8"), ("hdr_off", "<u4"), ("payload_off", "<u4"), ("length", "<u8"), ("avail", "<u4"),
+                           ("aux", "<u4")])
+H3_SETTINGS_DTYPE = np.dtype([("max_field_section_size", "<u8"), ("h3_datagram", "<u4"), ("rsv", "<u4")])
+H3F_CLIENT = 1
+H3F_REJECTED, H3F_FRAMES, H3F_EINVAL = -320, -321, -322
+H3_GENERAL_PROTOCOL, H3_FRAME_UNEXPECTED, H3_FRAME, H3_EXCESSIVE_LOAD = 0x30101, 0x30105, 0x30106, 0x30107
+(H3F_ERR_NONE, H3F_ERR_FRAME_TOO_LARGE, H3F_ERR_UNEXPECTED_TYPE, H3F_ERR_DATA_BEFORE_HEADERS, H3F_ERR_RESPONSE_TOO_LARGE,
+ H3F_ERR_MALFORMED_SETTINGS, H3F_ERR_INVALID_PRIORITY, H3F_ERR_INVALID_GOAWAY) = range(8)
+H3K_REQUEST, H3K_UNI, H3K_CONTROL, H3K_QPACK_ENCODER, H3K_QPACK_DECODER, H3K_DISCARD = range(6)
+H3P_HEADERS, H3P_DATA, H3P_DATA_PAYLOAD, H3P_POST_TRAILERS = range(4)
+H3P_SETTINGS, H3P_OPEN = 0, 1
+H3S_WALK_ON, H3S_TUNNEL, H3S_PEER_DATAGRAMS = 1, 2, 4
+
+
+def h3_deframe(data, str_off, conn_str, frm_first, frm_cap, st_in, max_frame_payload_size=16384, flags=0, in_size=None,
+               arena_fixed=None, arena_per_byte=0, stream=None, out=None):
+    """HTTP/3 de-framer (include/hhuff.h hhuff_h3_deframe) on device tensors: data uint8, str_off / frm_first int32 (u32
+    bits) of nstr + 1 entries, conn_str of nconn + 1, frm_cap = frm_first[-1] as a host int, st_in uint8 (H3_STREAM_DTYPE
+    records, 32 bytes a stream).  Returns a dict of device tensors: st_out (out={"st_out": st_in} updates in place),
+    frames (uint8, H3_FRAME_DTYPE records), nframes, consumed, sstatus, serr (per stream), out, enc_off, enc_len,
+    conn_first (per connection), sec_off [nstr + 1], sec_stream_id (int64) and sec_stream [nstr], totals [3], peers
+    (uint8, QPACK_PEER), settings (uint8, H3_SETTINGS_DTYPE), got_settings and, with arena_fixed given, arena_off
+    (int64 [nstr + 1]).  out, enc_off, enc_len, sec_off, conn_first and sec_stream_id go to qpack_decode as they are
+    (in_size = out.numel()).  out: a dict with some of these tensors preallocated -- a persistent peers array among
+    them.  No host synchronisation."""
+    import torch
+
+    dev = data.device
+    in_size = data.numel() if in_size is None else in_size
+    nstr, nconn = str_off.numel() - 1, conn_str.numel() - 1
+    out = dict(out or {})
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32, u8 = torch.int32, torch.uint8
+    r = dict(st_out=new("st_out", nstr * 32, u8), frames=new("frames", frm_cap * 32, u8), nframes=new("nframes", nstr, i32),
+             consumed=new("consumed", nstr, i32), sstatus=new("sstatus", nstr, i32), serr=new("serr", nstr, i32),
+             out=new("out", in_size, u8), enc_off=new("enc_off", nconn, i32), enc_len=new("enc_len", nconn, i32),
+             sec_off=new("sec_off", nstr + 1, i32), conn_first=new("conn_first", nconn + 1, i32),
+             sec_stream_id=new("sec_stream_id", nstr, torch.int64), sec_stream=new("sec_stream", nstr, i32),
+             totals=new("totals", 3, i32), peers=new("peers", nconn * 8, u8), settings=new("settings", nconn * 16, u8),
+             got_settings=new("got_settings", nconn, i32))
+    if arena_fixed is not None:
+        r["arena_off"] = new("arena_off", nstr + 1, torch.int64)
+    _check(lib().hhuff_h3_deframe(_dp(data), in_size, _dp(str_off), nstr, _dp(conn_str), nconn, _dp(frm_first), frm_cap,
+                                  max_frame_payload_size, flags, _dp(st_in), _dp(r["st_out"]), _dp(r["frames"]),
+                                  _dp(r["nframes"]), _dp(r["consumed"]), _dp(r["sstatus"]), _dp(r["serr"]), _dp(r["out"]),
+                                  _dp(r["enc_off"]), _dp(r["enc_len"]), _dp(r["sec_off"]), _dp(r["conn_first"]),
+                                  _dp(r["sec_stream_id"]), _dp(r["sec_stream"]), _dp(r["totals"]), _dp(r["peers"]),
+                                  _dp(r["settings"]), _dp(r["got_settings"]), _dp(r.get("arena_off")), arena_fixed or 0,
+                                  arena_per_byte, _stream(stream)), "hhuff_h3_deframe")
     return r
 
 

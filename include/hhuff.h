@@ -1218,6 +1218,191 @@ int hhuff_h2_deframe(const uint8_t *in, uint64_t in_size,            /* in_size 
                      uint32_t *totals /* [2]: nblk, block bytes */,
                      uint64_t *arena_off, uint64_t arena_fixed, uint32_t arena_per_byte, void *stream);
 
+/* (2l) HTTP/3 frames on the receive side: the bytes of many connections' QUIC streams -> the encoder-stream bytes
+ *      and field sections the decoders of (2d) take, and the peers' SETTINGS.  One call is one step of every stream.
+ *      It follows h2o_http3_read_frame (lib/http3/common.c:1057-1145), the request-stream handlers of h2o's server
+ *      (lib/http3/server.c:1367-1453, 1499-1536) and client (lib/common/http3client.c:438-540),
+ *      unknown_type_handle_input and control_stream_handle_input (common.c:365-439),
+ *      h2o_http3_handle_settings_frame (common.c:1422-1473) and h2o_http3_decode_priority_update_frame /
+ *      h2o_http3_decode_goaway_frame (lib/http3/frame.c:40-98).
+ *        stream s       in[str_off[s] .. str_off[s+1]): the bytes the previous step did not consume, then the new
+ *                       ones; its state st_in[s]; frame slots frm_first[s] .. frm_first[s+1] - 1 of `frames`
+ *                       (frm_first[nstr] = frm_cap, host copy)
+ *        connection c   owns streams conn_str[c] .. conn_str[c+1] - 1 (conn_str[nconn] = nstr)
+ *        max_frame_payload_size   h2o's conn->max_frame_payload_size
+ *        flags          HHUFF_H3F_CLIENT: is_client of read_frame's table, and the client's handlers
+ *      Per stream: st_out[s] the state to present next time (st_out may be st_in), nframes[s], consumed[s] (relative
+ *      to str_off[s]; the caller keeps in[str_off[s] + consumed[s] ..) and presents it again in front of the next
+ *      bytes), sstatus[s] = 0, h2o's return value as it is (0x30000 + code, as HHUFF_QPK_DECOMPRESSION_FAILED) or
+ *      HHUFF_H3F_REJECTED / _FRAMES / _EINVAL, serr[s] = the HHUFF_H3F_ERR_* that names h2o's err_desc.
+ *        frames         frames[frm_first[s] + i], i < nframes[s]: the frames walked, in wire order; the other slots
+ *                       are not written.  The body bytes that continue a DATA frame begun in an earlier step get a
+ *                       record with hdr_off == payload_off, length = the data_left presented and avail = the bytes
+ *                       taken.
+ *        out            in_size bytes.  First the connections' QPACK encoder-stream bytes in connection order:
+ *                       out[enc_off[c] .. + enc_len[c]), the bytes of several _QPACK_ENCODER streams of one connection
+ *                       joined in stream order.  Behind them the field sections packed back to back, in stream
+ *                       order: section k = out[sec_off[k] .. sec_off[k+1]), connection c's sections conn_first[c] ..
+ *                       conn_first[c+1] - 1.  A stream yields at most one section a call (rules 3 and 6), so sec_off
+ *                       has nstr + 1 entries -- those past nsec all hold the end, so they read as empty sections --,
+ *                       conn_first nconn + 1, and sec_stream_id[k] (the stream's stream_id) and sec_stream[k] (its
+ *                       index in this call) are written for k < nsec.
+ *        totals         [0] = nsec, [1] = the section bytes, [2] = the encoder bytes
+ *        arena_off      NULL, or nstr + 1 u64: the running sum of arena_fixed + arena_per_byte * (section length)
+ *                       over the sections before k (entries past nsec hold the total)
+ *      out, enc_off, enc_len, sec_off, conn_first, sec_stream_id and nconn are, as they are and on the same stream,
+ *      the in, enc_off, enc_len, sec_off, conn_first, stream_id and nconn of hhuff_qpack_decode, _parse_requests,
+ *      _parse_responses and their _slots and _sessions variants, with this call's in_size.  Their host copy of nsec
+ *      is totals[0]; a caller that does not read it back may pass nstr to hhuff_qpack_decode, _parse_requests and
+ *      _parse_responses: the sections past conn_first[nconn] are empty, lie in no connection's range, and get a
+ *      status nobody reads (the per-section arrays then need nstr entries).
+ *        peers, settings, got_settings   got_settings[c] = 1 when a control stream of connection c passed its
+ *                       SETTINGS frame in this call, else 0.  Only then are peers[c] (the raw
+ *                       SETTINGS_QPACK_MAX_TABLE_CAPACITY and _BLOCKED_STREAMS, 0 when absent, saturated at
+ *                       2^32 - 1) and settings[c] written, so a persistent peers array fills as connections arrive
+ *                       and goes to hhuff_qpack_flatten_sessions_peers unchanged.  h2o's clamp to its own
+ *                       encoder_table_capacity is the min(capacity, header_table_size) that call makes.  A repeated
+ *                       setting id takes the last value, as h2o's loop does.  Of several control streams of one
+ *                       connection that pass SETTINGS in one call (h2o has one) the first in stream order is taken.
+ *      The call keeps no state.  Streams do not affect one another, although h2o closes the connection on most of
+ *      the errors below: what to do with a failed connection's other sections is the caller's decision.  Per stream
+ *      the bytes are walked by these rules, in h2o's order.  The first failing rule stops that stream's walk:
+ *      the failing frame is neither listed nor consumed, and what was completed before stands.
+ *      Request streams (kind _REQUEST):
+ *      1. h2o_http3_read_frame: a type varint cut short: sstatus 0 (h2o: H2O_HTTP3_ERROR_INCOMPLETE, wait); a length
+ *         varint cut short: 0; for any type but DATA, length > max_frame_payload_size: 0x30101
+ *         (H2O_HTTP3_ERROR_GENERAL_PROTOCOL, _ERR_FRAME_TOO_LARGE), decided before completeness; then the payload cut
+ *         short: 0; then the type table (common.c:1124-1132) for the side and the stream kind: 0x30105
+ *         (H2O_HTTP3_ERROR_FRAME_UNEXPECTED).  Unknown types pass.  A DATA frame needs only its header.  Varints of
+ *         every width are read as ptls_decode_quicint reads them, non-minimal encodings included.
+ *      2. Server, phase _HEADERS (server.c:1499-1536): a too-large HEADERS frame is HHUFF_H3F_REJECTED (h2o resets the
+ *         stream with REQUEST_REJECTED and returns 0; serr stays _ERR_FRAME_TOO_LARGE); every other read_frame error
+ *         is returned as it is; DATA is 0x30105; other types are listed and stepped over.
+ *      3. Server, a HEADERS frame in _HEADERS: it becomes the stream's section (aux = its index k), st_out.phase =
+ *         _DATA, and the walk stops behind the frame: what follows depends on the decoder's verdict, which this call
+ *         cannot know.  With HHUFF_H3S_WALK_ON it goes on as if the section had decoded.  A caller whose section
+ *         comes back HHUFF_QPK_BLOCKED keeps the stream from the record's hdr_off with st_in, as h2o's *src =
+ *         frame_start does (server.c:1555).
+ *      4. Server, phase _DATA (server.c:1411-1453): HEADERS under HHUFF_H3S_TUNNEL is 0x30105 with
+ *         _ERR_UNEXPECTED_TYPE; otherwise it is trailers: listed with aux = ~0u, no section, phase _POST_TRAILERS.
+ *         DATA of non-zero length opens _DATA_PAYLOAD with data_left = length, and the bytes present are taken at
+ *         once (avail of them; data_left falls, and at 0 the phase is _DATA again); DATA of length 0 is listed and
+ *         the phase stays.  Other types are listed and stepped over.
+ *      5. Server, phase _POST_TRAILERS (server.c:1367-1386): HEADERS and DATA are 0x30105.
+ *      6. Client, phase _HEADERS (http3client.c:506-540): any read_frame error but incomplete is 0x30107
+ *         (H2O_HTTP3_ERROR_EXCESSIVE_LOAD) with _ERR_RESPONSE_TOO_LARGE; DATA is 0x30105 with
+ *         _ERR_DATA_BEFORE_HEADERS; HEADERS is the section and the walk stops, or goes on under _WALK_ON.  A 1xx
+ *         answer is the caller's to see: it then presents _HEADERS again.
+ *      7. Client, phase _DATA (http3client.c:438-504): read_frame errors are returned as they are; HEADERS under
+ *         _TUNNEL is 0x30105 (no err_desc), else it is listed with aux = ~0u and ignored -- the client has no
+ *         post-trailers phase, and a client state record with _POST_TRAILERS is HHUFF_H3F_EINVAL --; PUSH_PROMISE
+ *         and unknown types are listed and ignored; DATA as in rule 4.  For a DATA frame of length 0
+ *         handle_input_expect_data_frame sets bytes_left_in_data_frame = 0 and enters handle_input_data_payload,
+ *         which appends nothing, sets the handler back to expect_data_frame at once and calls on_body without
+ *         bytes: the frame is listed with avail 0 and the phase stays _DATA, as on the server.
+ *      Unidirectional streams:
+ *      8. _UNI (common.c:403-439): the type varint cut short: wait, nothing consumed; 0: _CONTROL at _SETTINGS; 2:
+ *         _QPACK_ENCODER; 3: _QPACK_DECODER; anything else (push streams included): _DISCARD -- h2o sends STOP_SENDING
+ *         with STREAM_CREATION; the caller sees the kind change.  The same call goes on with the new kind.
+ *      9. _QPACK_ENCODER: every byte is gathered and consumed.  The decoder's enc_consumed[c] then tells the caller
+ *         what to present again.
+ *      10. _QPACK_DECODER: nothing (but the type varint of rule 8) is consumed: those bytes are
+ *         hhuff_qpack_flatten_sessions' dec_off / dec_len.
+ *      11. _DISCARD: everything is consumed.
+ *      Control streams (kind _CONTROL):
+ *      12. Per frame read_frame (rule 1 with the control column); then common.c:384-388: has_received_settings ==
+ *         (type == SETTINGS), or DATA, is 0x30105 without err_desc -- in phase _SETTINGS any other first frame, in
+ *         _OPEN a second SETTINGS.  That test fires before server.c:1910 can say MISSING_SETTINGS (0x3010a), so h2o
+ *         never reports that code, and neither does this call.
+ *      13. Then the handler (server.c:1903-1948, http3client.c:339-376): SETTINGS by
+ *         h2o_http3_handle_settings_frame -- a varint cut short, a datagram value (ids 0x33, 0x276) other than 0 or
+ *         1, or 1 without HHUFF_H3S_PEER_DATAGRAMS is 0x30106 (H2O_HTTP3_ERROR_FRAME, _ERR_MALFORMED_SETTINGS) --,
+ *         then phase _OPEN.  On the server PRIORITY_UPDATE (0xF0700, 0xF0701) by
+ *         h2o_http3_decode_priority_update_frame: an empty payload or an element id of the wrong kind is 0x30106
+ *         without err_desc; aux = the id's bytes (the priority field value follows them).  An id cut short is what
+ *         h2o makes of it: frame.c:49 stores the decoder's UINT64_MAX in the 63-bit field `element` before comparing,
+ *         so "invalid PRIORITY frame" is never said (HHUFF_H3F_ERR_INVALID_PRIORITY names it and is never reported)
+ *         and the id reads as 2^63 - 1, a server-initiated unidirectional stream: 0x30106 for 0xF0700, and for
+ *         0xF0701 the frame passes with aux = 1, the byte ptls_decode_quicint had taken.  On the client GOAWAY by h2o_http3_decode_goaway_frame: a cut
+ *         varint or bytes behind it are 0x30106 with _ERR_INVALID_GOAWAY; aux = the id's bytes.  Everything else
+ *         (the server's GOAWAY, CANCEL_PUSH and MAX_PUSH_ID included) is listed with aux 0 and stepped over.
+ *      All streams:
+ *      14. A frame that passed its rules and finds no frame slot left: HHUFF_H3F_FRAMES, at that frame's boundary.
+ *      HHUFF_H3F_EINVAL reports a state record with an unknown kind, phase or flag bit, a non-zero reserved byte,
+ *      a non-zero phase on a kind that has none, data_left != 0 outside _DATA_PAYLOAD or _DATA_PAYLOAD with
+ *      data_left == 0: nothing is consumed and st_out[s] = st_in[s].
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array (arena_off may be NULL),
+ *      in_size > 2^32 - 3 or an unknown flag bit; nstr == 0 or nconn == 0 returns HHUFF_OK.  Asynchronous on
+ *      `stream`, no atomics, no host synchronisation and no copy to the host; bitwise deterministic.  Stream-ordered
+ *      pool workspace of 65 bytes per stream and 16 per 256 of them (hhuff_pool_trim).  A stream's range is clamped to in_size, its slots
+ *      to frm_cap and a connection's streams to nstr.  Of `in` the call reads the streams' bytes and, with them, the
+ *      aligned dwords (by address) that hold a section's or an encoder run's bytes, as (2k) does. */
+typedef struct hhuff_h3_stream {     /* 32 bytes: one stream's state between steps */
+    uint64_t stream_id;              /* the QUIC stream id (goes to sec_stream_id) */
+    uint64_t data_left;              /* _DATA_PAYLOAD: the bytes of the open DATA frame still to come; else 0 */
+    uint8_t  kind, phase, flags;     /* HHUFF_H3K_*, HHUFF_H3P_*, HHUFF_H3S_* */
+    uint8_t  rsv[13];                /* 0 */
+} hhuff_h3_stream_t;
+typedef struct hhuff_h3_frame {      /* 32 bytes: one per frame walked */
+    uint64_t type;
+    uint32_t hdr_off, payload_off;   /* offsets in `in`: the type varint, the payload */
+    uint64_t length;                 /* the frame's length field */
+    uint32_t avail;                  /* the payload bytes present: length, except for DATA */
+    uint32_t aux;                    /* HEADERS: the section index, ~0u when it is no section; PRIORITY_UPDATE
+                                        (server) and GOAWAY (client): the bytes of the leading id varint; else 0 */
+} hhuff_h3_frame_t;
+typedef struct hhuff_h3_settings {   /* 16 bytes: what SETTINGS says beside the QPACK values */
+    uint64_t max_field_section_size; /* SETTINGS_MAX_FIELD_SECTION_SIZE; UINT64_MAX when the frame has none */
+    uint32_t h3_datagram;            /* 1: the peer enabled HTTP/3 datagrams */
+    uint32_t rsv;
+} hhuff_h3_settings_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h3_stream_t) == 32 && sizeof(hhuff_h3_frame_t) == 32 && sizeof(hhuff_h3_settings_t) == 16, "record sizes");
+#else
+typedef char hhuff_h3_records_are_32_bytes[sizeof(hhuff_h3_stream_t) == 32 && sizeof(hhuff_h3_frame_t) == 32 &&
+                                           sizeof(hhuff_h3_settings_t) == 16 ? 1 : -1];
+#endif
+#define HHUFF_H3F_CLIENT 1u           /* flags: the receiving side is h2o's client */
+#define HHUFF_H3F_REJECTED (-320)     /* sstatus: a too-large HEADERS frame in _HEADERS on the server */
+#define HHUFF_H3F_FRAMES (-321)       /* sstatus: out of frame slots */
+#define HHUFF_H3F_EINVAL (-322)       /* sstatus: the state record is not one this call writes */
+#define HHUFF_H3F_ERR_NONE 0u               /* *err_desc untouched */
+#define HHUFF_H3F_ERR_FRAME_TOO_LARGE 1u    /* h2o_http3_err_frame_too_large */
+#define HHUFF_H3F_ERR_UNEXPECTED_TYPE 2u    /* "unexpected frame type" */
+#define HHUFF_H3F_ERR_DATA_BEFORE_HEADERS 3u /* "received DATA frame before HEADERS" */
+#define HHUFF_H3F_ERR_RESPONSE_TOO_LARGE 4u /* "response header too large" */
+#define HHUFF_H3F_ERR_MALFORMED_SETTINGS 5u /* "malformed SETTINGS frame" */
+#define HHUFF_H3F_ERR_INVALID_PRIORITY 6u   /* "invalid PRIORITY frame": h2o never says it (rule 13) */
+#define HHUFF_H3F_ERR_INVALID_GOAWAY 7u     /* "Invalid GOAWAY frame" */
+#define HHUFF_H3K_REQUEST 0u
+#define HHUFF_H3K_UNI 1u              /* a unidirectional stream whose type varint has not been read */
+#define HHUFF_H3K_CONTROL 2u
+#define HHUFF_H3K_QPACK_ENCODER 3u
+#define HHUFF_H3K_QPACK_DECODER 4u
+#define HHUFF_H3K_DISCARD 5u
+#define HHUFF_H3P_HEADERS 0u          /* request streams */
+#define HHUFF_H3P_DATA 1u
+#define HHUFF_H3P_DATA_PAYLOAD 2u
+#define HHUFF_H3P_POST_TRAILERS 3u
+#define HHUFF_H3P_SETTINGS 0u         /* control streams */
+#define HHUFF_H3P_OPEN 1u
+#define HHUFF_H3S_WALK_ON 1u          /* go on behind the section as if it had decoded */
+#define HHUFF_H3S_TUNNEL 2u           /* server: req.is_tunnel_req; client: upgrade_to != NULL */
+#define HHUFF_H3S_PEER_DATAGRAMS 4u   /* the remote transport parameter max_datagram_frame_size != 0 */
+int hhuff_h3_deframe(const uint8_t *in, uint64_t in_size,            /* in_size <= 2^32 - 3 */
+                     const uint32_t *str_off, uint32_t nstr,         /* stream s: in[str_off[s] .. str_off[s+1]) */
+                     const uint32_t *conn_str, uint32_t nconn,       /* connection c: streams conn_str[c] .. conn_str[c+1] */
+                     const uint32_t *frm_first, uint32_t frm_cap,    /* frame slots; frm_cap = frm_first[nstr] (host copy) */
+                     uint64_t max_frame_payload_size, unsigned flags,
+                     const hhuff_h3_stream_t *st_in, hhuff_h3_stream_t *st_out,
+                     hhuff_h3_frame_t *frames, uint32_t *nframes, uint32_t *consumed,
+                     int32_t *sstatus, uint32_t *serr,
+                     uint8_t *out, uint32_t *enc_off, uint32_t *enc_len, uint32_t *sec_off, uint32_t *conn_first,
+                     uint64_t *sec_stream_id, uint32_t *sec_stream,
+                     uint32_t *totals /* [3]: nsec, section bytes, encoder bytes */,
+                     hhuff_qpack_peer_t *peers, hhuff_h3_settings_t *settings, uint32_t *got_settings,
+                     uint64_t *arena_off, uint64_t arena_fixed, uint32_t arena_per_byte, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
