@@ -23,19 +23,16 @@
 
 #include "hhuff_decwork.h"
 #include "hhuff_device.h"
+#include "hhuff_devtables.h"
 #include "hhuff_image.h"
 #include "hhuff.h"
+#include "hhuff_int.h"
 #include "hhuff_launch.h"
 #include "hhuff_request.h"
 #include "hhuff_slots.h"
 
 namespace hhuff {
 namespace {
-__device__ const uint32_t b_dec_lut[1u << HHUFF_LUT_BITS] = HHUFF_DEC_LUT_INIT;
-__device__ const uint32_t b_kinfo[31] = HHUFF_ONES_KINFO_INIT;
-__device__ const uint32_t b_ones[HHUFF_ONES_NENT] = HHUFF_ONES_ENT_INIT;
-__device__ const uint32_t b_name_invalid[8] = HHUFF_NAME_INVALID_INIT;
-__device__ const uint32_t b_value_invalid[8] = HHUFF_VALUE_INVALID_INIT;
 __device__ const uint8_t b_static_bytes[HHUFF_STATIC_NBYTES] = HHUFF_STATIC_BYTES_INIT;
 __device__ const uint16_t b_static_ent[61 * 4] = HHUFF_STATIC_ENT_INIT;
 
@@ -45,7 +42,6 @@ constexpr int32_t kErrInvalidChar = -254;   // H2O_HTTP2_ERROR_INVALID_HEADER_CH
 constexpr int32_t kBlkArena = HHUFF_BLK_ARENA;
 constexpr int32_t kBlkSkipped = HHUFF_BLK_SKIPPED;
 constexpr uint32_t kEntryOverhead = 32;  // HEADER_TABLE_ENTRY_SIZE_OFFSET (hpack.c:30)
-constexpr int64_t kIntIncomplete = -255, kIntBad = -9;
 constexpr uint32_t kLitHuffmanV = 4, kLitUpperV = 5;  // HHUFF_LIT_HUFFMAN / _UPPERCASE verdicts
 constexpr uint32_t kClsUnknown = 0xFFFFu;  // a table entry's name class not computed yet
 }  // namespace
@@ -127,25 +123,6 @@ struct WinSource {  // decode_core's source interface over a Win
     __device__ __forceinline__ uint32_t word(uint32_t a) const { return w->word(a); }
 };
 
-// h2o_hpack_decode_int (hpack.c:52-83) at position p, bounded by end
-__device__ int64_t blk_decode_int(const Win& in, uint64_t& p, uint64_t end, uint32_t prefix_bits) {
-    if (p >= end) return kIntIncomplete;
-    const uint64_t pmax = (1u << prefix_bits) - 1u;
-    uint64_t v = in.byte(p++) & pmax;
-    if (v != pmax) return (int64_t)v;
-    uint32_t shift = 0;
-    for (; shift < 56; shift += 7) {
-        if (p == end) return kIntIncomplete;
-        const uint32_t b = in.byte(p++);
-        v += (uint64_t)(b & 127u) << shift;
-        if (!(b & 128u)) return (int64_t)v;
-    }
-    if (p == end) return kIntIncomplete;
-    if (in.byte(p) & 128u) return kIntBad;
-    v += (uint64_t)(in.byte(p++) & 127u) << shift;
-    if (v > 0x7FFFFFFFFFFFFFFFull) return kIntBad;
-    return (int64_t)v;
-}
 struct DynTable {  // one connection's dynamic table (newest entry = dynamic index 62)
     Entry* ent;
     uint32_t E, start, num;
@@ -189,7 +166,7 @@ __device__ int blk_string(const BlkArgs& A, const Win& W, uint64_t& p, uint64_t 
             const uint32_t ln = A.lit_len[r];
             const bool huff = (W.byte(p) & 0x80u) != 0;
             uint64_t q = p;
-            const uint64_t n = (uint64_t)blk_decode_int(W, q, end, 7);  // fits: the parse pass checked it
+            const uint64_t n = (uint64_t)hpack_int(W.in, q, end, 7);  // fits: the parse pass checked it
             // decode_string's order: Huffman -- arena room, then the decoder's verdict; raw -- the name
             // validator's verdict, then arena room
             if (huff) {
@@ -210,32 +187,17 @@ __device__ int blk_string(const BlkArgs& A, const Win& W, uint64_t& p, uint64_t 
         // unmarked, or another verdict (a payload past the library's length limit): decode in place below
     }
     const bool huff = (W.byte(p) & 0x80u) != 0;
-    const int64_t n = blk_decode_int(W, p, end, 7);
+    const int64_t n = hpack_int(W.in, p, end, 7);
     if (n < 0 || (uint64_t)n > end - p) return kStrFail;
     if (huff) {
         if (cur + ((uint64_t)n * 8u) / 5u > aend) return kStrArena;
         if ((uint64_t)n > kMaxStrLen) return kStrFail;
-        RegSink sink;
-        sink.init(A.arena + cur);
-        // decode with first / last byte tracking (soft bits need them, hpack.c:136-152)
-        struct SinkFL {
-            RegSink s;
-            uint32_t first, last;
-            __device__ __forceinline__ void put1(uint32_t b) {
-                first = s.cnt == 0 ? (b & 0xFFu) : first;
-                last = b & 0xFFu;
-                s.put1(b);
-            }
-            __device__ __forceinline__ void put12(uint32_t syms, bool two) {
-                first = s.cnt == 0 ? (syms & 0xFFu) : first;
-                last = (two ? (syms >> 8) : syms) & 0xFFu;
-                s.put12(syms, two);
-            }
-            __device__ __forceinline__ uint32_t count() const { return s.count(); }
-        } fl{sink, 0u, 0u};
+        RegSinkFL fl;  // first / last byte tracked: the soft bits need them (hpack.c:136-152)
+        fl.init(A.arena + cur);
+        fl.first = fl.last = 0;
         const DecResult r = decode_core(WinSource{&W}, (uint32_t)p, (uint32_t)n, fl, T);
         if (!r.ok) return kStrFail;
-        fl.s.finish();
+        fl.finish();
         soft |= soft_bits(is_name, r.len, r.flags, fl.first, fl.last);
         len = r.len;
     } else {
@@ -258,14 +220,14 @@ __device__ int blk_string(const BlkArgs& A, const Win& W, uint64_t& p, uint64_t 
                [&](uint32_t i, uint8_t v) {
                    const uint32_t c = v;
                    if (is_name) {
-                       if (check_name && ((b_name_invalid[c >> 5] >> (c & 31)) & 1u)) {
+                       if (check_name && ((g_name_invalid[c >> 5] >> (c & 31)) & 1u)) {
                            if (c - 'A' < 26u)
                                upper = true;
                            else
                                bad = true;
                        }
                    } else {
-                       bad |= ((b_value_invalid[c >> 5] >> (c & 31)) & 1u) != 0;
+                       bad |= ((g_value_invalid[c >> 5] >> (c & 31)) & 1u) != 0;
                    }
                    dst[i] = v;
                },
@@ -302,21 +264,21 @@ __device__ int32_t blk_field(const BlkArgs& A, const Win& W, DynTable& t, uint64
         if (p >= end) return kErrCompression;
         const uint32_t b = W.byte(p);
         if (b >= 128) {  // indexed header field
-            if ((index = blk_decode_int(W, p, end, 7)) <= 0) return kErrCompression;
+            if ((index = hpack_int(W.in, p, end, 7)) <= 0) return kErrCompression;
             value_indexed = true;
         } else if (b >= 64) {  // literal with incremental indexing
             if (b == 64)
                 ++p;
-            else if ((index = blk_decode_int(W, p, end, 6)) <= 0)
+            else if ((index = hpack_int(W.in, p, end, 6)) <= 0)
                 return kErrCompression;
             do_index = true;
         } else if (b < 32) {  // literal without indexing / never indexed
             if ((b & 0xFu) == 0)
                 ++p;
-            else if ((index = blk_decode_int(W, p, end, 4)) <= 0)
+            else if ((index = hpack_int(W.in, p, end, 4)) <= 0)
                 return kErrCompression;
         } else {  // dynamic table size update
-            const int64_t c = blk_decode_int(W, p, end, 5);
+            const int64_t c = hpack_int(W.in, p, end, 5);
             if (c < 0 || (uint64_t)c > t.maxcap) return kErrCompression;
             t.cap = (uint64_t)c;
             while (t.num != 0 && t.size > t.cap) t.evict_one();
@@ -389,10 +351,7 @@ __global__ __launch_bounds__(kBlkThreads) void hpack_walk_kernel(BlkArgs A) {
     __shared__ uint16_t s_sent[61 * 4];
     __shared__ uint16_t s_scls[61];  // the static names' classes for the request rules
     for (uint32_t k = threadIdx.x; k < 61 * 4; k += blockDim.x) s_sent[k] = b_static_ent[k];
-    for (uint32_t k = threadIdx.x; k < (1u << HHUFF_LUT_BITS) / 4; k += blockDim.x)
-        reinterpret_cast<uint4*>(s_lut)[k] = reinterpret_cast<const uint4*>(b_dec_lut)[k];
-    for (uint32_t k = threadIdx.x; k < HHUFF_ONES_NENT; k += blockDim.x) s_ones[k] = b_ones[k];
-    if (threadIdx.x < 31) s_kinfo[threadIdx.x] = b_kinfo[threadIdx.x];
+    load_dec_tables(s_lut, s_kinfo, s_ones, blockDim.x);
     if (threadIdx.x < 61)
         s_scls[threadIdx.x] = (uint16_t)req_name_class(b_static_bytes + b_static_ent[4 * threadIdx.x],
                                                        b_static_ent[4 * threadIdx.x + 1]);
@@ -538,25 +497,7 @@ __global__ __launch_bounds__(256) void blk_table_kernel(BlkArgs A) {
     const TableState s = *ts;
     const uint32_t nring = s.ring ^ 1u;
     const uint64_t rbase = base + sizeof(TableState) + (uint64_t)E * sizeof(Entry) + nring * tbl_ring(A.table_size);
-    uint32_t carry = 0;
-    for (uint32_t k0 = 0; k0 < s.num; k0 += 64) {
-        const uint32_t k = k0 + (uint32_t)lane;
-        const bool live = k < s.num;
-        uint32_t i = s.start + k;
-        i = i >= E ? i - E : i;
-        Entry e{};
-        if (live) e = ent[i];
-        const uint32_t sz = live ? e.nl + e.vl : 0u;
-        const uint32_t dst = carry + wave_excl_scan(sz, lane);
-        carry += (uint32_t)__builtin_amdgcn_readlane((int)(dst - carry + sz), 63);
-        uint8_t* d = A.scratch + rbase + dst;
-        wave_copy64(src_ptr(A, e.nsrc), d, live ? e.nl : 0u, lane);
-        wave_copy64(src_ptr(A, e.vsrc), d + e.nl, live ? e.vl : 0u, lane);
-        if (live) {
-            ent[i].nsrc = kSrcScr | (rbase + dst);
-            ent[i].vsrc = kSrcScr | (rbase + dst + e.nl);
-        }
-    }
+    wave_table_pass(A.scratch, ent, E, s.start, s.num, rbase, kSrcScr, lane, [&](uint64_t x) { return src_ptr(A, x); });
     if (lane == 0) ts->ring = nring;
 }
 
@@ -576,7 +517,7 @@ __device__ __forceinline__ bool mark_literal(const Win& W, uint64_t& p, uint64_t
                                              uint32_t* __restrict__ lit_bits, uint32_t* __restrict__ name_bits) {
     if (p >= end) return false;
     uint64_t q = p;
-    const int64_t n = blk_decode_int(W, q, end, 7);
+    const int64_t n = hpack_int(W.in, q, end, 7);
     if (n < 0 || (uint64_t)n > end - q) return false;
     atomicOr(lit_bits + (p >> 5), 1u << (p & 31));
     if (is_name) atomicOr(name_bits + (p >> 5), 1u << (p & 31));
@@ -598,24 +539,24 @@ __global__ __launch_bounds__(kMarkThreads) void blk_mark_kernel(const uint8_t* _
             const uint32_t c = W.byte(p);
             bool name_lit = false;
             if (c >= 128) {
-                if (blk_decode_int(W, p, end, 7) <= 0) break;
+                if (hpack_int(W.in, p, end, 7) <= 0) break;
                 continue;  // indexed: no literal
             } else if (c >= 64) {
                 if (c == 64) {
                     ++p;
                     name_lit = true;
-                } else if (blk_decode_int(W, p, end, 6) <= 0) {
+                } else if (hpack_int(W.in, p, end, 6) <= 0) {
                     break;
                 }
             } else if (c < 32) {
                 if ((c & 0xFu) == 0) {
                     ++p;
                     name_lit = true;
-                } else if (blk_decode_int(W, p, end, 4) <= 0) {
+                } else if (hpack_int(W.in, p, end, 4) <= 0) {
                     break;
                 }
             } else {
-                if (blk_decode_int(W, p, end, 5) < 0) break;
+                if (hpack_int(W.in, p, end, 5) < 0) break;
                 continue;  // table size update
             }
             if (name_lit && !mark_literal(W, p, end, true, lit_bits, name_bits)) break;

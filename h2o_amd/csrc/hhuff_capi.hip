@@ -266,9 +266,8 @@ HHUFF_API int hhuff_hpack_decode_blocks(const uint8_t* in, uint64_t in_size, con
                                         uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
                                         int32_t* bstatus, void* scratch, uint64_t scratch_size, unsigned flags,
                                         void* stream) {
-    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, nullptr, nullptr, nullptr, nullptr};
-    return hpack_blocks(nullptr, call, scratch_size, stream);
+    return hhuff_hpack_decode_blocks_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off,
+        name_len, value_off, value_len, fflags, nfields, bstatus, scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API int hhuff_hpack_parse_requests_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
@@ -290,10 +289,8 @@ HHUFF_API int hhuff_hpack_parse_requests(const uint8_t* in, uint64_t in_size, co
                                          uint32_t* value_off, uint32_t* value_len, uint8_t* fflags, uint32_t* nfields,
                                          int32_t* bstatus, hhuff_request_t* req, void* scratch, uint64_t scratch_size,
                                          unsigned flags, void* stream) {
-    if (nconn != 0 && !req) return arg_fail("NULL array");
-    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, req, nullptr, nullptr, nullptr};
-    return hpack_blocks(nullptr, call, scratch_size, stream);
+    return hhuff_hpack_parse_requests_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off,
+        name_len, value_off, value_len, fflags, nfields, bstatus, req, scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API int hhuff_hpack_parse_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
@@ -315,10 +312,8 @@ HHUFF_API int hhuff_hpack_parse_responses(const uint8_t* in, uint64_t in_size, c
                                           uint32_t* name_off, uint32_t* name_len, uint32_t* value_off, uint32_t* value_len,
                                           uint8_t* fflags, uint32_t* nfields, int32_t* bstatus, hhuff_response_t* res,
                                           void* scratch, uint64_t scratch_size, unsigned flags, void* stream) {
-    if (nconn != 0 && !res) return arg_fail("NULL array");
-    hhuff::HpdCall call{in, in_size, blk_off, conn_first, nconn, table_size, arena, arena_off, name_off, name_len, value_off,
-                        value_len, fflags, nfields, bstatus, (uint8_t*)scratch, flags, nullptr, res, trailers, nullptr};
-    return hpack_blocks(nullptr, call, scratch_size, stream);
+    return hhuff_hpack_parse_responses_slots(nullptr, in, in_size, blk_off, conn_first, nconn, table_size, trailers, arena, arena_off,
+        name_off, name_len, value_off, value_len, fflags, nfields, bstatus, res, scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API uint64_t hhuff_hpack_enc_scratch_size(uint32_t nconn) { return (uint64_t)nconn * hhuff::hpenc_conn_scratch(); }
@@ -639,11 +634,9 @@ HHUFF_API int hhuff_qpack_decode(const uint8_t* in, uint64_t in_size, const uint
                                  int32_t* sstatus, uint64_t* req_insert_count, int32_t* enc_status,
                                  uint32_t* enc_consumed, uint64_t* insert_count, void* scratch, uint64_t scratch_size,
                                  unsigned flags, void* stream) {
-    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
-                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
-                        nullptr, nullptr, nullptr, nullptr};
-    return qpack_step(nullptr, call, false, nullptr, scratch_size, stream);
+    return hhuff_qpack_decode_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec, header_table_size,
+        max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
+        req_insert_count, enc_status, enc_consumed, insert_count, scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_requests_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
@@ -674,13 +667,9 @@ HHUFF_API int hhuff_qpack_parse_requests(const uint8_t* in, uint64_t in_size, co
                                          int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                                          const uint64_t* stream_id, hhuff_qpack_request_t* req, void* scratch,
                                          uint64_t scratch_size, unsigned flags, void* stream) {
-    if (nconn != 0 && nsec != 0 && (!stream_id || !req)) return arg_fail("NULL array");
-    if (((uintptr_t)req & 7u) != 0) return arg_fail("req must be 8-byte aligned");
-    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
-                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
-                        stream_id, req, nullptr, nullptr};
-    return qpack_step(nullptr, call, false, nullptr, scratch_size, stream);
+    return hhuff_qpack_parse_requests_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
+        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields,
+        sstatus, req_insert_count, enc_status, enc_consumed, insert_count, stream_id, req, scratch, scratch_size, flags, stream);
 }
 
 HHUFF_API int hhuff_qpack_parse_responses_slots(const hhuff_conn_slots_t* slots, const uint8_t* in, uint64_t in_size,
@@ -712,13 +701,9 @@ HHUFF_API int hhuff_qpack_parse_responses(const uint8_t* in, uint64_t in_size, c
                                           int32_t* enc_status, uint32_t* enc_consumed, uint64_t* insert_count,
                                           const uint64_t* stream_id, hhuff_qpack_response_head_t* res, void* scratch,
                                           uint64_t scratch_size, unsigned flags, void* stream) {
-    if (nconn != 0 && nsec != 0 && (!stream_id || !res)) return arg_fail("NULL array");
-    if (((uintptr_t)res & 7u) != 0) return arg_fail("res must be 8-byte aligned");
-    hhuff::QpdCall call{in, in_size, enc_off, enc_len, sec_off, conn_first, num_blocked, nconn, nsec, header_table_size,
-                        max_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields, sstatus,
-                        req_insert_count, enc_status, enc_consumed, insert_count, (uint8_t*)scratch, flags,
-                        stream_id, nullptr, res, nullptr};
-    return qpack_step(nullptr, call, false, nullptr, scratch_size, stream);
+    return hhuff_qpack_parse_responses_slots(nullptr, in, in_size, enc_off, enc_len, sec_off, conn_first, nconn, nsec,
+        header_table_size, max_blocked, num_blocked, arena, arena_off, name_off, name_len, value_off, value_len, fflags, nfields,
+        sstatus, req_insert_count, enc_status, enc_consumed, insert_count, stream_id, res, scratch, scratch_size, flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

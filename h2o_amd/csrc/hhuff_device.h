@@ -181,6 +181,22 @@ struct RegSink {
     }
 };
 
+// RegSink that also remembers the first and last byte (the soft bits need them, hpack.c:136-152): the direct
+// decode path and the literals the header-block decoders decode in place.
+struct RegSinkFL : RegSink {
+    uint32_t first, last;
+    __device__ __forceinline__ void put1(uint32_t b) {
+        first = cnt == 0 ? (b & 0xFFu) : first;
+        last = b & 0xFFu;
+        RegSink::put1(b);
+    }
+    __device__ __forceinline__ void put12(uint32_t syms, bool two) {
+        first = cnt == 0 ? (syms & 0xFFu) : first;
+        last = (two ? (syms >> 8) : syms) & 0xFFu;
+        RegSink::put12(syms, two);
+    }
+};
+
 // CountSink: counts the bytes and remembers the first and last one, writes nothing (first pass of the
 // packed-output direct path: the lengths fix every string's place before the second pass writes).
 struct CountSink {
@@ -422,6 +438,34 @@ __device__ __forceinline__ void wave_copy_fields(uint32_t s0, uint32_t nf, int l
     }
 }
 
+// The table pass of a header-block decoder, by one wave: the `num` live entries of a connection's entry ring
+// (ent[E], from `start` on) get their name and value bytes written back to back to scratch + rbase -- the ring
+// they do not use now -- and are pointed there (tag | scratch offset).  Entry has nsrc, vsrc, nl, vl; src(s) is
+// the address of byte source s.  Live bytes never exceed the ring (each entry costs its bytes + 32 of the capacity).
+template <class Entry, class Src>
+__device__ __forceinline__ void wave_table_pass(uint8_t* scratch, Entry* ent, uint32_t E, uint32_t start, uint32_t num,
+                                                uint64_t rbase, uint64_t tag, int lane, Src src) {
+    uint32_t carry = 0;
+    for (uint32_t k0 = 0; k0 < num; k0 += 64) {
+        const uint32_t k = k0 + (uint32_t)lane;
+        const bool live = k < num;
+        uint32_t i = start + k;
+        i = i >= E ? i - E : i;
+        Entry e{};
+        if (live) e = ent[i];
+        const uint32_t sz = live ? e.nl + e.vl : 0u;
+        const uint32_t dst = carry + wave_excl_scan(sz, lane);
+        carry += (uint32_t)__builtin_amdgcn_readlane((int)(dst - carry + sz), 63);
+        uint8_t* d = scratch + rbase + dst;
+        wave_copy64(src(e.nsrc), d, live ? e.nl : 0u, lane);
+        wave_copy64(src(e.vsrc), d + e.nl, live ? e.vl : 0u, lane);
+        if (live) {
+            ent[i].nsrc = tag | (rbase + dst);
+            ent[i].vsrc = tag | (rbase + dst + e.nl);
+        }
+    }
+}
+
 // Zero LDS bytes [a, b) of a wave's buffer (a, b multiples of 16), 16-B stores by the whole wave.
 __device__ __forceinline__ void lds_zero(uint8_t* base, uint32_t a, uint32_t b, int lane) {
     for (uint32_t k = a + 16u * (uint32_t)lane; k < b; k += 1024u)
@@ -601,6 +645,20 @@ __device__ __forceinline__ uint8_t soft_bits(bool is_name, uint32_t cnt, uint32_
         return (cnt == 0 || ((flags & 1u) && first != ':')) ? 0x1 : 0x0;
     const bool ws = cnt != 0 && (first == ' ' || first == '\t' || last == ' ' || last == '\t');  // :110-115
     return ((flags & 2u) || ws) ? 0x2 : 0x0;
+}
+
+// h2o_lookup_token on a raw name (qpack.c:585) can only change a verdict for the pseudo-header tokens
+// (every other token is a valid lower-case name): lib/common/token_table.h
+__device__ __forceinline__ bool pseudo_token(const uint8_t* s, uint32_t len) {
+    const char* tok[6] = {":authority", ":method", ":path", ":protocol", ":scheme", ":status"};
+    const uint32_t tl[6] = {10, 7, 5, 9, 7, 7};
+    for (int k = 0; k < 6; ++k) {
+        if (tl[k] != len) continue;
+        bool eq = true;
+        for (uint32_t j = 0; j < len && eq; ++j) eq = s[j] == (uint8_t)tok[k][j];
+        if (eq) return true;
+    }
+    return false;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -1,16 +1,16 @@
 // What the header encoders of both protocols share (hhuff_hpenc.hip: HPACK, hhuff_qpenc.hip: QPACK): the
-// Huffman code tables, the prefix-integer and string lengths, the string hash, prep's per-pair step, the
-// register-sink writers, the long-string lists with the two launches that serve them, and the launchers'
-// workspace and launch helpers.  One object is built per .hip and the units share no device symbols, so the
-// tables have internal linkage: one copy per unit.
+// prefix-integer and string lengths, the string hash, prep's per-pair step, the register-sink writers, the
+// long-string lists with the two launches that serve them, and the launchers' workspace and launch helpers.
+// The Huffman code tables are hhuff_devtables.h's.  One object is built per .hip and the units share no device
+// symbols, so the tables have internal linkage: one copy per unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hhuff.h"
 #include "hhuff_device.h"
+#include "hhuff_devtables.h"
 #include "hhuff_launch.h"
-#include "hhuff_tables.h"
 
 namespace hhuff {
 // Strings too long for one lane: their hash / code bits (long_bits_kernel) and their payloads
@@ -50,8 +50,6 @@ inline LongWork long_ws(Carve& cv, uint64_t bits, uint64_t jobs) {
     } while (0)
 
 namespace {
-__device__ const uint32_t e_enc_code[256] = HHUFF_ENC_CODE_INIT;
-__device__ const uint8_t e_enc_nbits[256] = HHUFF_ENC_NBITS_INIT;
 __device__ const uint8_t __attribute__((aligned(16))) e_server[16] = {'s', 'e', 'r', 'v', 'e', 'r'};
 
 constexpr uint32_t kLongStr = 256;     // strings longer than this are hashed / coded by a whole wave

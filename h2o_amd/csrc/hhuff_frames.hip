@@ -26,9 +26,6 @@
 namespace hhuff {
 namespace {
 
-constexpr uint32_t kWalkThreads = 256;  // connections a walk workgroup: the unit of the first level of sums
-constexpr uint32_t kScanThreads = 1024;
-
 struct FrmArgs {
     const uint8_t* in;
     uint64_t in_size;
@@ -56,22 +53,6 @@ struct FrmArgs {
     uint4* job;    // [frm_cap]: source offset in `in`, destination offset in blk, length, 0
 };
 
-// Whatever in_off and frm_first hold, a connection's bytes stay inside in[0 .. in_size) and its slots inside
-// [0, frm_cap).
-struct ConnRange {
-    uint32_t start, len, f0, cap;
-    __device__ ConnRange(const FrmArgs& A, uint32_t c) {
-        const uint64_t s = A.in_off[c], e = A.in_off[c + 1];
-        start = (uint32_t)(s < A.in_size ? s : A.in_size);
-        const uint64_t e2 = e < start ? start : (e < A.in_size ? e : A.in_size);
-        len = (uint32_t)(e2 - start);
-        const uint32_t a = A.frm_first[c], b = A.frm_first[c + 1];
-        f0 = a < A.frm_cap ? a : A.frm_cap;
-        const uint32_t f1 = b < f0 ? f0 : (b < A.frm_cap ? b : A.frm_cap);
-        cap = f1 - f0;
-    }
-};
-
 struct PlaceSink {
     const FrmArgs& A;
     uint32_t start, f0, block0, byte0;
@@ -95,23 +76,6 @@ struct PlaceSink {
     }
 };
 
-// Sums over a workgroup of kWalkThreads lanes: excl = the sum of the lanes before this one, total = all of them.
-__device__ __forceinline__ void wg_scan(uint2 v, uint2& excl, uint2& total) {
-    __shared__ uint2 s[kWalkThreads];
-    const uint32_t tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kWalkThreads; d <<= 1) {
-        uint2 o = make_uint2(0u, 0u);
-        if (tid >= d) o = s[tid - d];
-        __syncthreads();
-        s[tid].x += o.x, s[tid].y += o.y;
-        __syncthreads();
-    }
-    const uint2 incl = s[tid];
-    excl = make_uint2(incl.x - v.x, incl.y - v.y), total = s[kWalkThreads - 1u];
-}
-
 template <bool PLACE>
 __global__ __launch_bounds__(kWalkThreads) void frm_walk_kernel(FrmArgs A) {
     const uint64_t c64 = (uint64_t)blockIdx.x * kWalkThreads + threadIdx.x;
@@ -124,14 +88,14 @@ __global__ __launch_bounds__(kWalkThreads) void frm_walk_kernel(FrmArgs A) {
         wg_scan(mine, before, all);
         if (!act) return;
         const uint2 wg = A.part[blockIdx.x];
-        const ConnRange R(A, c);
+        const SlotRange R(A.in_off, A.frm_first, c, A.in_size, A.frm_cap);
         const frm::Params P{A.max_frame_size, A.max_block_bytes, A.flags, R.cap};
         A.conn_first[c] = wg.x + before.x;
         PlaceSink sink{A, R.start, R.f0, wg.x + before.x, wg.y + before.y};
         frm::walk(A.in + R.start, R.len, P, sink, res);
     } else {
         if (act) {
-            const ConnRange R(A, c);
+            const SlotRange R(A.in_off, A.frm_first, c, A.in_size, A.frm_cap);
             const frm::Params P{A.max_frame_size, A.max_block_bytes, A.flags, R.cap};
             frm::NoSink sink;
             frm::walk(A.in + R.start, R.len, P, sink, res);
@@ -146,35 +110,8 @@ __global__ __launch_bounds__(kWalkThreads) void frm_walk_kernel(FrmArgs A) {
 
 // part[w] (the sums of walk workgroup w) -> the sums of the workgroups before w, in place; conn_first[nconn], totals.
 __global__ __launch_bounds__(kScanThreads) void frm_scan_kernel(FrmArgs A, uint32_t nparts) {
-    __shared__ uint2 run_sum[kScanThreads];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t run = (nparts + kScanThreads - 1u) / kScanThreads;  // consecutive entries a lane
-    const uint64_t p0 = (uint64_t)tid * run;
-    const uint64_t p1 = p0 + run < nparts ? p0 + run : nparts;
-    uint2 s = make_uint2(0u, 0u);
-    for (uint64_t p = p0; p < p1; ++p) {
-        const uint2 v = A.part[p];
-        s.x += v.x, s.y += v.y;
-    }
-    run_sum[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < kScanThreads; d <<= 1) {  // inclusive scan of the runs' sums
-        uint2 o = make_uint2(0u, 0u);
-        if (tid >= d) o = run_sum[tid - d];
-        __syncthreads();
-        run_sum[tid].x += o.x, run_sum[tid].y += o.y;
-        __syncthreads();
-    }
-    uint2 at = tid ? run_sum[tid - 1u] : make_uint2(0u, 0u);
-    for (uint64_t p = p0; p < p1; ++p) {
-        const uint2 v = A.part[p];
-        A.part[p] = at;
-        at.x += v.x, at.y += v.y;
-    }
-    if (tid == kScanThreads - 1u) {
-        const uint2 t = run_sum[tid];
-        A.conn_first[A.nconn] = t.x, A.totals[0] = t.x, A.totals[1] = t.y;
-    }
+    const uint2 t = scan_parts(A.part, nparts);
+    if (threadIdx.x == kScanThreads - 1u) A.conn_first[A.nconn] = t.x, A.totals[0] = t.x, A.totals[1] = t.y;
 }
 
 __global__ __launch_bounds__(256) void frm_finish_kernel(FrmArgs A) {

@@ -30,9 +30,6 @@
 namespace hhuff {
 namespace {
 
-constexpr uint32_t kH3WalkThreads = 256;  // streams a walk workgroup: the unit of the first level of sums
-constexpr uint32_t kH3ScanThreads = 1024;
-
 struct H3Args {
     const uint8_t* in;
     uint64_t in_size;
@@ -74,23 +71,6 @@ struct H3Args {
     uint8_t* dgram;  // [nstr]: h3_datagram
 };
 
-// Whatever str_off and frm_first hold, a stream's bytes stay inside in[0 .. in_size) and its slots inside
-// [0, frm_cap).
-struct StrRange {
-    uint32_t start, len, f0, cap;
-    __device__ StrRange(const H3Args& A, uint32_t s) {
-        const uint64_t b = A.str_off[s], e = A.str_off[s + 1];
-        start = (uint32_t)(b < A.in_size ? b : A.in_size);
-        const uint64_t e2 = e < start ? start : (e < A.in_size ? e : A.in_size);
-        len = (uint32_t)(e2 - start);
-        const uint32_t x = A.frm_first[s], y = A.frm_first[s + 1];
-        f0 = x < A.frm_cap ? x : A.frm_cap;
-        const uint32_t f1 = y < f0 ? f0 : (y < A.frm_cap ? y : A.frm_cap);
-        cap = f1 - f0;
-    }
-};
-
-__device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ uint32_t sat32(uint64_t v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
 
 struct H3PlaceSink {
@@ -120,38 +100,21 @@ struct H3PlaceSink {
     }
 };
 
-// Sums over a workgroup of kH3WalkThreads lanes: excl = the sum of the lanes before this one, total = all of them.
-__device__ __forceinline__ void h3_wg_scan(uint4 v, uint4& excl, uint4& total) {
-    __shared__ uint4 s[kH3WalkThreads];
-    const uint32_t tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kH3WalkThreads; d <<= 1) {
-        uint4 o = make_uint4(0u, 0u, 0u, 0u);
-        if (tid >= d) o = s[tid - d];
-        __syncthreads();
-        s[tid] = add4(s[tid], o);
-        __syncthreads();
-    }
-    const uint4 incl = s[tid];
-    excl = make_uint4(incl.x - v.x, incl.y - v.y, incl.z - v.z, incl.w - v.w), total = s[kH3WalkThreads - 1u];
-}
-
 template <bool PLACE>
-__global__ __launch_bounds__(kH3WalkThreads) void h3f_walk_kernel(H3Args A) {
-    const uint64_t s64 = (uint64_t)blockIdx.x * kH3WalkThreads + threadIdx.x;
+__global__ __launch_bounds__(kWalkThreads) void h3f_walk_kernel(H3Args A) {
+    const uint64_t s64 = (uint64_t)blockIdx.x * kWalkThreads + threadIdx.x;
     const bool act = s64 < A.nstr;  // (every lane stays for the workgroup's sums)
     const uint32_t s = (uint32_t)s64;
     h3f::Result res{};
     if (PLACE) {
         const uint4 mine = act ? A.count[s] : make_uint4(0u, 0u, 0u, 0u);
         uint4 before, all;
-        h3_wg_scan(mine, before, all);
+        wg_scan(mine, before, all);
         if (!act) return;
-        const uint4 at = add4(A.part[blockIdx.x], before);
+        const uint4 at = vadd(A.part[blockIdx.x], before);
         A.before[s] = at;
         const uint32_t enc_total = A.part[gridDim.x].z;  // the sections lie behind all encoder bytes
-        const StrRange R(A, s);
+        const SlotRange R(A.str_off, A.frm_first, s, A.in_size, A.frm_cap);
         const hhuff_h3_stream_t st = A.st_in[s];
         const h3f::Params P{A.max_frame_payload_size, A.flags & HHUFF_H3F_CLIENT, R.cap};
         H3PlaceSink sink{A, s, R.start, R.f0, st.stream_id, at.x, enc_total + at.y, at.z};
@@ -159,7 +122,7 @@ __global__ __launch_bounds__(kH3WalkThreads) void h3f_walk_kernel(H3Args A) {
         A.st_out[s] = h3f::next_state(st, res);  // (written here, behind the last read of st_in: st_out may be st_in)
     } else {
         if (act) {
-            const StrRange R(A, s);
+            const SlotRange R(A.str_off, A.frm_first, s, A.in_size, A.frm_cap);
             const hhuff_h3_stream_t st = A.st_in[s];
             const h3f::Params P{A.max_frame_payload_size, A.flags & HHUFF_H3F_CLIENT, R.cap};
             h3f::NoSink sink;
@@ -168,38 +131,16 @@ __global__ __launch_bounds__(kH3WalkThreads) void h3f_walk_kernel(H3Args A) {
             A.count[s] = make_uint4(res.nsec, res.sec_bytes, res.enc_bytes, res.got_settings);
         }
         uint4 before, all;
-        h3_wg_scan(make_uint4(res.nsec, res.sec_bytes, res.enc_bytes, res.got_settings), before, all);
+        wg_scan(make_uint4(res.nsec, res.sec_bytes, res.enc_bytes, res.got_settings), before, all);
         if (threadIdx.x == 0) A.part[blockIdx.x] = all;
     }
 }
 
 // part[w] (the sums of walk workgroup w) -> the sums of the workgroups before w, in place; part[nparts] and
 // before[nstr] = the totals; conn_first[nconn], totals.
-__global__ __launch_bounds__(kH3ScanThreads) void h3f_scan_kernel(H3Args A, uint32_t nparts) {
-    __shared__ uint4 run_sum[kH3ScanThreads];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t run = (nparts + kH3ScanThreads - 1u) / kH3ScanThreads;  // consecutive entries a lane
-    const uint64_t p0 = (uint64_t)tid * run;
-    const uint64_t p1 = p0 + run < nparts ? p0 + run : nparts;
-    uint4 s = make_uint4(0u, 0u, 0u, 0u);
-    for (uint64_t p = p0; p < p1; ++p) s = add4(s, A.part[p]);
-    run_sum[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < kH3ScanThreads; d <<= 1) {  // inclusive scan of the runs' sums
-        uint4 o = make_uint4(0u, 0u, 0u, 0u);
-        if (tid >= d) o = run_sum[tid - d];
-        __syncthreads();
-        run_sum[tid] = add4(run_sum[tid], o);
-        __syncthreads();
-    }
-    uint4 at = tid ? run_sum[tid - 1u] : make_uint4(0u, 0u, 0u, 0u);
-    for (uint64_t p = p0; p < p1; ++p) {
-        const uint4 v = A.part[p];
-        A.part[p] = at;
-        at = add4(at, v);
-    }
-    if (tid == kH3ScanThreads - 1u) {
-        const uint4 t = run_sum[tid];
+__global__ __launch_bounds__(kScanThreads) void h3f_scan_kernel(H3Args A, uint32_t nparts) {
+    const uint4 t = scan_parts(A.part, nparts);
+    if (threadIdx.x == kScanThreads - 1u) {
         A.part[nparts] = t, A.before[A.nstr] = t;
         A.conn_first[A.nconn] = t.x, A.totals[0] = t.x, A.totals[1] = t.y, A.totals[2] = t.z;
     }
@@ -248,7 +189,7 @@ __global__ __launch_bounds__(256) void h3f_finish_kernel(H3Args A) {
 }
 
 hipError_t launch_h3_deframe(H3Args& A, hipStream_t stream) {
-    const uint32_t wgrid = (uint32_t)(((uint64_t)A.nstr + kH3WalkThreads - 1u) / kH3WalkThreads);
+    const uint32_t wgrid = (uint32_t)(((uint64_t)A.nstr + kWalkThreads - 1u) / kWalkThreads);
     const uint64_t n = A.nstr;
     const uint64_t dgram_bytes = (n + 15u) & ~15ull;
     // job, count, setting [nstr], before [nstr + 1], part [wgrid + 1] of 16 bytes each, then dgram
@@ -264,9 +205,9 @@ hipError_t launch_h3_deframe(H3Args& A, hipStream_t stream) {
     A.dgram = reinterpret_cast<uint8_t*>(A.part + wgrid + 1u);
     e = hipMemsetAsync(A.job, 0, 16u * n, stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(h3f_walk_kernel<false>, dim3(wgrid), dim3(kH3WalkThreads), 0, stream, A);
-        hipLaunchKernelGGL(h3f_scan_kernel, dim3(1), dim3(kH3ScanThreads), 0, stream, A, wgrid);
-        hipLaunchKernelGGL(h3f_walk_kernel<true>, dim3(wgrid), dim3(kH3WalkThreads), 0, stream, A);
+        hipLaunchKernelGGL(h3f_walk_kernel<false>, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
+        hipLaunchKernelGGL(h3f_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, A, wgrid);
+        hipLaunchKernelGGL(h3f_walk_kernel<true>, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
         hipLaunchKernelGGL(h3f_conn_kernel, dim3((A.nconn + 255u) / 256u), dim3(256), 0, stream, A);
         hipLaunchKernelGGL(h3f_finish_kernel, dim3((uint32_t)((n + 1u + 255u) / 256u)), dim3(256), 0, stream, A);
         hipLaunchKernelGGL(frm_gather_kernel, dim3((uint32_t)((n + kGatherThreads - 1u) / kGatherThreads)), dim3(kGatherThreads), 0,

@@ -150,7 +150,7 @@ __device__ __forceinline__ FrameRule frame_rule(const hhuff_hpack_response_t& R)
 // 1. prep: one lane per header (item nhdr: the server name under the server token)
 __global__ __launch_bounds__(256) void hpe_prep_kernel(HpeArgs A) {
     __shared__ uint8_t s_nbits[256];
-    s_nbits[threadIdx.x] = e_enc_nbits[threadIdx.x];
+    s_nbits[threadIdx.x] = g_enc_nbits[threadIdx.x];
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i <= A.nhdr; i += (uint64_t)gridDim.x * 256u) {
         uint32_t info;
@@ -189,7 +189,7 @@ template <bool HASH>
 __global__ __launch_bounds__(256) void long_bits_kernel(const uint8_t* in, const hhuff_hpack_header_t* hdr, uint32_t nhdr,
                                                         uint32_t server_off, uint32_t server_len, uint4* rec, LongWork L) {
     __shared__ uint8_t s_nbits[256];
-    s_nbits[threadIdx.x] = e_enc_nbits[threadIdx.x];
+    s_nbits[threadIdx.x] = g_enc_nbits[threadIdx.x];
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const uint32_t n = min(L.bits[0], L.cap);
@@ -282,7 +282,7 @@ __device__ void wave_huff_long(const uint8_t* src, uint32_t len, uint8_t* dst, c
 __global__ __launch_bounds__(256) void long_payload_kernel(const uint8_t* in, LongWork L) {
     __shared__ uint2 s_enc[256];
     __shared__ uint32_t s_stage[4][kStageWords + 4];
-    s_enc[threadIdx.x] = make_uint2(e_enc_code[threadIdx.x], e_enc_nbits[threadIdx.x]);
+    s_enc[threadIdx.x] = make_uint2(g_enc_code[threadIdx.x], g_enc_nbits[threadIdx.x]);
     for (uint32_t k = threadIdx.x; k < 4 * (kStageWords + 4); k += 256) (&s_stage[0][0])[k] = 0u;
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -565,7 +565,7 @@ __device__ __forceinline__ void put_frame_header(uint8_t* d, uint32_t len, uint3
 //    stream id, table size update, :status, server, and the content-length at the end)
 __global__ __launch_bounds__(256) void hpe_emit_kernel(HpeArgs A) {
     __shared__ uint2 s_enc[256];
-    s_enc[threadIdx.x] = make_uint2(e_enc_code[threadIdx.x], e_enc_nbits[threadIdx.x]);
+    s_enc[threadIdx.x] = make_uint2(g_enc_code[threadIdx.x], g_enc_nbits[threadIdx.x]);
     __syncthreads();
     const GlobalSource src{A.in, A.in_size};
     const uint64_t items = (uint64_t)A.nhdr + A.nres;

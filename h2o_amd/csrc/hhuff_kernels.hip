@@ -23,17 +23,11 @@
 #include <vector>
 
 #include "hhuff_device.h"
+#include "hhuff_devtables.h"
+#include "hhuff_int.h"
 #include "hhuff_launch.h"
 
 namespace hhuff {
-
-__device__ const uint32_t g_dec_lut[1u << HHUFF_LUT_BITS] = HHUFF_DEC_LUT_INIT;
-__device__ const uint32_t g_name_invalid[8] = HHUFF_NAME_INVALID_INIT;    // raw-literal validity bitmaps
-__device__ const uint32_t g_value_invalid[8] = HHUFF_VALUE_INVALID_INIT;  // (hpack.c:171-180, 200-209)
-__device__ const uint32_t g_kinfo[31] = HHUFF_ONES_KINFO_INIT;
-__device__ const uint32_t g_ones[HHUFF_ONES_NENT] = HHUFF_ONES_ENT_INIT;
-__device__ const uint32_t g_enc_code[256] = HHUFF_ENC_CODE_INIT;
-__device__ const uint8_t g_enc_nbits[256] = HHUFF_ENC_NBITS_INIT;
 
 // ------------------------------------------------------------------------------------------------
 // tile helpers
@@ -378,21 +372,6 @@ __device__ __forceinline__ void lane_copy(uint8_t* __restrict__ dst, const uint8
     for (uint32_t j = 0; j < (n & 3u); ++j) dst[j] = src[j];
 }
 
-// RegSink that also remembers the first and last byte (direct decode path).
-struct RegSinkFL : RegSink {
-    uint32_t first, last;
-    __device__ __forceinline__ void put1(uint32_t b) {
-        first = cnt == 0 ? (b & 0xFFu) : first;
-        last = b & 0xFFu;
-        RegSink::put1(b);
-    }
-    __device__ __forceinline__ void put12(uint32_t syms, bool two) {
-        first = cnt == 0 ? (syms & 0xFFu) : first;
-        last = (two ? (syms >> 8) : syms) & 0xFFu;
-        RegSink::put12(syms, two);
-    }
-};
-
 // ------------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------------
@@ -429,13 +408,6 @@ struct DecArgs {
     // stream kernel: strings a wave takes from the batch counter at a time (stream_claim)
     uint32_t claim = 64;
 };
-
-__device__ __forceinline__ void load_dec_tables(uint32_t* s_lut, uint32_t* s_kinfo, uint32_t* s_ones, int nthreads) {
-    for (uint32_t k = threadIdx.x; k < (1u << HHUFF_LUT_BITS) / 4; k += nthreads)
-        reinterpret_cast<uint4*>(s_lut)[k] = reinterpret_cast<const uint4*>(g_dec_lut)[k];
-    for (uint32_t k = threadIdx.x; k < HHUFF_ONES_NENT; k += nthreads) s_ones[k] = g_ones[k];
-    if (threadIdx.x < 31) s_kinfo[threadIdx.x] = g_kinfo[threadIdx.x];
-}
 
 // a string long enough for split_decode_kernel goes to its list (when the launch has one) instead of being
 // decoded by this lane; a full list leaves it here
@@ -2710,46 +2682,15 @@ __device__ __forceinline__ uint32_t lit_header(const LitArgs& A, uint32_t i, boo
     const uint32_t p = A.prefix_of ? A.prefix_of[i] : A.prefix_bits;
     const uint32_t b0 = A.in[off];
     huff = ((b0 >> p) & 1u) != 0;
-    const uint64_t pmax = (1u << p) - 1u;
-    uint64_t v = b0 & pmax, q = off + 1;
-    if (v == pmax) {
-        bool done = false;
-        uint32_t shift = 0;
-        for (; shift < 56; shift += 7) {
-            if (q == end) return kLitIncomplete;
-            const uint32_t b = A.in[q++];
-            v += (uint64_t)(b & 127u) << shift;
-            if (!(b & 128u)) {
-                done = true;
-                break;
-            }
-        }
-        if (!done) {  // the 9th octet (hpack.c:75-81)
-            if (q == end) return kLitIncomplete;
-            const uint32_t b = A.in[q];
-            if (b & 128u) return kLitBadInt;
-            v += (uint64_t)(b & 127u) << shift;
-            ++q;
-            if (v > 0x7FFFFFFFFFFFFFFFull) return kLitBadInt;
-        }
-    }
+    uint64_t q = off;
+    const int64_t n = hpack_int(A.in, q, end, p);
+    if (n < 0) return n == kIntIncomplete ? kLitIncomplete : kLitBadInt;
+    const uint64_t v = (uint64_t)n;
     if (v > end - q) return kLitTruncated;
     if (v > kMaxStrLen) return kLitTooLong;
     hdr = (uint32_t)(q - off);
     len = (uint32_t)v;
     return 0;
-}
-
-__device__ __forceinline__ bool pseudo_token(const uint8_t* s, uint32_t len) {  // lib/common/token_table.h
-    const char* tok[6] = {":authority", ":method", ":path", ":protocol", ":scheme", ":status"};
-    const uint32_t tl[6] = {10, 7, 5, 9, 7, 7};
-    for (int k = 0; k < 6; ++k) {
-        if (tl[k] != len) continue;
-        bool eq = true;
-        for (uint32_t j = 0; j < len && eq; ++j) eq = s[j] == (uint8_t)tok[k][j];
-        if (eq) return true;
-    }
-    return false;
 }
 
 // Pass 1: headers; raw payloads are validated and copied here (they skip the Huffman kernel, which

@@ -33,8 +33,10 @@
 
 #include "hhuff_decwork.h"
 #include "hhuff_device.h"
+#include "hhuff_devtables.h"
 #include "hhuff_image.h"
 #include "hhuff.h"
+#include "hhuff_int.h"
 #include "hhuff_launch.h"
 #include "hhuff_qpark.h"
 #include "hhuff_request.h"
@@ -42,11 +44,6 @@
 
 namespace hhuff {
 namespace {
-__device__ const uint32_t q_dec_lut[1u << HHUFF_LUT_BITS] = HHUFF_DEC_LUT_INIT;
-__device__ const uint32_t q_kinfo[31] = HHUFF_ONES_KINFO_INIT;
-__device__ const uint32_t q_ones[HHUFF_ONES_NENT] = HHUFF_ONES_ENT_INIT;
-__device__ const uint32_t q_name_invalid[8] = HHUFF_NAME_INVALID_INIT;
-__device__ const uint32_t q_value_invalid[8] = HHUFF_VALUE_INVALID_INIT;
 __device__ const uint8_t q_static_bytes[HHUFF_QSTATIC_NBYTES] = HHUFF_QSTATIC_BYTES_INIT;
 __device__ const uint16_t q_static_ent[99 * 4] = HHUFF_QSTATIC_ENT_INIT;
 
@@ -56,7 +53,6 @@ constexpr int32_t kQIncomplete = -1;       // H2O_HTTP3_ERROR_INCOMPLETE (http3_
 constexpr int32_t kErrInvalidChar = -254;  // H2O_HTTP2_ERROR_INVALID_HEADER_CHAR
 constexpr uint32_t kEntryOverhead = 32;    // HEADER_ENTRY_SIZE_OFFSET (qpack.c:32)
 constexpr int64_t kQuicIntMax = 4611686018427387903LL;  // PTLS_QUICINT_MAX
-constexpr int64_t kIntIncomplete = -255, kIntBad = -9;
 }  // namespace
 
 struct QpkArgs : QpdCall {  // the call, and what launch_qpack adds to it
@@ -120,29 +116,9 @@ static_assert(offsetof(QState, max_size) == offsetof(img::QdState, max_size) && 
 __host__ __device__ __forceinline__ uint32_t qpk_ring_bytes(uint32_t T) { return ((T < 16u ? 16u : T) + 15u) & ~15u; }
 __host__ __device__ __forceinline__ uint32_t qpk_entries(uint32_t T) { return T / kEntryOverhead + 1u; }
 
-// h2o_hpack_decode_int (lib/http2/hpack.c:52-83) at in[p], bounded by end
-__device__ int64_t q_hpack_int(const uint8_t* __restrict__ in, uint64_t& p, uint64_t end, uint32_t prefix_bits) {
-    if (p >= end) return kIntIncomplete;
-    const uint64_t pmax = (1u << prefix_bits) - 1u;
-    uint64_t v = in[p++] & pmax;
-    if (v != pmax) return (int64_t)v;
-    uint32_t shift = 0;
-    for (; shift < 56; shift += 7) {
-        if (p == end) return kIntIncomplete;
-        const uint32_t b = in[p++];
-        v += (uint64_t)(b & 127u) << shift;
-        if (!(b & 128u)) return (int64_t)v;
-    }
-    if (p == end) return kIntIncomplete;
-    if (in[p] & 128u) return kIntBad;
-    v += (uint64_t)(in[p++] & 127u) << shift;
-    if (v > 0x7FFFFFFFFFFFFFFFull) return kIntBad;
-    return (int64_t)v;
-}
-
 // decode_int (qpack.c:215-220): 0, kQIncomplete or kDF
 __device__ __forceinline__ int32_t q_int(int64_t& v, const uint8_t* in, uint64_t& p, uint64_t end, uint32_t prefix) {
-    v = q_hpack_int(in, p, end, prefix);
+    v = hpack_int(in, p, end, prefix);
     if (v < 0) return v == kIntIncomplete ? kQIncomplete : kDF;
     return 0;
 }
@@ -153,7 +129,7 @@ __device__ bool q_valid_name(Get get, uint64_t n, uint32_t& soft) {
     bool bad = n == 0;
     for (uint64_t i = 0; i < n; ++i) {
         const uint32_t c = get(i);
-        if ((q_name_invalid[c >> 5] >> (c & 31)) & 1u) {
+        if ((g_name_invalid[c >> 5] >> (c & 31)) & 1u) {
             if (c - 'A' < 26u) return false;
             bad = true;
         }
@@ -172,43 +148,10 @@ __device__ void q_valid_value(Get get, uint64_t n, uint32_t& soft) {
     }
     for (uint64_t i = 0; !bad && i < n; ++i) {
         const uint32_t c = get(i);
-        bad = ((q_value_invalid[c >> 5] >> (c & 31)) & 1u) != 0;
+        bad = ((g_value_invalid[c >> 5] >> (c & 31)) & 1u) != 0;
     }
     if (bad) soft |= 0x2u;
 }
-
-// h2o_lookup_token on a raw name (qpack.c:585) can only change a verdict for the pseudo-header tokens
-// (every other token is a valid lower-case name): :authority :method :path :protocol :scheme :status
-template <class Get>
-__device__ bool q_pseudo_token(Get get, uint64_t n) {
-    if (n < 5 || n > 10 || get(0) != ':') return false;
-    const char* const tok[6] = {":authority", ":method", ":path", ":protocol", ":scheme", ":status"};
-    const uint8_t len[6] = {10, 7, 5, 9, 7, 7};
-    for (int k = 0; k < 6; ++k) {
-        if (len[k] != n) continue;
-        bool eq = true;
-        for (uint64_t i = 1; eq && i < n; ++i) eq = get(i) == (uint8_t)tok[k][i];
-        if (eq) return true;
-    }
-    return false;
-}
-
-// sink with first / last byte tracking over a RegSink (soft bits need them, hpack.c:136-152)
-struct ArenaSinkFL {
-    RegSink s;
-    uint32_t first, last;
-    __device__ __forceinline__ void put1(uint32_t b) {
-        first = s.cnt == 0 ? (b & 0xFFu) : first;
-        last = b & 0xFFu;
-        s.put1(b);
-    }
-    __device__ __forceinline__ void put12(uint32_t syms, bool two) {
-        first = s.cnt == 0 ? (syms & 0xFFu) : first;
-        last = (two ? (syms >> 8) : syms) & 0xFFu;
-        s.put12(syms, two);
-    }
-    __device__ __forceinline__ uint32_t count() const { return s.count(); }
-};
 
 struct QTable {  // one connection's table, as the kernels see it
     QEntry* ent;
@@ -272,11 +215,12 @@ __device__ bool q_enc_string(const QpkArgs& A, bool huff, bool is_name, uint64_t
     }
     if (huff) {
         if (n > kMaxStrLen) return false;
-        ArenaSinkFL sk{RegSink{}, 0u, 0u};
-        sk.s.init(const_cast<uint8_t*>(A.lit_out) + (p * 8u) / 5u);
+        RegSinkFL sk;
+        sk.init(const_cast<uint8_t*>(A.lit_out) + (p * 8u) / 5u);
+        sk.first = sk.last = 0;
         const DecResult d = decode_core(GlobalSource{A.in, A.in_size}, (uint32_t)p, (uint32_t)n, sk, T);
         if (!d.ok) return false;
-        sk.s.finish();
+        sk.finish();
         soft |= soft_bits(is_name, d.len, d.flags, sk.first, sk.last);
         len = d.len;
         src = kQLit | ((p * 8u) / 5u);
@@ -365,10 +309,7 @@ __device__ int32_t q_handle_input(QTable& t, const QpkArgs& A, uint64_t p, uint6
                     ret = kDF;
                 } else {
                     // a name h2o_lookup_token knows goes in as a token header with soft bits 0 (:383-384)
-                    if (e.soft) {
-                        const uint8_t* nb = q_src(A, e.nsrc);
-                        if (q_pseudo_token([&](uint64_t i) { return (uint32_t)nb[i]; }, e.nl)) e.soft = 0;
-                    }
+                    if (e.soft && pseudo_token(q_src(A, e.nsrc), e.nl)) e.soft = 0;
                     ret = q_value_and_insert(t, A, e, vhuff, p, (uint64_t)value_len, vpre, T);
                 }
                 p += (uint64_t)value_len;
@@ -406,14 +347,6 @@ __device__ __forceinline__ QTable q_table(const QpkArgs& A, uint64_t slot) {  //
     QTable t{reinterpret_cast<QEntry*>(scr + sizeof(QState)), qpk_entries(A.T), {}};
     t.s = *reinterpret_cast<const QState*>(scr);
     return t;
-}
-
-__device__ __forceinline__ void load_dec_tables(uint32_t* s_lut, uint32_t* s_kinfo, uint32_t* s_ones) {
-    for (uint32_t k = threadIdx.x; k < (1u << HHUFF_LUT_BITS) / 4; k += blockDim.x)
-        reinterpret_cast<uint4*>(s_lut)[k] = reinterpret_cast<const uint4*>(q_dec_lut)[k];
-    for (uint32_t k = threadIdx.x; k < HHUFF_ONES_NENT; k += blockDim.x) s_ones[k] = q_ones[k];
-    if (threadIdx.x < 31) s_kinfo[threadIdx.x] = q_kinfo[threadIdx.x];
-    __syncthreads();
 }
 
 // one connection's encoder stream (cs: its slab, by the call's map or by the connection's own number)
@@ -454,7 +387,8 @@ __global__ __launch_bounds__(256) void qpack_encoder_kernel(QpkArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
     __shared__ uint32_t s_kinfo[32];
     __shared__ uint32_t s_ones[HHUFF_ONES_NENT];
-    load_dec_tables(s_lut, s_kinfo, s_ones);
+    load_dec_tables(s_lut, s_kinfo, s_ones, blockDim.x);
+    __syncthreads();
     DecTables T;  // assigned, not brace-initialised (see hhuff_blocks.hip)
     T.lut = s_lut;
     T.kinfo = s_kinfo;
@@ -491,7 +425,8 @@ __global__ __launch_bounds__(256) void qpack_encoder_ds_kernel(QpkArgs A, QdsArg
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
     __shared__ uint32_t s_kinfo[32];
     __shared__ uint32_t s_ones[HHUFF_ONES_NENT];
-    load_dec_tables(s_lut, s_kinfo, s_ones);
+    load_dec_tables(s_lut, s_kinfo, s_ones, blockDim.x);
+    __syncthreads();
     DecTables T;  // assigned, not brace-initialised (see hhuff_blocks.hip)
     T.lut = s_lut;
     T.kinfo = s_kinfo;
@@ -601,25 +536,7 @@ __global__ __launch_bounds__(256) void qpack_table_kernel(QpkArgs A) {
     QEntry* ent = reinterpret_cast<QEntry*>(A.scratch + base + sizeof(QState));
     const uint32_t nring = s.ring ^ 1u;
     const uint64_t rbase = base + sizeof(QState) + (uint64_t)E * sizeof(QEntry) + nring * (uint64_t)qpk_ring_bytes(A.T);
-    uint32_t carry = 0;
-    for (uint32_t k0 = 0; k0 < s.num; k0 += 64) {
-        const uint32_t k = k0 + (uint32_t)lane;
-        const bool live = k < s.num;
-        uint32_t i = s.start + k;
-        i = i >= E ? i - E : i;
-        QEntry e{};
-        if (live) e = ent[i];
-        const uint32_t sz = live ? e.nl + e.vl : 0u;
-        const uint32_t dst = carry + wave_excl_scan(sz, lane);
-        carry += (uint32_t)__builtin_amdgcn_readlane((int)(dst - carry + sz), 63);
-        uint8_t* d = A.scratch + rbase + dst;
-        wave_copy64(q_src(A, e.nsrc), d, live ? e.nl : 0u, lane);
-        wave_copy64(q_src(A, e.vsrc), d + e.nl, live ? e.vl : 0u, lane);
-        if (live) {
-            ent[i].nsrc = kQScr | (rbase + dst);
-            ent[i].vsrc = kQScr | (rbase + dst + e.nl);
-        }
-    }
+    wave_table_pass(A.scratch, ent, E, s.start, s.num, rbase, kQScr, lane, [&](uint64_t x) { return q_src(A, x); });
     if (lane == 0) ps->ring = nring;
 }
 
@@ -714,18 +631,19 @@ __device__ int32_t q_literal(const QpkArgs& A, QArena& R, uint32_t& soft, uint64
     if (huff) {
         if (R.cur + ((uint64_t)n * 8u) / 5u > R.end) return HHUFF_QPK_ARENA;
         if ((uint64_t)n > kMaxStrLen) return kDF;
-        ArenaSinkFL sk{RegSink{}, 0u, 0u};
-        sk.s.init(R.a + R.cur);
+        RegSinkFL sk;
+        sk.init(R.a + R.cur);
+        sk.first = sk.last = 0;
         const DecResult d = decode_core(GlobalSource{A.in, A.in_size}, (uint32_t)p, (uint32_t)n, sk, T);
         if (!d.ok) return kDF;
-        sk.s.finish();
+        sk.finish();
         soft |= soft_bits(is_name, d.len, d.flags, sk.first, sk.last);
         len = d.len;
     } else {
         const uint8_t* src = in + p;
         auto get = [&](uint64_t i) { return (uint32_t)src[i]; };
         if (is_name) {  // tokens are taken as they are; anything else is validated (:583-588)
-            if (!q_pseudo_token(get, (uint64_t)n) && !q_valid_name(get, (uint64_t)n, soft)) return kDF;
+            if (!pseudo_token(src, (uint32_t)n) && !q_valid_name(get, (uint64_t)n, soft)) return kDF;  // (n < 2^32: u32 offsets)
         } else {
             q_valid_value(get, (uint64_t)n, soft);
         }
@@ -881,7 +799,8 @@ __global__ __launch_bounds__(256) void qpack_sections_kernel(QpkArgs A) {
     __shared__ __attribute__((aligned(16))) uint32_t s_lut[1u << HHUFF_LUT_BITS];
     __shared__ uint32_t s_kinfo[32];
     __shared__ uint32_t s_ones[HHUFF_ONES_NENT];
-    load_dec_tables(s_lut, s_kinfo, s_ones);
+    load_dec_tables(s_lut, s_kinfo, s_ones, blockDim.x);
+    __syncthreads();
     DecTables T;  // assigned, not brace-initialised (see hhuff_blocks.hip)
     T.lut = s_lut;
     T.kinfo = s_kinfo;
@@ -1028,7 +947,7 @@ __device__ __forceinline__ bool q_mark_literal(const uint8_t* in, uint64_t& p, u
                                                const QMarks& M) {
     if (p >= end) return false;
     uint64_t q = p;
-    const int64_t n = q_hpack_int(in, q, end, prefix);
+    const int64_t n = hpack_int(in, q, end, prefix);
     if (n < 0 || (uint64_t)n > end - q) return false;
     const uint32_t w = (uint32_t)(p >> 5), m = 1u << (p & 31);
     atomicOr(M.lit + w, m);
@@ -1047,17 +966,17 @@ __global__ __launch_bounds__(256) void qpack_mark_kernel(QpkArgs A, QMarks M) {
             const uint64_t k = c - A.nconn;
             uint64_t p = A.sec_off[k];
             const uint64_t end = A.sec_off[k + 1];
-            bool go = q_hpack_int(in, p, end, 8) >= 0 && p < end && q_hpack_int(in, p, end, 7) >= 0;
+            bool go = hpack_int(in, p, end, 8) >= 0 && p < end && hpack_int(in, p, end, 7) >= 0;
             while (go && p < end) {
                 const uint32_t kind = in[p] >> 4;
                 if (kind >= 8) {  // indexed, static or dynamic
-                    go = q_hpack_int(in, p, end, 6) >= 0;
+                    go = hpack_int(in, p, end, 6) >= 0;
                 } else if (kind == 1) {  // indexed, post-base
-                    go = q_hpack_int(in, p, end, 4) >= 0;
+                    go = hpack_int(in, p, end, 4) >= 0;
                 } else if (kind == 2 || kind == 3) {  // literal name, then the value
                     go = q_mark_literal(in, p, end, 3, M) && q_mark_literal(in, p, end, 7, M);
                 } else {  // name reference (static / dynamic 4 bits, post-base 3), then the value
-                    go = q_hpack_int(in, p, end, kind == 0 ? 3 : 4) >= 0 && q_mark_literal(in, p, end, 7, M);
+                    go = hpack_int(in, p, end, kind == 0 ? 3 : 4) >= 0 && q_mark_literal(in, p, end, 7, M);
                 }
             }
             continue;
@@ -1069,14 +988,14 @@ __global__ __launch_bounds__(256) void qpack_mark_kernel(QpkArgs A, QMarks M) {
             const uint32_t b = in[p];
             switch (b >> 5) {
                 default:  // insert with name reference: index, then the value
-                    go = q_hpack_int(in, p, end, 6) >= 0 && q_mark_literal(in, p, end, 7, M);
+                    go = hpack_int(in, p, end, 6) >= 0 && q_mark_literal(in, p, end, 7, M);
                     break;
                 case 2:
                 case 3:  // insert with a literal name: the name (5-bit prefix), then the value
                     go = q_mark_literal(in, p, end, 5, M) && q_mark_literal(in, p, end, 7, M);
                     break;
                 case 0:
-                case 1: go = q_hpack_int(in, p, end, 5) >= 0; break;  // duplicate, set capacity
+                case 1: go = hpack_int(in, p, end, 5) >= 0; break;  // duplicate, set capacity
             }
         }
     }

@@ -12,6 +12,7 @@
 
 #include "hhuff_enc.h"
 #include "hhuff_image.h"
+#include "hhuff_int.h"
 #include "hhuff_qtable.h"
 #include "hhuff_slots.h"
 
@@ -39,7 +40,7 @@ __device__ __forceinline__ uint32_t q_str_len(uint32_t len, uint32_t bits, uint3
 
 __device__ __forceinline__ uint32_t code_bits(const uint8_t* p, uint32_t len) {
     uint32_t bits = 0;
-    for (uint32_t k = 0; k < len; ++k) bits += e_enc_nbits[p[k]];
+    for (uint32_t k = 0; k < len; ++k) bits += g_enc_nbits[p[k]];
     return bits;
 }
 
@@ -145,7 +146,7 @@ __device__ __forceinline__ uint32_t q_ndigits(uint64_t v) {
 __device__ __forceinline__ uint32_t q_digits(uint64_t v, uint32_t& bits) {
     const uint32_t n = q_ndigits(v);
     bits = 0;
-    for (uint32_t k = 0; k < n; ++k) bits += e_enc_nbits[q_digit(v, n, k)];
+    for (uint32_t k = 0; k < n; ++k) bits += g_enc_nbits[q_digit(v, n, k)];
     return n;
 }
 
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(256) void qpe_layout_kernel(QpeArgs A) {
 
 __global__ __launch_bounds__(256) void qpe_emit_kernel(QpeArgs A) {
     __shared__ uint2 s_enc[256];
-    s_enc[threadIdx.x] = make_uint2(e_enc_code[threadIdx.x], e_enc_nbits[threadIdx.x]);
+    s_enc[threadIdx.x] = make_uint2(g_enc_code[threadIdx.x], g_enc_nbits[threadIdx.x]);
     __syncthreads();
     const GlobalSource src{A.in, A.in_size};
     const uint64_t items = (uint64_t)A.nhdr + A.nres;
@@ -474,35 +475,18 @@ struct QsSection {
     uint32_t smallest;                       // evicting: the smallest index referenced so far
 };
 
-// h2o_hpack_decode_int (lib/http2/hpack.c:52-83) through decode_int (qpack.c:215-220): 0, 1 incomplete, 2 overflow
-__device__ int qs_decode_int(const uint8_t* b, uint32_t n, uint32_t& p, uint32_t prefix, uint64_t& v) {
-    const uint32_t mx = (1u << prefix) - 1u;
-    if (p >= n) return 1;
-    v = b[p++] & mx;
-    if (v != mx) return 0;
-    for (uint32_t shift = 0; shift < 56; shift += 7) {
-        if (p == n) return 1;
-        const uint32_t x = b[p++];
-        v += (uint64_t)(x & 127u) << shift;
-        if (!(x & 128u)) return 0;
-    }
-    if (p == n) return 1;
-    if (b[p] & 128u) return 2;
-    v += (uint64_t)(b[p++] & 127u) << 56;
-    return v > 0x7FFFFFFFFFFFFFFFull ? 2 : 0;
-}
-
 // h2o_qpack_encoder_handle_input (qpack.c:963-1005): `consumed` = the bytes of the instructions taken
 template <bool EV>
 __device__ int32_t qs_handle_input(QsConn& t, const uint8_t* b, uint32_t n, uint32_t& consumed) {
-    uint32_t p = 0;
+    uint64_t p = 0;
     while (p < n) {
         const uint32_t kind = b[p] >> 6;
-        uint64_t v = 0;
-        const int rc = qs_decode_int(b, n, p, kind >= 2 ? 7u : 6u, v);
-        if (rc == 1) return 0;  // the rest waits for more input
-        if (rc == 2) return HHUFF_QPK_DECOMPRESSION_FAILED;
-        consumed = p;
+        // h2o_hpack_decode_int through decode_int (qpack.c:215-220)
+        const int64_t r = hpack_int(b, p, n, kind >= 2 ? 7u : 6u);
+        if (r == kIntIncomplete) return 0;  // the rest waits for more input
+        if (r < 0) return HHUFF_QPK_DECOMPRESSION_FAILED;
+        const uint64_t v = (uint64_t)r;
+        consumed = (uint32_t)p;
         if (kind == 0) {  // Insert Count Increment (handle_table_state_synchronize :902-918)
             if (v == 0 || (uint64_t)t.s.lkr + v >= (uint64_t)t.s.count + 1u) return HHUFF_QPK_DECODER_STREAM;
             t.s.lkr += (uint32_t)v;
@@ -684,7 +668,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
             F.info = si | kSiStatic | kSiExact;
         } else {
             F.vl = qs_decimal((uint16_t)R.status, dg);
-            hash_bits_lane(dg, F.vl, e_enc_nbits, F.vh, F.vb);
+            hash_bits_lane(dg, F.vl, g_enc_nbits, F.vh, F.vb);
             F.info = 24u | kSiStatic;
         }
         O.code[0] = qs_field<EV, DUP>(t, S, F, len, ins, ins_len);
@@ -704,7 +688,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
                 G.info |= kSiExact;
             } else {
                 G.vl = qs_decimal(R.content_length, dg);
-                hash_bits_lane(dg, G.vl, e_enc_nbits, G.vh, G.vb);
+                hash_bits_lane(dg, G.vl, g_enc_nbits, G.vh, G.vb);
             }
             O.code[2] = qs_field<EV, DUP>(t, S, G, len, ins, ins_len);
             S.pos += len;
@@ -729,8 +713,8 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
     }
     if (R.flags & HHUFF_QRES_DATAGRAM) {  // no static entry, not likely to repeat
         QsField F{q_dfid_name, C.in + R.dfid_off, 16u, R.dfid_len, N.dfid, 0u, 0u, 0u, 0u};
-        hash_bits_lane(q_dfid_name, 16u, e_enc_nbits, F.nh, F.nb);
-        hash_bits_lane(F.v, F.vl, e_enc_nbits, F.vh, F.vb);
+        hash_bits_lane(q_dfid_name, 16u, g_enc_nbits, F.nh, F.nb);
+        hash_bits_lane(F.v, F.vl, g_enc_nbits, F.vh, F.vb);
         O.code[3] = qs_field<EV, DUP>(t, S, F, len, ins, ins_len);
         O.df_len = len;
         S.pos += len;
@@ -740,7 +724,7 @@ __device__ void qs_walk_section(const QseArgs& A, QsConn& t, const hhuff_qpack_r
 
 __global__ __launch_bounds__(256) void qse_prep_kernel(QseArgs A) {
     __shared__ uint8_t s_nbits[256];
-    s_nbits[threadIdx.x] = e_enc_nbits[threadIdx.x];
+    s_nbits[threadIdx.x] = g_enc_nbits[threadIdx.x];
     __syncthreads();
     const QseCall& C = A.c;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i <= C.nhdr; i += (uint64_t)gridDim.x * 256u) {
@@ -853,9 +837,9 @@ __global__ __launch_bounds__(64) void qse_walk_kernel(QseArgs A) {
 
     QsNames N;
     uint32_t nb;
-    hash_bits_lane(q_status_name, 7u, e_enc_nbits, N.status, nb);
-    hash_bits_lane(q_cl_name, 14u, e_enc_nbits, N.cl, nb);
-    hash_bits_lane(q_dfid_name, 16u, e_enc_nbits, N.dfid, nb);
+    hash_bits_lane(q_status_name, 7u, g_enc_nbits, N.status, nb);
+    hash_bits_lane(q_cl_name, 14u, g_enc_nbits, N.cl, nb);
+    hash_bits_lane(q_dfid_name, 16u, g_enc_nbits, N.dfid, nb);
 
     const uint32_t r1 = min(C.conn_first[c + 1], C.nres), r0 = min(C.conn_first[c], r1);
     for (uint32_t r = r0; r < r1; ++r) {
@@ -1004,7 +988,7 @@ __device__ __forceinline__ void qs_emit_insert(RegSink& sink, const GlobalSource
 // connections (Set Dynamic Table Capacity)
 __global__ __launch_bounds__(256) void qse_emit_kernel(QseArgs A) {
     __shared__ uint2 s_enc[256];
-    s_enc[threadIdx.x] = make_uint2(e_enc_code[threadIdx.x], e_enc_nbits[threadIdx.x]);
+    s_enc[threadIdx.x] = make_uint2(g_enc_code[threadIdx.x], g_enc_nbits[threadIdx.x]);
     __syncthreads();
     const QseCall& C = A.c;
     const GlobalSource src{C.in, C.in_size};
