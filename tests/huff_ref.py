@@ -6,6 +6,10 @@ with this file, and tests/test_decode_edges_host.py compares this file with the 
   walk(src)             -> Walk: the symbols, the bit offset at which each starts, where the walk stopped and why
   decode(src, is_name)  -> (bytes | None, status): status is the batch API's byte -- 0x80 for a string that fails,
                            else the soft bits (0x1 name, 0x2 value)
+  encode(src)           -> bytes | None: h2o_hpack_encode_huffman (hpack.c:774-804) from the same two tables, code
+                           after code on a bit string; None where the call returns SIZE_MAX (tests/encode_edges.py's
+                           corpus and plans compare with it, tests/test_encode_edges_host.py compares it with the
+                           oracle and the golden encode vectors)
 
 `src` is a bytes object or a str of '0' / '1' (any number of bits: the generators and the models of
 tests/decode_edges.py walk bit strings that are no whole bytes yet)."""
@@ -120,3 +124,24 @@ def decode(src, is_name=False):
 
 def symbol_starts(src):
     return walk(src).starts
+
+
+# every symbol's code as a string of '0' / '1', MSB first (RFC 7541 Appendix B)
+_CODE_BITS = ["".join("1" if (c >> j) & 1 else "0" for j in range(n - 1, -1, -1))
+              for c, n in zip(tables.ENC_CODE, tables.ENC_NBITS)]
+
+
+def code_bits(src):
+    """the codes of the bytes of `src`, one after another, as a string of '0' / '1'"""
+    return "".join(map(_CODE_BITS.__getitem__, bytes(src)))
+
+
+def encode(src):
+    """h2o_hpack_encode_huffman (lib/http2/hpack.c:774-804) on the bit string: the codes MSB first, the last byte
+    filled with ones, and None (the call's SIZE_MAX) when the code needs more than len - 1 bytes -- also for len 0"""
+    bits = code_bits(src)
+    nbytes = (len(bits) + 7) // 8
+    if nbytes > len(src) - 1:
+        return None
+    bits += "1" * (8 * nbytes - len(bits))
+    return bytes(int(bits[p:p + 8], 2) for p in range(0, len(bits), 8))

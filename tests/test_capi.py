@@ -38,22 +38,23 @@ def test_library_is_gfx950_code_object():
 CAPI_CHECK = os.path.join(ROOT, "build", "capi_check")
 
 
-def build_capi_check():
-    """tests/capi_check.c: a C translation unit against include/hhuff.h, linked with libhhuff.so"""
+def build_capi_check(source="capi_check.c", target=None):
+    """tests/capi_check.c (or another C translation unit of tests/): built against include/hhuff.h and linked with
+    libhhuff.so -> the program's path (build/<the source's name without .c> unless `target` names another)"""
     import subprocess
 
     from h2o_amd import build
 
     build.build(verbose=False)
-    os.makedirs(os.path.dirname(CAPI_CHECK), exist_ok=True)
-    src = os.path.join(ROOT, "tests", "capi_check.c")
-    if not os.path.exists(CAPI_CHECK) or os.path.getmtime(CAPI_CHECK) < max(os.path.getmtime(src),
-                                                                            os.path.getmtime(build.LIB)):
+    exe = target or os.path.join(ROOT, "build", os.path.splitext(source)[0])
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    src = os.path.join(ROOT, "tests", source)
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(src), os.path.getmtime(build.LIB)):
         subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
-                        "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", src, "-o", CAPI_CHECK,
+                        "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", src, "-o", exe,
                         "-L" + os.path.dirname(build.LIB), "-lhhuff", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
                         "-Wl,-rpath," + os.path.dirname(build.LIB) + ":/opt/rocm/lib"], check=True)
-    return CAPI_CHECK
+    return exe
 
 
 def test_c_translation_unit_builds_and_links():
