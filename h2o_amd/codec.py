@@ -219,6 +219,11 @@ def lib():
         L.hhuff_h2_deframe.restype = ctypes.c_int
         L.hhuff_h2_deframe.argtypes = ([_vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp] + [ctypes.c_uint32] * 3 +
                                        [ctypes.c_uint] + [_vp] * 11 + [ctypes.c_uint64, ctypes.c_uint32, _vp])
+        L.hhuff_h2_control.restype = ctypes.c_int
+        L.hhuff_h2_control.argtypes = ([_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint,
+                                        ctypes.c_uint32] + [_vp] * 7 + [ctypes.c_uint64, _vp, _vp, _vp])
+        L.hhuff_hpack_responses_set_peers.restype = ctypes.c_int
+        L.hhuff_hpack_responses_set_peers.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
         L.hhuff_h3_deframe.restype = ctypes.c_int
         L.hhuff_h3_deframe.argtypes = ([_vp, ctypes.c_uint64] + [_vp, ctypes.c_uint32] * 3 + [ctypes.c_uint64, ctypes.c_uint] +
                                        [_vp] * 19 + [ctypes.c_uint64, ctypes.c_uint32, _vp])
@@ -245,7 +250,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
             "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers", "hhuff_tokens_table_size", "hhuff_tokens_build",
             "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
-            "hhuff_h3_deframe") + SLOTS_SYMBOLS
+            "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -973,6 +978,78 @@ def h2_deframe(data, in_off, frm_first, frm_cap, max_frame_size=16384, max_block
                                   _dp(r["blocks"]), _dp(r["totals"]), _dp(r.get("arena_off")), arena_fixed or 0,
                                   arena_per_byte, _stream(stream)), "hhuff_h2_deframe")
     return r
+
+
+# include/hhuff.h (2k'): hhuff_h2_peer_t / hhuff_h2_ctl_t as numpy records, and the section's constants
+H2_PEER_DTYPE = np.dtype([("header_table_size", "<u4"), ("enable_push", "<u4"), ("max_concurrent_streams", "<u4"),
+                          ("initial_window_size", "<u4"), ("max_frame_size", "<u4"), ("flags", "<u4"), ("send_window", "<i8"),
+                          ("recv_window", "<i8")])
+H2_CTL_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("status", "<i4"), ("err", "<u2"), ("flags", "u1"), ("reply_len", "u1")])
+H2_PEER_INIT = (4096, 1, 0xFFFFFFFF, 65535, 16384, 0, 65535, 65535)  # HHUFF_H2_PEER_INIT
+H2C_CLIENT = 1
+H2C_SPACE, H2C_EINVAL = -312, -313
+ERR_FLOW_CONTROL = -3  # H2O_HTTP2_ERROR_FLOW_CONTROL (ERR_PROTOCOL, ERR_FRAME_SIZE: above)
+H2P_SETTINGS, H2P_GOAWAY = 1, 2
+H2R_ACK, H2R_NEEDS_STREAM, H2R_STREAM_ERROR, H2R_WINDOW_DELTA, H2R_WINDOW_UPDATE = 1, 2, 4, 8, 16
+(H2C_ERR_NONE, H2C_ERR_DATA_STREAM_ID, H2C_ERR_DATA_FRAME, H2C_ERR_PRIORITY_STREAM_ID, H2C_ERR_PRIORITY_FRAME,
+ H2C_ERR_SELF_DEPENDENCY, H2C_ERR_RST_STREAM_STREAM_ID, H2C_ERR_RST_STREAM_FRAME, H2C_ERR_SETTINGS_STREAM_ID,
+ H2C_ERR_SETTINGS_ACK, H2C_ERR_SETTINGS_FRAME, H2C_ERR_SETTINGS_SIZE, H2C_ERR_PING_FRAME, H2C_ERR_GOAWAY_STREAM_ID,
+ H2C_ERR_GOAWAY_FRAME, H2C_ERR_WINDOW_UPDATE_FRAME, H2C_ERR_FLOW_CONTROL) = range(17)
+H2O_CONNECTION_WINDOW_SIZE = 16777216  # the server's recv_window_size (H2O_HTTP2_SETTINGS_HOST_CONNECTION_WINDOW_SIZE)
+
+
+def h2_control_reply_bound(slots):
+    """include/hhuff.h hhuff_h2_control_reply_bound"""
+    return 17 * slots
+
+
+def h2_new_peers(nconn, device=None):
+    """nconn records of HHUFF_H2_PEER_INIT: a numpy array of H2_PEER_DTYPE, or with `device` a uint8 tensor there"""
+    p = np.empty(nconn, H2_PEER_DTYPE)
+    p[:] = H2_PEER_INIT
+    if device is None:
+        return p
+    import torch
+
+    return torch.from_numpy(p.view(np.uint8).copy()).to(device)
+
+
+def h2_control(data, frames, nframes, frm_first, frm_cap, peers, rep_off, flags=0, recv_window_size=0, in_size=None,
+               rep_size=None, stream=None, out=None):
+    """HTTP/2 control frames (include/hhuff.h hhuff_h2_control) on device tensors: data, frames, nframes, frm_first and
+    frm_cap are h2_deframe's; peers a uint8 tensor of H2_PEER_DTYPE records (h2_new_peers), rep_off int32 (u32 bits) of
+    nconn + 1 entries.  Returns a dict of device tensors: ctl (uint8, H2_CTL_DTYPE records, one per frame slot), nctl,
+    cstatus, cerr, rep_len (per connection), rep and peers (the records to present next time: a new tensor unless
+    out={"peers": peers} updates in place).  out: a dict with some of these tensors preallocated.  No host
+    synchronisation (rep_size given, or rep preallocated)."""
+    import torch
+
+    dev = data.device
+    in_size = data.numel() if in_size is None else in_size
+    nconn = frm_first.numel() - 1
+    out = dict(out or {})
+    if "rep" not in out and rep_size is None:
+        rep_size = int(rep_off[-1].item()) & 0xFFFFFFFF
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32, u8 = torch.int32, torch.uint8
+    r = dict(ctl=new("ctl", frm_cap * 16, u8), nctl=new("nctl", nconn, i32), cstatus=new("cstatus", nconn, i32),
+             cerr=new("cerr", nconn, i32), rep_len=new("rep_len", nconn, i32), rep=new("rep", rep_size or 0, u8),
+             peers=new("peers", nconn * 40, u8))
+    if rep_size is None:
+        rep_size = r["rep"].numel()
+    _check(lib().hhuff_h2_control(_dp(data), in_size, _dp(frames), _dp(nframes), _dp(frm_first), frm_cap, nconn, flags,
+                                  recv_window_size, _dp(peers), _dp(r["peers"]), _dp(r["ctl"]), _dp(r["nctl"]),
+                                  _dp(r["cstatus"]), _dp(r["cerr"]), _dp(r["rep"]), rep_size, _dp(rep_off), _dp(r["rep_len"]),
+                                  _stream(stream)), "hhuff_h2_control")
+    return r
+
+
+def hpack_responses_set_peers(peers, res, conn_first, nres, stream=None):
+    """include/hhuff.h hhuff_hpack_responses_set_peers: the peers' header_table_size and max_frame_size (uint8 tensor of
+    H2_PEER_DTYPE records) into the HPE_RESPONSE_DTYPE records `res` (uint8 tensor), in place; conn_first int32 (u32
+    bits) [nconn + 1]"""
+    _check(lib().hhuff_hpack_responses_set_peers(_dp(peers), _dp(res), _dp(conn_first), conn_first.numel() - 1, nres,
+                                                 _stream(stream)), "hhuff_hpack_responses_set_peers")
 
 
 # include/hhuff.h (2l): hhuff_h3_stream_t / hhuff_h3_frame_t / hhuff_h3_settings_t as numpy records (peers: QPACK_PEER), and

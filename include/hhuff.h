@@ -1218,6 +1218,149 @@ int hhuff_h2_deframe(const uint8_t *in, uint64_t in_size,            /* in_size 
                      uint32_t *totals /* [2]: nblk, block bytes */,
                      uint64_t *arena_off, uint64_t arena_fixed, uint32_t arena_per_byte, void *stream);
 
+/* (2k') HTTP/2 control frames: the payload rules of the frames (2k) steps over, the peer's SETTINGS, the connection
+ *      windows and the replies h2o queues, for many connections at once.  h2o_http2_decode_data_payload,
+ *      _priority_payload, _rst_stream_payload, _ping_payload, _goaway_payload, _window_update_payload and
+ *      h2o_http2_update_peer_settings (lib/http2/frame.c:37-66, 152-177, 226-310), h2o_http2_window_update
+ *      (include/h2o/http2_common.h:234-241), the reply layouts of frame.c:68-122, and what handle_settings_frame,
+ *      handle_ping_frame, handle_window_update_frame, handle_priority_frame, handle_goaway_frame and handle_data_frame
+ *      do without a stream (lib/http2/connection.c:976-989, 1097-1108, 1151-1261; the client's twins,
+ *      lib/common/http2client.c:662-871).
+ *        in, in_size, frames, nframes, frm_first, frm_cap, nconn   hhuff_h2_deframe's, as they are and on the same stream
+ *        flags              HHUFF_H2C_CLIENT: the client's handlers (they differ from the server's in the receive window)
+ *        recv_window_size   the server's H2O_HTTP2_SETTINGS_HOST_CONNECTION_WINDOW_SIZE; 0: no receive window kept
+ *        peers_in, peers_out   one hhuff_h2_peer_t per connection: the caller's between steps (peers_out may be
+ *                           peers_in); a new connection starts from HHUFF_H2_PEER_INIT
+ *        ctl                ctl[frm_first[c] + i], i < nframes[c]: frame i's record, at the frame record's index; the
+ *                           other slots are not written
+ *        rep, rep_off       connection c's replies go to rep[rep_off[c] .. rep_off[c+1]), clamped to rep_size;
+ *                           hhuff_h2_control_reply_bound(slots of the connection) always fits
+ *      Per connection: nctl[c], the frames handled; cstatus[c] / cerr[c], the first connection-level failure in wire
+ *      order (h2o's return value and the HHUFF_H2C_ERR_* that names its err_desc, or HHUFF_H2C_SPACE / _EINVAL);
+ *      rep_len[c], the reply bytes written; peers_out[c].
+ *      A connection's frames are handled in wire order by these rules, each in h2o's order of tests (NEEDS_STREAM etc.:
+ *      the record's HHUFF_H2R_* flags; a failing frame's record has status and err, SETTINGS also a, and zeros else):
+ *        DATA (0)           stream id 0: -1 (_DATA_STREAM_ID); PADDED with length 0 or length < 1 + pad: -1
+ *                           (_DATA_FRAME); else a = the data's offset in `in`, b = its length (may be 0), NEEDS_STREAM.
+ *                           Server with recv_window_size != 0: recv_window -= length (padding included); at
+ *                           recv_window <= recv_window_size / 2 a WINDOW_UPDATE on stream 0 carrying recv_window_size -
+ *                           recv_window (its low 32 bits) is owed, recv_window = recv_window_size, flag WINDOW_UPDATE
+ *                           (connection.c:986-989).  h2o's client consumes its connection window only behind the
+ *                           stream lookups (http2client.c:516-519, 585, 599): with HHUFF_H2C_CLIENT recv_window is left
+ *                           alone and that window is the caller's.
+ *        PRIORITY (2)       stream id 0: -1 (_PRIORITY_STREAM_ID); length != 5: -6 (_PRIORITY_FRAME); dependency ==
+ *                           stream id: -1 (_SELF_DEPENDENCY, both h2o sides); else a = exclusive << 31 | dependency,
+ *                           b = weight 1..256, NEEDS_STREAM
+ *        RST_STREAM (3)     stream id 0: -1 (_RST_STREAM_STREAM_ID); length != 4: -6 (_RST_STREAM_FRAME); else a =
+ *                           the error code, NEEDS_STREAM (the idle-id test is the caller's)
+ *        SETTINGS (4)       stream id != 0: -1 (_SETTINGS_STREAM_ID); ACK with length != 0: -6 (_SETTINGS_ACK); ACK
+ *                           with length 0: flag ACK.  Without ACK, h2o_http2_update_peer_settings pair by pair:
+ *                           ENABLE_PUSH above 1 and MAX_FRAME_SIZE outside 16384 .. 16777215 are -1,
+ *                           INITIAL_WINDOW_SIZE above 0x7fffffff is -3 (_SETTINGS_FRAME each); unknown identifiers
+ *                           are skipped, the last of a repeated one wins; a length that is no multiple of 6 applies
+ *                           every whole pair and is then -6 (_SETTINGS_SIZE: h2o sets no err_desc).  An error leaves
+ *                           the earlier pairs of the frame applied, as h2o does.  a = the whole pairs read without
+ *                           error; on success b = the int32 change of initial_window_size this frame made (flag
+ *                           WINDOW_DELTA when b != 0: the caller adds it to every stream's send window), a SETTINGS
+ *                           ACK (9 bytes) is owed and peers_out[c].flags gets HHUFF_H2P_SETTINGS
+ *        PING (6)           stream id != 0: -1; length != 8: -6 (both _PING_FRAME, h2o's one text); else a, b = the
+ *                           opaque bytes 0-3 and 4-7, big-endian, flag ACK copied from the frame; without ACK a PING
+ *                           with ACK and the same 8 bytes (17 bytes) is owed
+ *        GOAWAY (7)         stream id != 0: -1 (_GOAWAY_STREAM_ID); length < 8: -6 (_GOAWAY_FRAME); else a =
+ *                           last_stream_id & 0x7fffffff, b = the error code, peers_out[c].flags gets HHUFF_H2P_GOAWAY;
+ *                           the debug data stays where the frame record says (payload_off + 8)
+ *        WINDOW_UPDATE (8)  length != 4: -6; increment (& 0x7fffffff) 0 on stream 0: -1 (both _WINDOW_UPDATE_FRAME,
+ *                           connection level).  Increment 0 on a stream is h2o's stream-level error: the record has
+ *                           status -1, _WINDOW_UPDATE_FRAME and STREAM_ERROR | NEEDS_STREAM (the caller resets the
+ *                           stream), a RST_STREAM(PROTOCOL_ERROR) on that stream (13 bytes) is owed, the connection's
+ *                           own status stays 0 and the walk goes on.  Increment > 0 on stream 0: send_window +
+ *                           increment > INT32_MAX is -3 (_FLOW_CONTROL), else send_window += increment; a = the
+ *                           increment.  Increment > 0 on a stream: a = the increment, NEEDS_STREAM.
+ *        HEADERS, PUSH_PROMISE, CONTINUATION, any type >= 10   the record is zeroed (expect_default,
+ *                           connection.c:1320-1326, ignores unknown types; header frames are (2k)'s)
+ *      The walk of a connection stops at its first connection-level failure: nctl[c] counts the frames in front of
+ *      it, the failing frame's record (slot nctl[c]) is the last one written -- not written for HHUFF_H2C_SPACE and
+ *      HHUFF_H2C_EINVAL --, and peers_out[c] is what h2o's conn->peer_settings and windows hold at the moment its
+ *      handler returns the error, the partially applied SETTINGS frame included.  Without failure nctl[c] =
+ *      nframes[c].  A control failure precedes any failure the de-framer reported for the connection, since every
+ *      listed frame lies in front of the point where the de-framer stopped; header blocks with first_frame >=
+ *      frm_first[c] + nctl[c] belong to a connection h2o would already have closed.
+ *      Replies are written in wire order, for the frames in front of the failure, exactly as h2o queues them on
+ *      conn->_write.buf; a record's reply_len is what its frame added.  A region that cannot take a frame's reply
+ *      stops the connection in front of that frame with HHUFF_H2C_SPACE, nothing of the frame applied.
+ *      Checks that need stream state stay with the caller, as in (2k): idle and closed stream ids, stream windows,
+ *      max_streams_for_priority, all handle_data_frame does behind the connection window.  NEEDS_STREAM marks the
+ *      records the caller has to look at.
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array, in_size >= 2^32, an unknown
+ *      flag bit or recv_window_size > INT32_MAX; nconn == 0 returns HHUFF_OK.  Asynchronous on `stream`, no host
+ *      synchronisation, no workspace, no atomics; bitwise deterministic.  frames[] and nframes[] are not trusted:
+ *      nframes[c] is clamped to the connection's slots and the slots to frm_cap; a record whose payload leaves
+ *      in[0 .. in_size) stops its connection with HHUFF_H2C_EINVAL.  Of `in` the call reads payload bytes only. */
+typedef struct hhuff_h2_peer {       /* 40 bytes, 8-byte aligned */
+    uint32_t header_table_size, enable_push, max_concurrent_streams, initial_window_size, max_frame_size;
+                                     /* conn->peer_settings */
+    uint32_t flags;                  /* HHUFF_H2P_* */
+    int64_t  send_window;            /* conn->_write.window; the caller subtracts the DATA it sends */
+    int64_t  recv_window;            /* conn->_input_window (server, recv_window_size != 0), else untouched */
+} hhuff_h2_peer_t;
+/* a new connection: H2O_HTTP2_SETTINGS_DEFAULT, both windows 65535 */
+#define HHUFF_H2_PEER_INIT { 4096u, 1u, 0xFFFFFFFFu, 65535u, 16384u, 0u, 65535, 65535 }
+typedef struct hhuff_h2_ctl {        /* 16 bytes: one per frame record */
+    uint32_t a, b;
+    int32_t  status;                 /* h2o's return value for this frame */
+    uint16_t err;                    /* HHUFF_H2C_ERR_* */
+    uint8_t  flags;                  /* HHUFF_H2R_* */
+    uint8_t  reply_len;              /* reply bytes this frame added */
+} hhuff_h2_ctl_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h2_peer_t) == 40 && sizeof(hhuff_h2_ctl_t) == 16, "record sizes");
+#else
+typedef char hhuff_h2_control_record_sizes[sizeof(hhuff_h2_peer_t) == 40 && sizeof(hhuff_h2_ctl_t) == 16 ? 1 : -1];
+#endif
+#define HHUFF_H2C_CLIENT 1u           /* flags: the client's handlers */
+#define HHUFF_H2C_SPACE (-312)        /* cstatus: the reply region cannot take the next frame's reply */
+#define HHUFF_H2C_EINVAL (-313)       /* cstatus: a frame record's payload leaves in[0 .. in_size) */
+#define HHUFF_H2P_SETTINGS 1u         /* peer flags: a SETTINGS without ACK has been applied */
+#define HHUFF_H2P_GOAWAY 2u           /* a GOAWAY has arrived */
+#define HHUFF_H2R_ACK 1u              /* record flags: SETTINGS / PING with ACK */
+#define HHUFF_H2R_NEEDS_STREAM 2u     /* the caller's stream-state checks and actions remain */
+#define HHUFF_H2R_STREAM_ERROR 4u     /* status is a stream-level error: RST_STREAM written, the walk went on */
+#define HHUFF_H2R_WINDOW_DELTA 8u     /* SETTINGS: b is to be added to every stream's send window */
+#define HHUFF_H2R_WINDOW_UPDATE 16u   /* DATA: a connection-level WINDOW_UPDATE was written */
+#define HHUFF_H2C_ERR_NONE 0u
+#define HHUFF_H2C_ERR_DATA_STREAM_ID 1u        /* "invalid stream id in DATA frame" */
+#define HHUFF_H2C_ERR_DATA_FRAME 2u            /* "invalid DATA frame" */
+#define HHUFF_H2C_ERR_PRIORITY_STREAM_ID 3u    /* "invalid stream id in PRIORITY frame" */
+#define HHUFF_H2C_ERR_PRIORITY_FRAME 4u        /* "invalid PRIORITY frame" */
+#define HHUFF_H2C_ERR_SELF_DEPENDENCY 5u       /* "stream cannot depend on itself" */
+#define HHUFF_H2C_ERR_RST_STREAM_STREAM_ID 6u  /* "invalid stream id in RST_STREAM frame" */
+#define HHUFF_H2C_ERR_RST_STREAM_FRAME 7u      /* "invalid RST_STREAM frame" */
+#define HHUFF_H2C_ERR_SETTINGS_STREAM_ID 8u    /* "invalid stream id in SETTINGS frame" */
+#define HHUFF_H2C_ERR_SETTINGS_ACK 9u          /* "invalid SETTINGS frame (+ACK)" */
+#define HHUFF_H2C_ERR_SETTINGS_FRAME 10u       /* "invalid SETTINGS frame" */
+#define HHUFF_H2C_ERR_SETTINGS_SIZE 11u        /* a length that is no multiple of 6 (h2o: -6 without err_desc) */
+#define HHUFF_H2C_ERR_PING_FRAME 12u           /* "invalid PING frame" */
+#define HHUFF_H2C_ERR_GOAWAY_STREAM_ID 13u     /* "invalid stream id in GOAWAY frame" */
+#define HHUFF_H2C_ERR_GOAWAY_FRAME 14u         /* "invalid GOAWAY frame" */
+#define HHUFF_H2C_ERR_WINDOW_UPDATE_FRAME 15u  /* "invalid WINDOW_UPDATE frame" */
+#define HHUFF_H2C_ERR_FLOW_CONTROL 16u         /* "flow control window overflow" */
+static inline uint64_t hhuff_h2_control_reply_bound(uint64_t slots) { return 17u * slots; }
+int hhuff_h2_control(const uint8_t *in, uint64_t in_size,            /* in_size < 2^32 */
+                     const hhuff_h2_frame_t *frames, const uint32_t *nframes,
+                     const uint32_t *frm_first, uint32_t frm_cap, uint32_t nconn,
+                     unsigned flags, uint32_t recv_window_size,
+                     const hhuff_h2_peer_t *peers_in, hhuff_h2_peer_t *peers_out,
+                     hhuff_h2_ctl_t *ctl, uint32_t *nctl, int32_t *cstatus, uint32_t *cerr,
+                     uint8_t *rep, uint64_t rep_size, const uint32_t *rep_off /* [nconn + 1] */, uint32_t *rep_len,
+                     void *stream);
+/* The peers' settings into the HPACK encoder's response records: res[r].header_table_size =
+ * peers[c].header_table_size and res[r].max_frame_size = peers[c].max_frame_size for every response r of connection c
+ * (conn_first[c] .. conn_first[c+1] - 1, clamped to nres), one lane per response; no other byte of a record is
+ * written.  With it a step's SETTINGS reach hhuff_hpack_flatten_responses and its _slots form without the host.
+ * Device arrays; HHUFF_EINVAL for a NULL array, nconn == 0 or nres == 0 returns HHUFF_OK; asynchronous on `stream`. */
+int hhuff_hpack_responses_set_peers(const hhuff_h2_peer_t *peers, hhuff_hpack_response_t *res,
+                                    const uint32_t *conn_first, uint32_t nconn, uint32_t nres, void *stream);
+
 /* (2l) HTTP/3 frames on the receive side: the bytes of many connections' QUIC streams -> the encoder-stream bytes
  *      and field sections the decoders of (2d) take, and the peers' SETTINGS.  One call is one step of every stream.
  *      It follows h2o_http3_read_frame (lib/http3/common.c:1057-1145), the request-stream handlers of h2o's server
