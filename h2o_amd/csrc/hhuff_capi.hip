@@ -1,6 +1,6 @@
 // hhuff C-ABI shim (include/hhuff.h): argument checks, stream plumbing, the per-string h2o symbols
-// and the host-array batch entry points.  All compute goes through the HIP kernels in
-// hhuff_kernels.hip; there is no CPU codec in this library.
+// and the host-array batch entry points.  All compute goes through the HIP kernels (hhuff_kernels.hip the batch
+// codec and the per-string calls, hhuff_literals.hip, the header-block units); there is no CPU codec in this library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1846,6 +1846,10 @@ HHUFF_API int hhuff_set_decode_kernel(int mode) {
 }
 
 HHUFF_API uint32_t hhuff_set_edge_defer_min(uint32_t n) { return hhuff::set_edge_defer_min(n); }
+
+HHUFF_API int hhuff_debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n) {
+    return hhuff::debug_encode_blocks_per_cu(in_size, n);
+}
 
 HHUFF_API int hhuff_grid_size(int device, int which) {
     DeviceGuard guard(device);

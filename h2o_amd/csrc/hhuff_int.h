@@ -1,5 +1,5 @@
 // The HPACK / QPACK prefix integer on the receive side: h2o_hpack_decode_int (lib/http2/hpack.c:52-83), the one
-// definition the header-block decoders (hhuff_blocks.hip, hhuff_qpack.hip), the literal kernels (hhuff_kernels.hip),
+// definition the header-block decoders (hhuff_blocks.hip, hhuff_qpack.hip), the literal kernels (hhuff_literals.hip),
 // the QPACK encoder sessions' decoder stream (hhuff_qpenc.hip) and the host program tools/int_host.cpp run.  It reads
 // bytes[p .. end) and nothing else.
 #ifndef HHUFF_INT_H

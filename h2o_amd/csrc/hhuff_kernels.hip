@@ -1,4 +1,5 @@
-// hhuff HIP kernels for gfx950 (MI355X) and their launchers.
+// hhuff HIP kernels for gfx950 (MI355X) and their launchers: the batch codec and the per-string kernels (the header
+// literals are in hhuff_literals.hip).
 //
 // Work decomposition (both directions): one lane per string, 64 consecutive strings per wave
 // ("tile"), waves grid-stride over the batch.  Staged variant: a wave copies its tile's input span
@@ -2636,212 +2637,6 @@ __global__ __launch_bounds__(WAVES * 64) void flatten_pl_kernel(FlatArgs A, uint
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// String literals in header blocks: HPACK decode_string (hpack.c:223-261) and QPACK
-// decode_header_{name,value}_literal (qpack.c:559-629).  Literal i starts at in[lit_off[i]]: the H flag
-// at bit prefix_bits of that byte, the length as a prefix integer (h2o_hpack_decode_int, hpack.c:52-83),
-// then the payload, all before in[lit_end[i]].  Three launches: parse the headers (payload offset and
-// Huffman length per literal), the Huffman decode kernel over (payload, length) pairs, then a fix-up
-// that validates and copies the raw literals (h2o_hpack_validate_header_name / _value, hpack.c:163-221)
-// and folds the header verdicts into out_len / status.
-// ------------------------------------------------------------------------------------------------
-struct LitArgs {
-    const uint8_t* in;
-    uint64_t in_size;
-    const uint32_t* lit_off;
-    const uint32_t* lit_end;
-    uint32_t n;
-    uint32_t prefix_bits;
-    uint32_t flags;
-    const uint32_t* is_name_bits;
-    uint8_t* out;
-    uint32_t* out_len;
-    uint32_t* pay_off;
-    uint32_t* consumed;
-    uint8_t* status;
-    uint32_t* huff_len;  // workspace: Huffman payload length (0 for raw literals and errors)
-    uint8_t* code;       // workspace: verdict | H flag << 3 | soft bits << 4
-    const uint32_t* n_dev;  // NULL, or the literal count in device memory (n is then an upper bound)
-    uint32_t* long_list;    // NULL, or: raw payloads longer than kLongRaw are validated by literal_long_kernel
-    uint32_t* long_count;
-    const uint8_t* prefix_of;  // NULL, or each literal's own prefix_bits
-};
-
-constexpr uint32_t kLongRaw = 512;  // raw payload bytes above which one wave validates the literal
-
-enum : uint32_t { kLitIncomplete = 1, kLitBadInt = 2, kLitTruncated = 3, kLitHuffman = 4, kLitUpper = 5, kLitTooLong = 6 };
-
-// header of literal i -> verdict (0 = ok); hdr = header bytes, len = payload bytes, huff = H flag
-__device__ __forceinline__ uint32_t lit_header(const LitArgs& A, uint32_t i, bool& huff, uint32_t& hdr, uint32_t& len) {
-    const uint64_t off = A.lit_off[i];
-    const uint64_t end = A.lit_end ? min((uint64_t)A.lit_end[i], A.in_size) : A.in_size;
-    huff = false;
-    hdr = 0;
-    len = 0;
-    if (off >= end) return kLitIncomplete;
-    const uint32_t p = A.prefix_of ? A.prefix_of[i] : A.prefix_bits;
-    const uint32_t b0 = A.in[off];
-    huff = ((b0 >> p) & 1u) != 0;
-    uint64_t q = off;
-    const int64_t n = hpack_int(A.in, q, end, p);
-    if (n < 0) return n == kIntIncomplete ? kLitIncomplete : kLitBadInt;
-    const uint64_t v = (uint64_t)n;
-    if (v > end - q) return kLitTruncated;
-    if (v > kMaxStrLen) return kLitTooLong;
-    hdr = (uint32_t)(q - off);
-    len = (uint32_t)v;
-    return 0;
-}
-
-// Pass 1: headers; raw payloads are validated and copied here (they skip the Huffman kernel, which
-// sees length 0 for them).  code[i] = verdict | H flag << 3 | soft bits << 4 for the fix-up.
-__global__ void literal_parse_kernel(LitArgs A) {
-    const uint64_t n = A.n_dev ? (uint64_t)*A.n_dev : (uint64_t)A.n;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        bool huff;
-        uint32_t hdr, len;
-        uint32_t v = lit_header(A, (uint32_t)i, huff, hdr, len);
-        uint32_t soft = 0;
-        if (v == 0 && !huff && A.long_list && len > kLongRaw) {  // one lane would walk it alone: defer
-            A.long_list[atomicAdd(A.long_count, 1u)] = (uint32_t)i;
-        } else if (v == 0 && !huff) {
-            const bool is_name = A.is_name_bits ? ((A.is_name_bits[i >> 5] >> (i & 31)) & 1u) != 0 : false;
-            const uint64_t s0 = (uint64_t)A.lit_off[i] + hdr;
-            const uint8_t* src = A.in + s0;
-            const bool skip = is_name && ((A.flags & 1u) ? pseudo_token(src, len) : (len != 0 && src[0] == ':'));
-            const uint32_t* inval = is_name ? g_name_invalid : g_value_invalid;
-            uint8_t* dst = A.out + (s0 * 8u) / 5u;
-            // 16-byte aligned loads, four per round and no early exit: the loads of a long raw literal stay
-            // in flight together (and the blocks pipeline, kLitNoRawCopy, stores nothing in between)
-            const bool copy = !(A.flags & kLitNoRawCopy);
-            bool anybad = false, softbad = false, upper = false;
-            const uint64_t a0 = s0 & ~15ull, e0 = s0 + len;
-            for (uint64_t ar = a0; ar < e0; ar += 64) {
-                uint4 w4[4];
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) {
-                    const uint64_t a = ar + 16u * q;
-                    if (a + 16 <= A.in_size) {
-                        w4[q] = *reinterpret_cast<const uint4*>(A.in + a);
-                    } else {
-                        uint32_t w[4] = {0, 0, 0, 0};
-                        for (uint32_t k = 0; k < 16; ++k)
-                            if (a + k < A.in_size) w[k >> 2] |= (uint32_t)A.in[a + k] << (8 * (k & 3));
-                        w4[q] = make_uint4(w[0], w[1], w[2], w[3]);
-                    }
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) {
-                    const uint32_t wv[4] = {w4[q].x, w4[q].y, w4[q].z, w4[q].w};
-#pragma unroll
-                    for (uint32_t k = 0; k < 16; ++k) {
-                        const uint64_t pos = ar + 16u * q + k;
-                        if (pos < s0 || pos >= e0) continue;
-                        const uint32_t c = (wv[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                        const bool bad = ((inval[c >> 5] >> (c & 31)) & 1u) != 0;
-                        const bool up = bad && (c - 'A' < 26u);
-                        anybad |= bad;
-                        softbad |= bad && !up && !upper;  // names: only what precedes the first upper-case letter
-                        upper |= up;
-                        if (copy) dst[pos - s0] = (uint8_t)c;
-                    }
-                }
-            }
-            if (is_name) {
-                if (!skip) {  // h2o_hpack_validate_header_name: empty -> soft; upper case -> hard error
-                    soft = (len == 0 || softbad) ? 0x1 : 0u;
-                    if (upper) v = kLitUpper;
-                }
-            } else {  // h2o_hpack_validate_header_value, with the whitespace rule (hpack.c:110-115)
-                const bool ws = len != 0 && (src[0] == ' ' || src[0] == '\t' || src[len - 1] == ' ' || src[len - 1] == '\t');
-                soft = (anybad || ws) ? 0x2 : 0u;
-            }
-        }
-        A.pay_off[i] = A.lit_off[i] + hdr;
-        A.huff_len[i] = (v == 0 && huff) ? len : 0u;
-        A.consumed[i] = v == 0 ? hdr + len : 0u;
-        A.code[i] = (uint8_t)(v | (huff ? 8u : 0u) | (soft << 4));
-    }
-}
-
-// Long raw payloads (deferred by literal_parse_kernel): one wave per literal, 16 bytes per lane per round.  The
-// name rule needs the first upper-case letter's position (h2o_hpack_validate_header_name stops there, soft
-// errors count only before it), so lanes keep the first position of each kind and the wave takes minima.
-__global__ __launch_bounds__(256) void literal_long_kernel(LitArgs A) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t nl = *A.long_count;
-    const bool copy = !(A.flags & kLitNoRawCopy);
-    for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); w < nl; w += gridDim.x * 4u) {
-        const uint32_t i = A.long_list[w];
-        bool huff;
-        uint32_t hdr, len;
-        (void)lit_header(A, i, huff, hdr, len);  // verdict 0, raw: checked by the parse kernel
-        const bool is_name = A.is_name_bits ? ((A.is_name_bits[i >> 5] >> (i & 31)) & 1u) != 0 : false;
-        const uint64_t s0 = (uint64_t)A.lit_off[i] + hdr, e0 = s0 + len;
-        const uint8_t* src = A.in + s0;
-        const bool skip = is_name && ((A.flags & 1u) ? pseudo_token(src, len) : (len != 0 && src[0] == ':'));
-        const uint32_t* inval = is_name ? g_name_invalid : g_value_invalid;
-        uint8_t* dst = A.out + (s0 * 8u) / 5u;
-        uint32_t first_up = 0xFFFFFFFFu, first_soft = 0xFFFFFFFFu, anybad = 0;
-        for (uint64_t a = s0 + 16u * (uint32_t)lane; a < e0; a += 1024) {
-            uint8_t v[16];
-#pragma unroll
-            for (uint32_t k = 0; k < 16; ++k) v[k] = a + k < e0 ? A.in[a + k] : 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < 16; ++k) {
-                if (a + k >= e0) break;
-                const uint32_t c = v[k];
-                const bool bad = ((inval[c >> 5] >> (c & 31)) & 1u) != 0;
-                const bool up = bad && (c - 'A' < 26u);
-                const uint32_t pos = (uint32_t)(a + k - s0);
-                anybad |= bad ? 1u : 0u;
-                if (up) first_up = min(first_up, pos);
-                if (bad && !up) first_soft = min(first_soft, pos);
-                if (copy) dst[pos] = (uint8_t)c;
-            }
-        }
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            first_up = min(first_up, (uint32_t)__shfl_xor((int)first_up, d));
-            first_soft = min(first_soft, (uint32_t)__shfl_xor((int)first_soft, d));
-            anybad |= (uint32_t)__shfl_xor((int)anybad, d);
-        }
-        if (lane == 0) {
-            uint32_t v = 0, soft = 0;
-            if (is_name) {
-                if (!skip) {  // h2o_hpack_validate_header_name: empty -> soft; upper case -> hard error
-                    soft = first_soft < first_up ? 0x1u : 0u;
-                    if (first_up != 0xFFFFFFFFu) v = kLitUpper;
-                }
-            } else {  // h2o_hpack_validate_header_value, with the whitespace rule (hpack.c:110-115)
-                const bool ws = src[0] == ' ' || src[0] == '\t' || src[len - 1] == ' ' || src[len - 1] == '\t';
-                soft = (anybad || ws) ? 0x2u : 0u;
-            }
-            A.consumed[i] = v == 0 ? hdr + len : 0u;
-            A.code[i] = (uint8_t)(v | (soft << 4));
-        }
-    }
-}
-
-// Pass 3: fold the header / raw verdicts into out_len and status (the Huffman kernel ran in between).
-__global__ void literal_fix_kernel(LitArgs A) {
-    const uint64_t n = A.n_dev ? (uint64_t)*A.n_dev : (uint64_t)A.n;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t c = A.code[i];
-        const uint32_t v = c & 7u, soft = c >> 4;
-        if (v) {
-            A.out_len[i] = kFailLen;
-            A.status[i] = (uint8_t)(soft | kStatusFail | (v << 2));
-        } else if (!(c & 8u)) {
-            A.out_len[i] = A.consumed[i] - (A.pay_off[i] - A.lit_off[i]);
-            A.status[i] = (uint8_t)soft;
-        } else if (A.status[i] & kStatusFail) {  // h2o_hpack_decode_huffman returned SIZE_MAX
-            A.status[i] = (uint8_t)(kStatusFail | (kLitHuffman << 2));
-            A.consumed[i] = 0;
-        }
-    }
-}
-
 #if HHUFF_AB_VARIANTS  // A/B builds only (tools/ab.py build; include path tools/ab)
 #include "hhuff_ab_decoders.h"
 #endif
@@ -2892,24 +2687,27 @@ __global__ void literal_fix_kernel(LitArgs A) {
 #endif
 constexpr int kDecTWaves = HHUFF_DECT_W;
 constexpr int kEncOStr = HHUFF_ENCO_NS, kEncOThreads = HHUFF_ENCO_NS / HHUFF_ENCO_SPT;
-constexpr int kDecSWaves = 16, kEncSWaves = 16;
+// waves per workgroup: each constant is its kernel's template argument here and, times 64, the block size of its
+// row in kVariants below -- the one place a wave count is retuned
+constexpr int kDecSWaves = 16, kDecLWaves = 6, kDecDWaves = 4;
+constexpr int kEncSWaves = 16, kEncLWaves = 8, kEncDWaves = 4, kEncPWaves = 16;
+constexpr int kFlatDWaves = 4, kFlatPWaves = 16;
 #define DEC_S decode_staged_kernel<kDecSWaves, 3072, 4608, false>
-#define DEC_L decode_staged_kernel<6, 8192, 12928, false>
+#define DEC_L decode_staged_kernel<kDecLWaves, 8192, 12928, false>
 #define DEC_SP decode_staged_kernel<kDecSWaves, 3072, 4608, true>
-#define DEC_LP decode_staged_kernel<6, 8192, 12928, true>
-#define DEC_D decode_direct_kernel<4>
+#define DEC_LP decode_staged_kernel<kDecLWaves, 8192, 12928, true>
+#define DEC_D decode_direct_kernel<kDecDWaves>
 #define DEC_T decode_stream_kernel<kDecTWaves, HHUFF_DECT_NW, HHUFF_DECT_OUT, HHUFF_DECT_SEG>
 #define ENC_S encode_staged_kernel<kEncSWaves, 3584, false>
 #define ENC_O encode_sorted_kernel<kEncOStr, HHUFF_ENCO_CH, HHUFF_ENCO_SPT>
 #define ENC_OS five::encode_sorted_kernel<kEncOStr, HHUFF_ENCO_SMALL_CH, HHUFF_ENCO_SPT>
-#define ENC_L encode_staged_kernel<8, 8192, false>
+#define ENC_L encode_staged_kernel<kEncLWaves, 8192, false>
 #define ENC_SP encode_staged_kernel<kEncSWaves, 3584, true>
-#define ENC_LP encode_staged_kernel<8, 8192, true>
-#define ENC_D encode_direct_kernel<4>
-#define FLAT_D flatten_direct_kernel<4>
-#define ENC_P encode_pl_kernel<16, kPlStage>
-#define FLAT_P flatten_pl_kernel<16, kPlStage>
-#define FLAT_P_THREADS 1024
+#define ENC_LP encode_staged_kernel<kEncLWaves, 8192, true>
+#define ENC_D encode_direct_kernel<kEncDWaves>
+#define FLAT_D flatten_direct_kernel<kFlatDWaves>
+#define ENC_P encode_pl_kernel<kEncPWaves, kPlStage>
+#define FLAT_P flatten_pl_kernel<kFlatPWaves, kPlStage>
 
 // A/B builds only (tools/ab.py build; include path tools/ab): the kernels measured and not adopted, and the
 // definitions above that a build selecting one of them replaces
@@ -2920,43 +2718,58 @@ constexpr int kDecSWaves = 16, kEncSWaves = 16;
 enum Variant { kDecS, kDecL, kDecD, kEncS, kEncL, kEncD, kFlatD, kEncP, kFlatP, kDecT, kDecSP, kDecLP, kEncSP, kEncLP,
                kEncO, kEncOS, kNumVariants };
 
-static const void* variant_fn(int v) {
-    switch (v) {
-        case kDecS: return (const void*)DEC_S;
-        case kDecL: return (const void*)DEC_L;
-        case kDecSP: return (const void*)DEC_SP;
-        case kDecLP: return (const void*)DEC_LP;
-        case kEncSP: return (const void*)ENC_SP;
-        case kEncLP: return (const void*)ENC_LP;
-        case kDecD: return (const void*)DEC_D;
-        case kDecT: return (const void*)DEC_T;
-        case kEncS: return (const void*)ENC_S;
-        case kEncO: return (const void*)ENC_O;
-        case kEncOS: return (const void*)ENC_OS;
-        case kEncL: return (const void*)ENC_L;
-        case kFlatD: return (const void*)FLAT_D;
-        case kEncP: return (const void*)ENC_P;
-        case kFlatP: return (const void*)FLAT_P;
-        default: return (const void*)ENC_D;
-    }
+// One row per Variant, in the enum's order: the kernel (the DEC_* / ENC_* / FLAT_* macros, so an A/B build's
+// replacements land here) and its threads per block, from the constant the kernel's __launch_bounds__ is built from.
+// grid_for, the occupancy queries and every launch take both from here.  A row also names its Variant and its
+// kernel's parameter list (KernelSig), which the two launch helpers below check.
+using KernelFn = void (*)();
+template <class... P>
+struct KernelSig {  // one address per kernel parameter list
+    static constexpr char tag = 0;
+};
+struct VariantRow {
+    Variant v;
+    KernelFn fn;
+    int threads;
+    const char* sig;
+};
+template <class... P>
+static VariantRow variant_row(Variant v, void (*kernel)(P...), int threads) {
+    return {v, reinterpret_cast<KernelFn>(kernel), threads, &KernelSig<P...>::tag};
 }
-static int variant_threads(int v) {
-    switch (v) {
-        case kDecS:
-        case kDecSP: return kDecSWaves * 64;
-        case kDecT: return kDecTWaves * 64;
-        case kEncS:
-        case kEncSP: return kEncSWaves * 64;
-        case kDecL:
-        case kDecLP: return 384;
-        case kEncL:
-        case kEncLP: return 512;
-        case kEncO:
-        case kEncOS: return kEncOThreads;
-        case kEncP: return 1024;
-        case kFlatP: return FLAT_P_THREADS;
-        default: return 256;
-    }
+static const VariantRow kVariants[] = {
+    variant_row(kDecS, DEC_S, kDecSWaves * 64),    variant_row(kDecL, DEC_L, kDecLWaves * 64),
+    variant_row(kDecD, DEC_D, kDecDWaves * 64),    variant_row(kEncS, ENC_S, kEncSWaves * 64),
+    variant_row(kEncL, ENC_L, kEncLWaves * 64),    variant_row(kEncD, ENC_D, kEncDWaves * 64),
+    variant_row(kFlatD, FLAT_D, kFlatDWaves * 64), variant_row(kEncP, ENC_P, kEncPWaves * 64),
+    variant_row(kFlatP, FLAT_P, kFlatPWaves * 64), variant_row(kDecT, DEC_T, kDecTWaves * 64),
+    variant_row(kDecSP, DEC_SP, kDecSWaves * 64),  variant_row(kDecLP, DEC_LP, kDecLWaves * 64),
+    variant_row(kEncSP, ENC_SP, kEncSWaves * 64),  variant_row(kEncLP, ENC_LP, kEncLWaves * 64),
+    variant_row(kEncO, ENC_O, kEncOThreads),       variant_row(kEncOS, ENC_OS, kEncOThreads),
+};
+static_assert(sizeof(kVariants) / sizeof(kVariants[0]) == kNumVariants, "one row per Variant");
+// v's row; NULL if the rows' order has drifted from the enum's (every launch of v then fails)
+static const VariantRow* variant(int v) {
+    return v >= 0 && v < kNumVariants && kVariants[v].v == v ? &kVariants[v] : nullptr;
+}
+
+// Launch a kernel that the call site names, with the block size of its row: the arguments are checked against the
+// kernel's parameters by the compiler, as in a plain hipLaunchKernelGGL, and the kernel against the row here.
+template <class... P, class... Args>
+static hipError_t launch(void (*kernel)(P...), int v, int grid, hipStream_t stream, Args... args) {
+    const VariantRow* r = variant(v);
+    if (!r || r->fn != reinterpret_cast<KernelFn>(kernel)) return hipErrorInvalidDeviceFunction;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(r->threads), 0, stream, args...);
+    return hipGetLastError();
+}
+// Launch the variant a run-time choice picked among kernels that all take one KArgs and nothing else (named by the
+// caller, not deduced): the row's address is called as void (*)(KArgs) only if the row's kernel has that list.
+template <class KArgs>
+static hipError_t launch_as(int v, int grid, hipStream_t stream, const KArgs& A) {
+    const VariantRow* r = variant(v);
+    if (!r || r->sig != &KernelSig<KArgs>::tag) return hipErrorInvalidDeviceFunction;
+    hipLaunchKernelGGL(reinterpret_cast<void (*)(KArgs)>(r->fn), dim3(grid), dim3(r->threads), 0, stream, A);
+    return hipGetLastError();
 }
 
 static int grid_for(int v, int device, uint32_t n) {
@@ -2964,13 +2777,14 @@ static int grid_for(int v, int device, uint32_t n) {
     if (device < 0 || device >= 64) device = 0;
     if (cache[device][v] == 0) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, variant_fn(v), variant_threads(v), 0) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kVariants[v].fn, kVariants[v].threads,
+                                                         0) != hipSuccess ||
             per_cu < 1)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
         cache[device][v] = per_cu * cus;
     }
-    const uint64_t per_block = (uint64_t)variant_threads(v);
+    const uint64_t per_block = (uint64_t)kVariants[v].threads;
     const uint64_t blocks = ((uint64_t)n + per_block - 1) / per_block;
     const int g = cache[device][v];
     return (int)(blocks < (uint64_t)g ? (blocks ? blocks : 1) : g);
@@ -3077,6 +2891,26 @@ static hipError_t pool_alloc(void** p, uint64_t bytes, hipStream_t stream) {
     }
     return hipMallocFromPoolAsync(p, bytes, pool, stream);
 }
+// Owner of one stream-ordered allocation from that pool: freed on the stream it was allocated on, by release() --
+// which folds the free's error into a launcher's result, first error wins -- or when the owner goes out of scope.
+template <class T>
+struct Scratch {
+    T* p = nullptr;
+    hipStream_t stream = nullptr;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { (void)release(hipSuccess); }
+    hipError_t alloc(uint64_t count, hipStream_t s) {
+        stream = s;
+        return pool_alloc((void**)&p, count * sizeof(T), s);
+    }
+    hipError_t release(hipError_t e) {
+        const hipError_t f = p ? hipFreeAsync(p, stream) : hipSuccess;
+        p = nullptr;
+        return e != hipSuccess ? e : f;
+    }
+};
 // Edge records and edge_fix_kernel for batches of at least this many strings; below it the codec kernels store
 // their regions' shared 16-B chunks themselves, one byte a lane (edge_bytes).  Default: never deferred -- the
 // byte-lane edges measured c4 decode -5.5 %, c3 encode -5.3 %, c5 encode -5.6 %, flatten -6.6 %, c2 decode -9 %
@@ -3088,22 +2922,17 @@ static hipError_t pool_alloc(void** p, uint64_t bytes, hipStream_t stream) {
 static std::atomic<uint32_t> g_defer_min{HHUFF_DEFER_MIN};
 uint32_t set_edge_defer_min(uint32_t n) { return g_defer_min.exchange(n); }
 static bool defer_edges(uint32_t n) { return n >= g_defer_min.load(std::memory_order_relaxed); }
-static hipError_t alloc_edges(EdgeRec** p, uint32_t n, hipStream_t stream) {
-    return pool_alloc((void**)p, edge_recs(n) * sizeof(EdgeRec), stream);
-}
 
-// after a staged kernel launched with deferred edges: write them, release the records (stream order)
-static hipError_t finish_deferred(uint8_t* out, EdgeRec* edges, uint32_t n, hipStream_t stream,
+// after a staged kernel launched with deferred edges: write them; the records' owner releases them behind this
+// (stream order)
+static hipError_t finish_deferred(uint8_t* out, const EdgeRec* edges, uint32_t n, hipStream_t stream,
                                   const uint32_t* gate = nullptr, uint64_t recs = 0) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        const uint64_t nrec = recs ? recs : edge_recs(n);
-        const uint32_t blocks = (uint32_t)min((4 * nrec + 255) / 256, (uint64_t)8192);
-        hipLaunchKernelGGL(edge_fix_kernel, dim3(blocks), dim3(256), 0, stream, out, edges, nrec, gate);
-        e = hipGetLastError();
-    }
-    const hipError_t f = hipFreeAsync(edges, stream);
-    return e != hipSuccess ? e : f;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint64_t nrec = recs ? recs : edge_recs(n);
+    const uint32_t blocks = (uint32_t)min((4 * nrec + 255) / 256, (uint64_t)8192);
+    hipLaunchKernelGGL(edge_fix_kernel, dim3(blocks), dim3(256), 0, stream, out, edges, nrec, gate);
+    return hipGetLastError();
 }
 
 static bool use_pl_encode(uint64_t in_size, uint32_t n) {
@@ -3169,12 +2998,10 @@ static void calibrate_prices(int dev) {
             float best = 1e30f;
             for (int r = 0; ok && r < 4; ++r) {
                 ok = hipMemsetAsync(ctr, 0, 8, s) == hipSuccess && hipEventRecord(e0, s) == hipSuccess;
-                if (k == 0)
-                    hipLaunchKernelGGL(DEC_L, dim3(grid_for(kDecL, dev, kN[p])), dim3(384), 0, s, A);
-                else
-                    hipLaunchKernelGGL(DEC_T, dim3(grid_for(kDecT, dev, kN[p])), dim3(kDecTWaves * 64), 0, s, A, ctr);
+                const hipError_t le = k == 0 ? launch(DEC_L, kDecL, grid_for(kDecL, dev, kN[p]), s, A)
+                                             : launch(DEC_T, kDecT, grid_for(kDecT, dev, kN[p]), s, A, ctr);
                 float ms = 0.f;
-                ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(e1, s) == hipSuccess &&
+                ok = ok && le == hipSuccess && hipEventRecord(e1, s) == hipSuccess &&
                      hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
                 if (r > 0) best = std::min(best, ms);  // r == 0 warms up
             }
@@ -3257,66 +3084,69 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
     const int v = pick_decode(sel_bytes ? sel_bytes : in_size, n);
     const int grid = grid_for(v, current_device(), n);
     const bool defer = (v == kDecS || v == kDecL) && in_len == nullptr && out_off == nullptr && defer_edges(n);
+    Scratch<EdgeRec> edges;
     if (v == kDecL) {  // mixed lengths: the device picks staged or stream (see below)
         prices_in_effect(current_device(), A.price);  // no GPU work: see calibrate_prices
-        uint64_t* sel = nullptr;  // [0, 3 kSelBlocks): partial sums; then the verdict and the work counter
-        hipError_t e = pool_alloc((void**)&sel, (3 * kSelBlocks + 2) * sizeof(uint64_t), stream);
+        Scratch<uint64_t> sel;  // [0, 3 kSelBlocks): partial sums; then the verdict and the work counter
+        hipError_t e = sel.alloc(3 * kSelBlocks + 2, stream);
         if (e != hipSuccess) return e;
-        A.sel = sel;
-        A.gate = reinterpret_cast<uint32_t*>(sel + 3 * kSelBlocks);
-        unsigned long long* ctr = reinterpret_cast<unsigned long long*>(sel + 3 * kSelBlocks + 1);
-        hipLaunchKernelGGL(decode_select_kernel, dim3(kSelBlocks), dim3(64), 0, stream, A, sel, ctr);
+        A.sel = sel.p;
+        A.gate = reinterpret_cast<uint32_t*>(sel.p + 3 * kSelBlocks);
+        unsigned long long* ctr = reinterpret_cast<unsigned long long*>(sel.p + 3 * kSelBlocks + 1);
+        hipLaunchKernelGGL(decode_select_kernel, dim3(kSelBlocks), dim3(64), 0, stream, A, sel.p, ctr);
         e = hipGetLastError();
-        if (e == hipSuccess && defer) {
-            e = alloc_edges(&A.edges, n, stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(DEC_L, dim3(grid), dim3(384), 0, stream, A);
-                e = finish_deferred(out, A.edges, n, stream, A.gate);
-            }
-        } else if (e == hipSuccess) {
-            hipLaunchKernelGGL(DEC_L, dim3(grid), dim3(384), 0, stream, A);
-            e = hipGetLastError();
+        if (e == hipSuccess && defer) e = edges.alloc(edge_recs(n), stream);
+        if (e == hipSuccess) {
+            A.edges = edges.p;
+            e = launch(DEC_L, kDecL, grid, stream, A);
+            if (e == hipSuccess && defer) e = finish_deferred(out, edges.p, n, stream, A.gate);
         }
+        e = edges.release(e);
         if (e == hipSuccess) {
             A.edges = nullptr;
-            if (use_run() && in_len == nullptr && out_off == nullptr && A.n_dev == nullptr)
-                launch_run(A, grid_for(kDecT, current_device(), n), ctr, stream);
-            else
-                hipLaunchKernelGGL(DEC_T, dim3(grid_for(kDecT, current_device(), n)), dim3(kDecTWaves * 64), 0, stream,
-                                   A, ctr);
-            e = hipGetLastError();
+            const int tgrid = grid_for(kDecT, current_device(), n);
+            if (use_run() && in_len == nullptr && out_off == nullptr && A.n_dev == nullptr) {
+                launch_run(A, tgrid, ctr, stream);
+                e = hipGetLastError();
+            } else {
+                e = launch(DEC_T, kDecT, tgrid, stream, A, ctr);
+            }
         }
-        const hipError_t f = hipFreeAsync(sel, stream);
-        return e != hipSuccess ? e : f;
+        return sel.release(e);
     }
     if (defer) {
-        hipError_t e = alloc_edges(&A.edges, n, stream);
+        hipError_t e = edges.alloc(edge_recs(n), stream);
         if (e != hipSuccess) return e;
+        A.edges = edges.p;
     }
     if (v == kDecT) {  // work counter for the waves' string batches
-        unsigned long long* ctr = nullptr;
-        hipError_t e = pool_alloc((void**)&ctr, sizeof(*ctr), stream);
-        if (e == hipSuccess) e = hipMemsetAsync(ctr, 0, sizeof(*ctr), stream);
+        Scratch<unsigned long long> ctr;
+        hipError_t e = ctr.alloc(1, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(ctr.p, 0, sizeof(*ctr.p), stream);
         if (e == hipSuccess) {
-            if (use_run() && in_len == nullptr && out_off == nullptr && A.n_dev == nullptr)
-                launch_run(A, grid, ctr, stream);
-            else
-                hipLaunchKernelGGL(DEC_T, dim3(grid), dim3(kDecTWaves * 64), 0, stream, A, ctr);
-            e = hipGetLastError();
+            if (use_run() && in_len == nullptr && out_off == nullptr && A.n_dev == nullptr) {
+                launch_run(A, grid, ctr.p, stream);
+                e = hipGetLastError();
+            } else {
+                e = launch(DEC_T, kDecT, grid, stream, A, ctr.p);
+            }
         }
-        if (ctr) {
-            const hipError_t f = hipFreeAsync(ctr, stream);
-            if (e == hipSuccess) e = f;
-        }
-        return e;
+        return ctr.release(e);
     }
-    if (use_sw() && v == kDecS && defer && A.n_dev == nullptr) return launch_sw(A, grid, n, out, stream);
-    switch (v) {
-        case kDecS: hipLaunchKernelGGL(DEC_S, dim3(grid), dim3(kDecSWaves * 64), 0, stream, A); break;
-        case kDecL: hipLaunchKernelGGL(DEC_L, dim3(grid), dim3(384), 0, stream, A); break;
-        default: hipLaunchKernelGGL(DEC_D, dim3(grid), dim3(256), 0, stream, A); break;
-    }
-    return defer ? finish_deferred(out, A.edges, n, stream) : hipGetLastError();
+    if (use_sw() && v == kDecS && defer && A.n_dev == nullptr) return edges.release(launch_sw(A, grid, n, out, stream));
+    hipError_t e = launch_as<DecArgs>(v, grid, stream, A);  // kDecS (kDecL and kDecD take DecArgs alone too)
+    if (e == hipSuccess && defer) e = finish_deferred(out, edges.p, n, stream);
+    return edges.release(e);
+}
+
+// launch_literals_dev's decode step (hhuff_literals.hip): header literals as (offset, length) pairs, their count in
+// device memory
+hipError_t launch_decode_short_dev(const uint8_t* in, uint64_t in_size, const uint32_t* in_off, const uint32_t* in_len,
+                                   uint32_t n_max, const uint32_t* n_dev, const uint32_t* is_name_bits, uint8_t* out,
+                                   uint32_t* out_len, uint8_t* status, hipStream_t stream) {
+    DecArgs D{in, in_size, in_off, in_len, n_max, is_name_bits, out, nullptr, out_len, status, nullptr, nullptr, nullptr,
+              nullptr, n_dev};
+    return launch(DEC_S, kDecS, grid_for(kDecS, current_device(), n_max), stream, D);
 }
 
 // Long strings (kSplitMin Huffman bytes or more) are listed by the decode kernels and decoded afterwards, one
@@ -3344,19 +3174,19 @@ hipError_t launch_decode(const uint8_t* in, uint64_t in_size, const uint32_t* in
     const uint64_t bytes = sel_bytes ? sel_bytes : in_size;
     const uint32_t smin = n <= 16u ? kSplitMinFew : kSplitMin;
     const bool split = bytes >= smin && (bytes / n >= 128u || n <= 16u);
-    uint32_t* sp = nullptr;
+    Scratch<uint32_t> sp;  // the two list counts, then the lists
     if (split) {
         A.split_min = smin;
         A.split_cap = (uint32_t)std::min<uint64_t>(n, bytes / smin + 1);
         A.big_min = n <= 16u ? kSplitBigFew : kSplitBig;
         A.big_cap = (uint32_t)std::min<uint64_t>(n, bytes / A.big_min);
-        hipError_t e = pool_alloc((void**)&sp, 4ull * (2 + A.split_cap + A.big_cap), stream);
-        if (e == hipSuccess) e = hipMemsetAsync(sp, 0, 8, stream);
+        hipError_t e = sp.alloc(2ull + A.split_cap + A.big_cap, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(sp.p, 0, 8, stream);
         if (e != hipSuccess) return e;
-        A.split_n = sp;
-        A.big_n = sp + 1;
-        A.split_list = sp + 2;
-        A.big_list = A.big_cap ? sp + 2 + A.split_cap : nullptr;
+        A.split_n = sp.p;
+        A.big_n = sp.p + 1;
+        A.split_list = sp.p + 2;
+        A.big_list = A.big_cap ? sp.p + 2 + A.split_cap : nullptr;
     }
     hipError_t e = launch_decode_kernels(A, in_size, in_len, n, out, out_off, stream, sel_bytes);
     if (split) {
@@ -3373,10 +3203,47 @@ hipError_t launch_decode(const uint8_t* in, uint64_t in_size, const uint32_t* in
                                dim3(kSplitBlockWaves * 64), 0, stream, A);
             e = hipGetLastError();
         }
-        const hipError_t f = hipFreeAsync(sp, stream);
-        if (e == hipSuccess) e = f;
     }
-    return e;
+    return sp.release(e);
+}
+
+// The proportional-lane launch of a contiguous batch, for encode_pl_kernel and flatten_pl_kernel (v: kEncP or kFlatP;
+// A: EncArgs or FlatArgs): tiles of K strings planned for about 5/8 of a stage of bytes (bytes / n: the mean string),
+// from 4096 strings on sampled by encode_plan_kernel, which may pick a smaller K down to kPlCand[5].
+template <class PlArgs>
+static hipError_t launch_pl(void (*kernel)(PlArgs, uint32_t, const uint32_t*, uint64_t), int v, PlArgs A, uint64_t bytes,
+                            hipStream_t stream) {
+    const uint32_t n = A.n;
+    const uint64_t mean = bytes / n;
+    uint32_t K = (uint32_t)(mean ? kPlFill / mean : 64u);
+    K = K < 1 ? 1u : (K > 64 ? 64u : K);
+    K = 64u / ((64u + K - 1u) / K);  // down to 64 / m: m lanes per string, few idle
+    const bool sample = K > kPlCand[5] && n >= 4096;
+    const uint32_t kmin = sample ? kPlCand[5] : K;
+    const uint64_t tiles = ((uint64_t)n + kmin - 1) / kmin;
+    const int g = grid_for(v, current_device(), 0xFFFFFFFFu);
+    const uint64_t waves = (uint64_t)kVariants[v].threads / 64;  // a tile a wave
+    const uint64_t want = (tiles + waves - 1) / waves;
+    const int grid = (int)(want < (uint64_t)g ? (want ? want : 1) : g);
+    const bool defer = defer_edges(n);  // else edges stored in the kernel, one launch
+    const uint64_t recs = defer ? 2 * tiles : 0;  // deferred edges: 2 per tile of the smallest K the plan can pick
+    Scratch<EdgeRec> edges;
+    Scratch<uint32_t> part;  // the plan's partial sums
+    hipError_t e = defer ? edges.alloc(recs, stream) : hipSuccess;
+    if (e != hipSuccess) return e;
+    A.edges = edges.p;
+    if (sample) {
+        e = part.alloc(6 * kPlBlocks, stream);
+        if (e == hipSuccess) {
+            // a tile fits when its 16-B aligned span does: raw span + 30 <= stage
+            hipLaunchKernelGGL(encode_plan_kernel, dim3(kPlBlocks), dim3(64), 0, stream, A.in_off, n, K, kPlStage - 30u, part.p);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = launch(kernel, v, grid, stream, A, K, part.p, recs);
+    e = part.release(e);
+    if (e == hipSuccess && defer) e = finish_deferred(A.out, edges.p, n, stream, nullptr, recs);
+    return edges.release(e);
 }
 
 hipError_t launch_encode(const uint8_t* in, uint64_t in_size, const uint32_t* in_off, const uint32_t* in_len, uint32_t n,
@@ -3385,65 +3252,23 @@ hipError_t launch_encode(const uint8_t* in, uint64_t in_size, const uint32_t* in
     if (n == 0) return hipSuccess;
     EncArgs A{in, in_size, in_off, in_len, n, out, out_off, out_len, status, nullptr, nullptr};
     if (sel_bytes) in_size = sel_bytes;  // variant selection only; A keeps the addressable size
-    if (in_len == nullptr && out_off == nullptr && use_pl_encode(in_size, n)) {
-        // contiguous wire layout: proportional-lane tiles of K strings (about 5/8 of a stage of bytes)
-        const uint64_t mean = in_size / n;
-        uint32_t K = (uint32_t)(mean ? kPlFill / mean : 64u);
-        K = K < 1 ? 1u : (K > 64 ? 64u : K);
-        K = 64u / ((64u + K - 1u) / K);  // down to 64 / m: m lanes per string, few idle
-        const bool sample = K > kPlCand[5] && n >= 4096;
-        const uint32_t kmin = sample ? kPlCand[5] : K;
-        const uint64_t tiles = ((uint64_t)n + kmin - 1) / kmin;
-        const int g = grid_for(kEncP, current_device(), 0xFFFFFFFFu);
-        const uint64_t want = (tiles + 15) / 16;
-        const int grid = (int)(want < (uint64_t)g ? (want ? want : 1) : g);
-        const bool defer = defer_edges(n);  // else edges stored in the kernel, one launch
-        const uint64_t recs = defer ? 2 * tiles : 0;  // deferred edges: 2 per tile of the smallest K the plan can pick
-        hipError_t e = defer ? pool_alloc((void**)&A.edges, recs * sizeof(EdgeRec), stream) : hipSuccess;
-        if (e != hipSuccess) return e;
-        if (!sample) {
-            hipLaunchKernelGGL(ENC_P, dim3(grid), dim3(1024), 0, stream, A, K, (const uint32_t*)nullptr, recs);
-            return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipGetLastError();
-        }
-        uint32_t* part = nullptr;
-        e = pool_alloc((void**)&part, 6 * kPlBlocks * sizeof(uint32_t), stream);
-        if (e == hipSuccess) {
-            // a tile fits when its 16-B aligned span does: raw span + 30 <= stage
-            hipLaunchKernelGGL(encode_plan_kernel, dim3(kPlBlocks), dim3(64), 0, stream, in_off, n, K, kPlStage - 30u, part);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(ENC_P, dim3(grid), dim3(1024), 0, stream, A, K, (const uint32_t*)part, recs);
-            e = hipGetLastError();
-        }
-        if (part) {
-            const hipError_t f = hipFreeAsync(part, stream);
-            if (e == hipSuccess) e = f;
-        }
-        if (e != hipSuccess) {
-            if (defer) (void)hipFreeAsync(A.edges, stream);
-            return e;
-        }
-        return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipSuccess;
-    }
+    // contiguous wire layout, long enough strings: proportional lanes
+    if (in_len == nullptr && out_off == nullptr && use_pl_encode(in_size, n)) return launch_pl(ENC_P, kEncP, A, in_size, stream);
     int v = pick_encode(in_size, n);
     if (v == kEncS && in_len == nullptr && out_off == nullptr) v = pick_sorted(in_size, n);
     const int grid = grid_for(v, current_device(), n);
     const bool defer = v != kEncD && in_len == nullptr && out_off == nullptr && defer_edges(n);
+    Scratch<EdgeRec> edges;
     if (defer) {
-        hipError_t e = alloc_edges(&A.edges, n, stream);
+        hipError_t e = edges.alloc(edge_recs(n), stream);
         if (e != hipSuccess) return e;
+        A.edges = edges.p;
     }
-    switch (v) {
-        case kEncS: hipLaunchKernelGGL(ENC_S, dim3(grid), dim3(kEncSWaves * 64), 0, stream, A); break;
-        case kEncO: hipLaunchKernelGGL(ENC_O, dim3(grid), dim3(kEncOThreads), 0, stream, A); break;
-        case kEncOS: hipLaunchKernelGGL(ENC_OS, dim3(grid), dim3(kEncOThreads), 0, stream, A); break;
-        case kEncL: hipLaunchKernelGGL(ENC_L, dim3(grid), dim3(512), 0, stream, A); break;
-        default: hipLaunchKernelGGL(ENC_D, dim3(grid), dim3(256), 0, stream, A); break;
-    }
+    hipError_t e = launch_as<EncArgs>(v, grid, stream, A);  // every encode variant picked here takes EncArgs alone
     // the sorted encoder writes two records per chunk of kEncOStr strings, the tile kernels two per 64
     const uint64_t recs = v == kEncO || v == kEncOS ? 2 * (((uint64_t)n + kEncOStr - 1) / kEncOStr) : 0;
-    return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipGetLastError();
+    if (e == hipSuccess && defer) e = finish_deferred(out, edges.p, n, stream, nullptr, recs);
+    return edges.release(e);
 }
 
 // Debug query (tests only): the resident workgroups a CU of the sorted encoder that launch_encode picks for a
@@ -3452,7 +3277,9 @@ int debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n) {
     if (n == 0 || use_pl_encode(in_size, n) || pick_encode(in_size, n) != kEncS) return 0;
     const int v = pick_sorted(in_size, n);
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, variant_fn(v), variant_threads(v), 0) != hipSuccess) return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kVariants[v].fn, kVariants[v].threads, 0) !=
+        hipSuccess)
+        return -1;
     return per_cu;
 }
 
@@ -4260,14 +4087,13 @@ hipError_t launch_decode_packed(const uint8_t* in, uint64_t in_size, const uint3
     DecArgs A{in, in_size, in_off, nullptr, n, is_name_bits, out, nullptr, out_len, status, nullptr, nullptr, nullptr, pk_off, nullptr};
     const int v = mean <= 40 ? kDecSP : kDecLP;
     const bool defer = defer_edges(n);
-    hipError_t e = defer ? alloc_edges(&A.edges, n, stream) : hipSuccess;
+    Scratch<EdgeRec> edges;
+    hipError_t e = defer ? edges.alloc(edge_recs(n), stream) : hipSuccess;
     if (e != hipSuccess) return e;
-    const int grid = grid_for(v, current_device(), n);
-    if (v == kDecSP)
-        hipLaunchKernelGGL(DEC_SP, dim3(grid), dim3(kDecSWaves * 64), 0, stream, A);
-    else
-        hipLaunchKernelGGL(DEC_LP, dim3(grid), dim3(384), 0, stream, A);
-    return defer ? finish_deferred(out, A.edges, n, stream) : hipGetLastError();
+    A.edges = edges.p;
+    e = launch_as<DecArgs>(v, grid_for(v, current_device(), n), stream, A);
+    if (e == hipSuccess && defer) e = finish_deferred(out, edges.p, n, stream);
+    return edges.release(e);
 }
 
 hipError_t launch_encode_packed(const uint8_t* in, uint64_t in_size, const uint32_t* in_off, uint32_t n, uint8_t* out,
@@ -4278,32 +4104,29 @@ hipError_t launch_encode_packed(const uint8_t* in, uint64_t in_size, const uint3
     EncArgs A{in, in_size, in_off, nullptr, n, out, nullptr, out_len, status, nullptr, pk_off};
     const int v = mean <= 52 ? kEncSP : kEncLP;
     const bool defer = defer_edges(n);
-    hipError_t e = defer ? alloc_edges(&A.edges, n, stream) : hipSuccess;
+    Scratch<EdgeRec> edges;
+    hipError_t e = defer ? edges.alloc(edge_recs(n), stream) : hipSuccess;
     if (e != hipSuccess) return e;
-    const int grid = grid_for(v, current_device(), n);
-    if (v == kEncSP)
-        hipLaunchKernelGGL(ENC_SP, dim3(grid), dim3(kEncSWaves * 64), 0, stream, A);
-    else
-        hipLaunchKernelGGL(ENC_LP, dim3(grid), dim3(512), 0, stream, A);
-    return defer ? finish_deferred(out, A.edges, n, stream) : hipGetLastError();
+    A.edges = edges.p;
+    e = launch_as<EncArgs>(v, grid_for(v, current_device(), n), stream, A);
+    if (e == hipSuccess && defer) e = finish_deferred(out, edges.p, n, stream);
+    return edges.release(e);
 }
 
 static hipError_t pack_via_scratch(bool dec, const uint8_t* in, uint64_t in_size, const uint32_t* in_off, uint32_t n,
                                    const uint32_t* is_name_bits, uint8_t* out, uint32_t* pk_off, uint32_t* out_len,
                                    uint8_t* status, hipStream_t stream) {
-    uint8_t* tmp = nullptr;
-    const uint64_t bytes = (dec ? (in_size * 8) / 5 : in_size) + 64;
-    hipError_t e = pool_alloc((void**)&tmp, bytes, stream);
+    Scratch<uint8_t> tmp;
+    hipError_t e = tmp.alloc((dec ? (in_size * 8) / 5 : in_size) + 64, stream);
     if (e != hipSuccess) return e;
-    e = dec ? launch_decode(in, in_size, in_off, nullptr, n, is_name_bits, tmp, nullptr, out_len, status, stream)
-            : launch_encode(in, in_size, in_off, nullptr, n, tmp, nullptr, out_len, status, stream);
+    e = dec ? launch_decode(in, in_size, in_off, nullptr, n, is_name_bits, tmp.p, nullptr, out_len, status, stream)
+            : launch_encode(in, in_size, in_off, nullptr, n, tmp.p, nullptr, out_len, status, stream);
     if (e == hipSuccess) {
         const uint32_t blocks = (uint32_t)min(((uint64_t)n + 255) / 256, (uint64_t)65535);
-        hipLaunchKernelGGL(pack_tiles_kernel, dim3(blocks), dim3(256), 0, stream, tmp, in_off, n, dec, out_len, out, pk_off);
+        hipLaunchKernelGGL(pack_tiles_kernel, dim3(blocks), dim3(256), 0, stream, tmp.p, in_off, n, dec, out_len, out, pk_off);
         e = hipGetLastError();
     }
-    const hipError_t f = hipFreeAsync(tmp, stream);
-    return e != hipSuccess ? e : f;
+    return tmp.release(e);
 }
 
 hipError_t launch_flatten(const uint8_t* in, uint64_t in_size, const uint32_t* in_off, const uint32_t* in_len, uint32_t n,
@@ -4311,104 +4134,10 @@ hipError_t launch_flatten(const uint8_t* in, uint64_t in_size, const uint32_t* i
                           const uint32_t* out_off, uint32_t* out_len, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     FlatArgs A{in, in_size, in_off, in_len, n, first_bytes, prefix_bits, raw_bits, out, out_off, out_len};
-    if (in_len == nullptr && out_off == nullptr) {  // contiguous layout, implicit slots: proportional lanes
-        const uint64_t mean = in_size / n;
-        uint32_t K = (uint32_t)(mean ? kPlFill / mean : 64u);  // as launch_encode
-        K = K < 1 ? 1u : (K > 64 ? 64u : K);
-        K = 64u / ((64u + K - 1u) / K);
-        const bool sample = K > kPlCand[5] && n >= 4096;
-        const uint32_t kmin = sample ? kPlCand[5] : K;
-        const uint64_t tiles = ((uint64_t)n + kmin - 1) / kmin;
-        const int g = grid_for(kFlatP, current_device(), 0xFFFFFFFFu);
-        const uint64_t want = (tiles + FLAT_P_THREADS / 64 - 1) / (FLAT_P_THREADS / 64);
-        const int grid = (int)(want < (uint64_t)g ? (want ? want : 1) : g);
-        const bool defer = defer_edges(n);  // else edges stored in the kernel, one launch
-        const uint64_t recs = defer ? 2 * tiles : 0;  // deferred edges (see encode_pl_kernel)
-        hipError_t e = defer ? pool_alloc((void**)&A.edges, recs * sizeof(EdgeRec), stream) : hipSuccess;
-        if (e != hipSuccess) return e;
-        if (!sample) {
-            hipLaunchKernelGGL(FLAT_P, dim3(grid), dim3(FLAT_P_THREADS), 0, stream, A, K, (const uint32_t*)nullptr, recs);
-            return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipGetLastError();
-        }
-        uint32_t* part = nullptr;
-        e = pool_alloc((void**)&part, 6 * kPlBlocks * sizeof(uint32_t), stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(encode_plan_kernel, dim3(kPlBlocks), dim3(64), 0, stream, in_off, n, K, kPlStage - 30u, part);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(FLAT_P, dim3(grid), dim3(FLAT_P_THREADS), 0, stream, A, K, (const uint32_t*)part, recs);
-            e = hipGetLastError();
-        }
-        if (part) {
-            const hipError_t f = hipFreeAsync(part, stream);
-            if (e == hipSuccess) e = f;
-        }
-        if (e != hipSuccess) {
-            if (defer) (void)hipFreeAsync(A.edges, stream);
-            return e;
-        }
-        return defer ? finish_deferred(out, A.edges, n, stream, nullptr, recs) : hipSuccess;
-    }
-    const int grid = grid_for(kFlatD, current_device(), n);
-    hipLaunchKernelGGL(FLAT_D, dim3(grid), dim3(256), 0, stream, A);
-    return hipGetLastError();
+    // contiguous layout, implicit slots: proportional lanes
+    if (in_len == nullptr && out_off == nullptr) return launch_pl(FLAT_P, kFlatP, A, in_size, stream);
+    return launch(FLAT_D, kFlatD, grid_for(kFlatD, current_device(), n), stream, A);
 }
-
-hipError_t launch_literals(const uint8_t* in, uint64_t in_size, const uint32_t* lit_off, const uint32_t* lit_end, uint32_t n,
-                           uint32_t prefix_bits, uint32_t flags, const uint32_t* is_name_bits, uint8_t* out,
-                           uint32_t* out_len, uint32_t* pay_off, uint32_t* consumed, uint8_t* status, uint32_t* huff_len,
-                           hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    LitArgs A{in, in_size, lit_off, lit_end, n, prefix_bits, flags, is_name_bits, out, out_len, pay_off, consumed, status,
-              huff_len, reinterpret_cast<uint8_t*>(huff_len + n), nullptr, nullptr, nullptr, nullptr};
-    const uint32_t blocks = min((n + 255u) / 256u, 4096u);
-    hipLaunchKernelGGL(literal_parse_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = launch_decode(in, in_size, pay_off, huff_len, n, is_name_bits, out, nullptr, out_len, status, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(literal_fix_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    return hipGetLastError();
-}
-
-// Literals whose count is only known on the device (the header-block pipeline, hhuff_blocks.hip): n_max
-// bounds the arrays, *n_dev is the count.  Huffman payloads go through the stream kernel, which takes its
-// strings from a work counter and so needs no host-side count.  ws: 5 n_max bytes + 16.
-hipError_t launch_literals_dev(const uint8_t* in, uint64_t in_size, const uint32_t* lit_off, uint32_t n_max,
-                               const uint32_t* n_dev, uint32_t prefix_bits, uint32_t flags, const uint32_t* is_name_bits,
-                               uint8_t* out, uint32_t* out_len, uint32_t* pay_off, uint32_t* consumed, uint8_t* status,
-                               uint8_t* ws, hipStream_t stream, const uint8_t* prefix_of) {
-    if (n_max == 0) return hipSuccess;
-    // ws: huff_len u32[n_max], code u8[n_max], then (8-aligned) the stream counter u64, the long-literal
-    // count u32 (+ pad) and list u32[in_size / kLongRaw + 1]
-    uint32_t* huff_len = reinterpret_cast<uint32_t*>(ws);
-    uint8_t* tail = ws + 5ull * n_max + ((8 - (5ull * n_max) % 8) % 8);
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(tail);
-    uint32_t* long_count = reinterpret_cast<uint32_t*>(tail + 8);
-    uint32_t* long_list = reinterpret_cast<uint32_t*>(tail + 16);
-    LitArgs A{in, in_size, lit_off, nullptr, n_max, prefix_bits, flags, is_name_bits, out, out_len, pay_off, consumed,
-              status, huff_len, reinterpret_cast<uint8_t*>(huff_len + n_max), n_dev, long_list, long_count, prefix_of};
-    const int dev = current_device();
-    const uint32_t blocks = min((n_max + 255u) / 256u, 8192u);
-    hipError_t e = hipMemsetAsync(tail, 0, 16, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(literal_parse_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    hipLaunchKernelGGL(literal_long_kernel, dim3(1024), dim3(256), 0, stream, A);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    DecArgs D{in, in_size, pay_off, huff_len, n_max, is_name_bits, out, nullptr, out_len, status, nullptr, nullptr, nullptr,
-              nullptr, n_dev};
-    // header literals are short: the staged kernel (tiles of 64 consecutive literals, their span staged in
-    // LDS; a tile whose span exceeds the stage decodes lane by lane from global memory).  Measured against
-    // the stream kernel on the f4 benches: blocks 1.685 -> 1.485 ms, qpack 1.25 -> 1.08 ms.
-    (void)ctr;
-    hipLaunchKernelGGL(DEC_S, dim3(grid_for(kDecS, dev, n_max)), dim3(kDecSWaves * 64), 0, stream, D);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(literal_fix_kernel, dim3(blocks), dim3(256), 0, stream, A);
-    return hipGetLastError();
-}
-
-uint64_t literals_dev_ws(uint32_t n_max, uint64_t in_size) { return 5ull * n_max + 8 + 16 + 4 * (in_size / kLongRaw + 1); }
 
 hipError_t work_alloc(void** p, uint64_t bytes, hipStream_t stream) { return pool_alloc(p, bytes, stream); }
 
@@ -4424,10 +4153,6 @@ hipError_t pool_trim() {
 int grid_size(int device, int which) { return grid_for(which == 0 ? kDecS : kEncS, device, 0xFFFFFFFFu); }
 
 }  // namespace hhuff
-
-extern "C" __attribute__((visibility("default"))) int hhuff_debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n) {
-    return hhuff::debug_encode_blocks_per_cu(in_size, n);
-}
 
 #ifdef HHUFF_PROFILE
 namespace hhuff {

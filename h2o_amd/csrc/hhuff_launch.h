@@ -1,4 +1,6 @@
-// Internal launch interface between the C-ABI shim (hhuff_capi.hip) and the kernels (hhuff_kernels.hip).
+// Internal launch interface between the C-ABI shim (hhuff_capi.hip) and the kernel units: the batch codec and the
+// per-string kernels (hhuff_kernels.hip), the header literals (hhuff_literals.hip) and the header-block families
+// named below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,6 +82,11 @@ hipError_t launch_literals_dev(const uint8_t* in, uint64_t in_size, const uint32
                                uint8_t* out, uint32_t* out_len, uint32_t* pay_off, uint32_t* consumed, uint8_t* status,
                                uint8_t* ws, hipStream_t stream, const uint8_t* prefix_of = nullptr);
 uint64_t literals_dev_ws(uint32_t n_max, uint64_t in_size);
+// launch_literals_dev's decode step (hhuff_kernels.hip): the staged short-string kernel over (in_off, in_len)
+// pairs whose count lives in device memory (*n_dev <= n_max), implicit output slots
+hipError_t launch_decode_short_dev(const uint8_t* in, uint64_t in_size, const uint32_t* in_off, const uint32_t* in_len,
+                                   uint32_t n_max, const uint32_t* n_dev, const uint32_t* is_name_bits, uint8_t* out,
+                                   uint32_t* out_len, uint8_t* status, hipStream_t stream);
 // The literal list of marked input bytes (hhuff_blocks.hip): bit p of lit_bits marks a literal at byte p.
 // Writes word_pre (marks before each bitmap word), list (positions in order), lnames (bit r set when the
 // literal's name_bits bit is), prefix_of[r] (when given) = pfx_alt if its pfx_bits bit is set, else pfx_name for
@@ -239,6 +246,8 @@ hipError_t launch_conn_import(const hhuff_conn_family_t& fam, uint8_t* scratch, 
                               uint32_t n, const uint8_t* image, const uint64_t* img_off, const uint32_t* img_len,
                               int32_t* status, hipStream_t stream);
 int grid_size(int device, int which);
+// hhuff_debug_encode_blocks_per_cu (tests only): resident workgroups a CU of the sorted encoder launch_encode picks
+int debug_encode_blocks_per_cu(uint64_t in_size, uint32_t n);
 // the staged / stream prices (ps per string, per byte) a mixed-length decode on `device` uses: the fitted
 // defaults, pinned values, or (calibrate != 0: measured now, synchronously) this device's own
 // (hhuff_kernels.hip calibrate_prices); 0, or -1 when the device cannot be selected

@@ -42,16 +42,14 @@ static hipError_t launch_seg(DecArgs A, uint64_t in_size, uint32_t n, uint8_t* o
     const uint64_t tmax64 = in_size / kSegTB + 2u;  // tiles + 1 (the plan needs tf[T], T <= in_size / TB + 1)
     if (tmax64 >= (1ull << 31)) return hipErrorInvalidValue;
     const uint32_t tmax = (uint32_t)tmax64;
-    uint32_t* tf = nullptr;
-    hipError_t e = pool_alloc((void**)&tf, 4ull * tmax, stream);
+    Scratch<uint32_t> tf;
+    Scratch<EdgeRec> edges;
+    hipError_t e = tf.alloc(tmax, stream);
+    if (e == hipSuccess) e = edges.alloc(2ull * tmax, stream);
     if (e != hipSuccess) return e;
-    e = pool_alloc((void**)&A.edges, 2ull * tmax * sizeof(EdgeRec), stream);
-    if (e != hipSuccess) {
-        (void)hipFreeAsync(tf, stream);
-        return e;
-    }
+    A.edges = edges.p;
     const uint32_t pblocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + 256u) / 256u, 4096u);
-    hipLaunchKernelGGL(seg_plan_kernel, dim3(pblocks), dim3(256), 0, stream, A.in_off, n, kSegTB, tmax, tf, A.edges);
+    hipLaunchKernelGGL(seg_plan_kernel, dim3(pblocks), dim3(256), 0, stream, A.in_off, n, kSegTB, tmax, tf.p, A.edges);
     e = hipGetLastError();
     if (e == hipSuccess) {
         static int cus[64] = {};
@@ -60,13 +58,10 @@ static hipError_t launch_seg(DecArgs A, uint64_t in_size, uint32_t n, uint8_t* o
         if (c == 0 && (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1)) c = 256;
         const uint64_t want = (tmax64 + kSegWaves - 1) / kSegWaves;
         const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c);
-        hipLaunchKernelGGL(DEC_G, dim3(grid), dim3(kSegWaves * 64), 0, stream, A, (const uint32_t*)tf, tmax);
+        hipLaunchKernelGGL(DEC_G, dim3(grid), dim3(kSegWaves * 64), 0, stream, A, (const uint32_t*)tf.p, tmax);
         e = finish_deferred(out, A.edges, n, stream, nullptr, 2ull * tmax);
-    } else {
-        (void)hipFreeAsync(A.edges, stream);
     }
-    const hipError_t f = hipFreeAsync(tf, stream);
-    return e != hipSuccess ? e : f;
+    return tf.release(edges.release(e));
 }
 
 // Length-sorted decode chunks (decode_sorted_kernel) for the short-string contiguous layout, HHUFF_DEC_SORTED=1 (A/B;
@@ -85,15 +80,17 @@ static bool sorted_decode_on() {
 }
 static hipError_t launch_sorted_decode(DecArgs A, uint32_t n, uint8_t* out, hipStream_t stream) {
     const uint64_t nch = ((uint64_t)n + kDsStr - 1) / kDsStr;
-    hipError_t e = pool_alloc((void**)&A.edges, 2ull * nch * sizeof(EdgeRec), stream);
+    Scratch<EdgeRec> edges;
+    hipError_t e = edges.alloc(2ull * nch, stream);
     if (e != hipSuccess) return e;
+    A.edges = edges.p;
     static int cus[64] = {};
     const int dev = current_device();
     int& cu = cus[dev >= 0 && dev < 64 ? dev : 0];
     if (cu == 0 && (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1)) cu = 256;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((nch + 3) / 4, (uint64_t)cu);
     hipLaunchKernelGGL(decode_sorted_kernel<HHUFF_DS_CH>, dim3(grid), dim3(1024), 0, stream, A);
-    return finish_deferred(out, A.edges, n, stream, nullptr, 2ull * nch);
+    return edges.release(finish_deferred(out, A.edges, n, stream, nullptr, 2ull * nch));
 }
 
 // Run decode (decode_run_kernel, -DHHUFF_DEC_RUN=1): the contiguous layout's stream decode in runs of HHUFF_RUN_RL
