@@ -410,6 +410,25 @@ struct DecArgs {
     uint32_t claim = 64;
 };
 
+// decode_staged_kernel<.., LEAN = true>'s arguments: a contiguous batch (strings back to back, slot outputs) with
+// nothing else attached.  What DecArgs can carry besides is a constant here, so the kernel's tests of it fold away.
+struct DecLeanArgs {
+    const uint8_t* in;
+    uint64_t in_size;
+    const uint32_t* in_off;
+    uint32_t n;
+    const uint32_t* is_name_bits;
+    uint8_t* out;
+    uint32_t* out_len;
+    uint8_t* status;
+    static constexpr const uint32_t* in_len = nullptr;
+    static constexpr const uint32_t* out_off = nullptr;
+    static constexpr EdgeRec* edges = nullptr;
+    static constexpr uint32_t* gate = nullptr;
+    static constexpr uint32_t* pk_off = nullptr;
+    static constexpr const uint32_t* n_dev = nullptr;
+};
+
 // a string long enough for split_decode_kernel goes to its list (when the launch has one) instead of being
 // decoded by this lane; a full list leaves it here
 __device__ __forceinline__ bool split_push(const DecArgs& A, uint32_t i, uint32_t len) {
@@ -426,9 +445,11 @@ __device__ __forceinline__ bool split_push(const DecArgs& A, uint32_t i, uint32_
     A.split_list[k] = i;
     return true;
 }
+__device__ __forceinline__ bool split_push(const DecLeanArgs&, uint32_t, uint32_t) { return false; }  // (no lists)
 
 // direct variant for one lane: global input, register sink straight to `dst`
-__device__ __forceinline__ void decode_direct(const DecArgs& A, uint32_t s, uint32_t len, bool is_name, uint8_t* dst,
+template <class Args>
+__device__ __forceinline__ void decode_direct(const Args& A, uint32_t s, uint32_t len, bool is_name, uint8_t* dst,
                                               const DecTables& T, uint32_t& ol, uint8_t& st) {
     if (len > kMaxStrLen) {
         ol = kFailLen;
@@ -468,8 +489,12 @@ __device__ __forceinline__ void decode_direct(const DecArgs& A, uint32_t s, uint
 // never overwrite a source another lane still needs.  The next tile's input then goes into the other
 // half, beside the packed run, before the run's 16-B stores are issued (the pipeline order of the slot
 // layout, whose commit also precedes the stores).
-template <int WAVES, int IN_STAGE, int OUT_STAGE, bool PACKED>
-__global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
+//
+// LEAN (slot output only): the instantiation for contiguous batches that use none of pairs, explicit destinations,
+// the gate, split lists, a device-side count or deferred edges (DecLeanArgs); `region` is then a constant.
+template <int WAVES, int IN_STAGE, int OUT_STAGE, bool PACKED, bool LEAN = false>
+__global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(std::conditional_t<LEAN, DecLeanArgs, DecArgs> A) {
+    static_assert(!(LEAN && PACKED), "the lean arguments have no packed places");
     constexpr uint32_t Z = IN_STAGE + OUT_STAGE + 256u;  // + 16 slack: the run's last 16-B chunk may read past Z
     static_assert(OUT_STAGE <= 2 * IN_STAGE + 480 && Z % 16 == 0, "packed compaction needs OUT <= 2 IN");
     if (A.n_dev) A.n = *A.n_dev;  // the count lives in device memory (literal pre-passes)
@@ -480,7 +505,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_staged_kernel(DecArgs A) {
         uint32_t ones[(HHUFF_ONES_NENT + 3) & ~3];
         uint8_t buf[WAVES][Z + 16];
     };
-    if (A.gate) {  // mixed-length batch: price both kernels from the sampled tiles (decode_select_kernel)
+    if constexpr (!LEAN) if (A.gate) {  // mixed-length batch: price both kernels from the sampled tiles (decode_select_kernel)
         __shared__ uint32_t verdict;
         if (threadIdx.x < 64) {
             const uint32_t g = select_verdict(A.sel, A.price);
@@ -1756,8 +1781,9 @@ __device__ __forceinline__ SortChunk sort_chunk_issue(const EncArgs& A, uint64_t
 // at most 13,568 B, a 257-entry code table (the head and tail words are masked and look up entry 256 outside the
 // string), one packed record a string, 16-bit encoded lengths, byte ranks: 31,072 B at CH = 13,312.  Registers, 96
 // VGPRs for five waves a SIMD (a wave of each workgroup on every SIMD): the chunk's span in scalar registers, a
-// chunk's offsets kept in its LDS records only, the next span handed on through LDS, two copy-out chunks in flight,
-// and the thread index a fresh value in each phase of the loop (fresh() below).  At four workgroups a CU the trimmed
+// chunk's offsets kept in its LDS records only, the next span's bounds handed on through LDS, its bytes loaded behind
+// barrier 3 and committed in front of the next barrier 2 (not held across the encode), two copy-out chunks in
+// flight, and the thread index a fresh value in front of the copy-out (fresh() below).  At four workgroups a CU the trimmed
 // code is 2-4 % slower than the wide code (the phase-local index arithmetic alone costs 2 %), so the large stage
 // keeps the wide policy.  Every `if constexpr (P::kTrim)` below is one of those trims.
 struct SortedWide {
@@ -1772,7 +1798,7 @@ struct SortedTrim {
     static constexpr uint32_t kEnc = 257;  // 256: bytes outside a string
     using Str = uint32_t;                  // offset in the span | length << 14 of chunk string t
     using Rank = uint8_t;
-    static constexpr int copy_batch(int) { return 2; }  // (96 VGPRs hold two)
+    static constexpr int copy_batch(int) { return 2; }  // (four measured the same)
 };
 // (A by value, as a kernel holds it: through a reference the copy-out's predicates compiled to seven more instructions)
 template <class P, int NS, int CH, int SPT>
@@ -1791,9 +1817,10 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
     __shared__ uint32_t s_bin[kSortBins];  // strings per bin, then the bins' first places
     __shared__ uint32_t s_lohi[2][2];      // (trimmed) the next chunk's input span {lo, hi}, by the parity of the trip
     uint32_t t = threadIdx.x;
-    // fresh(): the thread index as a new value.  What a phase of the loop derives from it (addresses of the
-    // thread's records and stage chunks, its predicates) is then computed in that phase, not once before the loop
-    // and kept in registers across the encode: fourteen VGPRs (111 -> 97 as the allocator leaves them).
+    // fresh(): the thread index as a new value.  What the copy-out derives from it (addresses of the thread's stage
+    // chunks, its predicates) is then computed there, not once before the loop and kept in registers across the
+    // encode.  One place is enough since the span left the encode's registers: without it the kernel needs scratch
+    // at 96 VGPRs; in every phase, as before, it cost 2 %.
     auto fresh = [&] {
         if constexpr (P::kTrim) __asm__ volatile("" : "+v"(t));
     };
@@ -1873,7 +1900,7 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
     auto prepare = [&](const SortChunk (&q)[SPT], uint64_t qb, uint32_t z0) {
         const uint32_t sp = span_of(q[0]);
         if (sp > (uint32_t)CH) return;  // workgroup-uniform: the per-thread path needs none of it
-        commit_span(pv, q[0]);
+        if constexpr (!P::kTrim) commit_span(pv, q[0]);  // (trimmed: in front of the chunk's barrier 2)
         for (uint32_t k = z0 + t * 16u; k < sp + 16u; k += 16u * NT)
             *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(s_out) + k) = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
@@ -1892,7 +1919,7 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
     SortChunk cur[SPT];
     issue_chunk(cur, c * kSortStr);
     if constexpr (P::kTrim) land(cur);  // (its span to scalar registers)
-    issue_span(pv, cur[0]);
+    if constexpr (!P::kTrim) issue_span(pv, cur[0]);
     prepare(cur, c * kSortStr, 0u);
     // the next chunk's offsets are loaded a chunk ahead (after barrier 2) and waited for after barrier 3,
     // before the chunk's stores: no load is then waited for behind a data-dependent number of stores
@@ -1905,6 +1932,12 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
             s_lohi[0][1] = nxt[0].hi;
         }
     }
+    // Trimmed: the span is not held across the encode.  It is loaded behind barrier 3 of the chunk before, in front
+    // of that chunk's stores, and committed in front of its own barrier 2 (the input stage is read between barriers
+    // 2 and 3 only); the workgroup's first chunk and a chunk behind one past the stage load theirs there.  pv has one
+    // place in the loop where it is loaded ahead, so the loaded registers cross the back edge where they are, with
+    // no copy that would wait for them.
+    bool have_pv = false;
     PROF_DECL  // profile builds: barrier 1 / ranks + barrier 2 / encode / barrier 3 + lengths / copy out / prepare
     for (;;) {
         const uint64_t cb = c * kSortStr;
@@ -1915,7 +1948,6 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
         const uint64_t cn2 = cn + gridDim.x;  // the chunk after next
         __syncthreads();  // the chunk's stage, strings and ranks are in (trimmed: and the next chunk's span)
         PROF_MARK(0);
-        fresh();
         uint32_t nlo = 0, nhi = 0;
         if constexpr (P::kTrim) nlo = s_lohi[par][0], nhi = s_lohi[par][1];  // read here, used after the next barrier
         auto next_span = [&] {
@@ -1953,7 +1985,8 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
             if (A.edges && t < 2) rec[t].m = make_uint4(0u, 0u, 0u, 0u);  // direct stores: no edges to defer
             if (!more) break;
             next_span();
-            issue_span(pv, nxt[0]);
+            if constexpr (P::kTrim) have_pv = false;
+            else issue_span(pv, nxt[0]);
             prepare(nxt, cn * kSortStr, 0u);
             SortChunk nn[SPT];
             issue_ahead(nn, (cn2 < nch ? cn2 : cn) * kSortStr);
@@ -1971,12 +2004,18 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
                 s_perm[eb + ((bin[u] & 1u) ? xb : 0u) + rank[u]] = (typename P::Rank)(t + (uint32_t)u * NT);
             }
         }
+        if constexpr (P::kTrim) {
+            if (!have_pv) issue_span(pv, cur[0]);  // the first chunk, and one behind a chunk past the stage
+            commit_span(pv, cur[0]);
+            have_pv = true;
+        }
         __syncthreads();
         PROF_MARK(1);
-        fresh();
         next_span();
         for (uint32_t k = t; k < kSortBins; k += NT) s_bin[k] = 0u;  // read by every wave above: cleared for the next chunk
-        if (more) issue_span(pv, nxt[0]);     // the next chunk's span: in flight during the encode
+        if constexpr (!P::kTrim) {
+            if (more) issue_span(pv, nxt[0]);  // the next chunk's span: in flight during the encode
+        }
         SortChunk nn[SPT];
         issue_ahead(nn, (cn2 < nch ? cn2 : (more ? cn : c)) * kSortStr);
         // sorted position t = 64 wave + lane: wave w encodes the w-th length group (SPT = 2: then also the
@@ -2000,7 +2039,6 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
         }
         PROF_MARK(2);
         __syncthreads();
-        fresh();
         uint32_t olen[SPT], len[SPT];
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
@@ -2019,6 +2057,9 @@ __device__ __forceinline__ void encode_sorted_body(const EncArgs A) {
         // the chunk after next's offsets are waited for here too, on every path: `nxt = nn` below then copies
         // registers with no load pending, not behind this chunk's stores
         land_ahead(nn);
+        if constexpr (P::kTrim) {  // the next chunk's span: in flight from here to its commit
+            if (more) issue_span(pv, nxt[0]);
+        }
         PROF_MARK(5);
 #pragma unroll
         for (int u = 0; u < SPT; ++u) {
@@ -2694,6 +2735,7 @@ constexpr int kEncSWaves = 16, kEncLWaves = 8, kEncDWaves = 4, kEncPWaves = 16;
 constexpr int kFlatDWaves = 4, kFlatPWaves = 16;
 #define DEC_S decode_staged_kernel<kDecSWaves, 3072, 4608, false>
 #define DEC_L decode_staged_kernel<kDecLWaves, 8192, 12928, false>
+#define DEC_SR decode_staged_kernel<kDecSWaves, 3072, 4608, false, true>
 #define DEC_SP decode_staged_kernel<kDecSWaves, 3072, 4608, true>
 #define DEC_LP decode_staged_kernel<kDecLWaves, 8192, 12928, true>
 #define DEC_D decode_direct_kernel<kDecDWaves>
@@ -2716,7 +2758,7 @@ constexpr int kFlatDWaves = 4, kFlatPWaves = 16;
 #endif
 
 enum Variant { kDecS, kDecL, kDecD, kEncS, kEncL, kEncD, kFlatD, kEncP, kFlatP, kDecT, kDecSP, kDecLP, kEncSP, kEncLP,
-               kEncO, kEncOS, kNumVariants };
+               kEncO, kEncOS, kDecSR, kNumVariants };
 
 // One row per Variant, in the enum's order: the kernel (the DEC_* / ENC_* / FLAT_* macros, so an A/B build's
 // replacements land here) and its threads per block, from the constant the kernel's __launch_bounds__ is built from.
@@ -2746,6 +2788,7 @@ static const VariantRow kVariants[] = {
     variant_row(kDecSP, DEC_SP, kDecSWaves * 64),  variant_row(kDecLP, DEC_LP, kDecLWaves * 64),
     variant_row(kEncSP, ENC_SP, kEncSWaves * 64),  variant_row(kEncLP, ENC_LP, kEncLWaves * 64),
     variant_row(kEncO, ENC_O, kEncOThreads),       variant_row(kEncOS, ENC_OS, kEncOThreads),
+    variant_row(kDecSR, DEC_SR, kDecSWaves * 64),
 };
 static_assert(sizeof(kVariants) / sizeof(kVariants[0]) == kNumVariants, "one row per Variant");
 // v's row; NULL if the rows' order has drifted from the enum's (every launch of v then fails)
@@ -3134,6 +3177,12 @@ static hipError_t launch_decode_kernels(DecArgs A, uint64_t in_size, const uint3
         return ctr.release(e);
     }
     if (use_sw() && v == kDecS && defer && A.n_dev == nullptr) return edges.release(launch_sw(A, grid, n, out, stream));
+    // a contiguous batch with nothing attached (no pairs or destinations, edges stored in the kernel, no lists,
+    // the count on the host): kDecS's lean instantiation
+    if (v == kDecS && in_len == nullptr && out_off == nullptr && !defer && A.split_list == nullptr && A.n_dev == nullptr) {
+        const DecLeanArgs R{A.in, A.in_size, A.in_off, A.n, A.is_name_bits, A.out, A.out_len, A.status};
+        return launch_as<DecLeanArgs>(kDecSR, grid_for(kDecSR, current_device(), n), stream, R);
+    }
     hipError_t e = launch_as<DecArgs>(v, grid, stream, A);  // kDecS (kDecL and kDecD take DecArgs alone too)
     if (e == hipSuccess && defer) e = finish_deferred(out, edges.p, n, stream);
     return edges.release(e);
