@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI shim (hhuff_capi.hip) and the kernel units: the batch codec and the
+// Internal launch interface between the C-ABI shim (hhuff_capi*.hip, over hhuff_host.h) and the kernel units: the batch codec and the
 // per-string kernels (hhuff_kernels.hip), the header literals (hhuff_literals.hip) and the header-block families
 // named below.
 #pragma once
@@ -22,7 +22,7 @@ hipError_t launch_one(uint8_t* h, uint32_t len, uint32_t in_cap, bool is_name, b
 // One device-resident string past kOneMax, encoded by one block (out: 4-byte aligned, at least 4 ceil(8 len / 32)
 // bytes; out_len: the code bytes or kFailLen)
 hipError_t launch_encode_long(const uint8_t* in, uint32_t len, uint8_t* out, uint32_t* out_len, hipStream_t stream);
-// Resident per-string service (hhuff_capi.hip per_string): one wave polls kSvcSlots mailboxes in pinned,
+// Resident per-string service (hhuff_capi_string.hip per_string): one wave polls kSvcSlots mailboxes in pinned,
 // device-visible, coherent host memory and codes each posted string in place; it exits when `stop` is set,
 // after idle_ticks of the 100 MHz real-time counter without a request, or after max_ticks in all.
 constexpr uint32_t kSvcSlots = 64;

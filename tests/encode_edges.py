@@ -371,7 +371,7 @@ def mailbox_of(t):
 
 
 # ------------------------------------------------------------------------------------------------
-# a plain model of the mailbox exchange (svc_call in hhuff_capi.hip, service_kernel in hhuff_kernels.hip)
+# a plain model of the mailbox exchange (svc_call in hhuff_capi_string.hip, service_kernel in hhuff_kernels.hip)
 # ------------------------------------------------------------------------------------------------
 DEFECTS = ("trust_hot",      # the chunks read ahead for the hot mailbox are used without testing their tags
            "keep_ck_slot",   # ck_slot is not cleared after the first mailbox served in a poll

@@ -1,5 +1,5 @@
-"""A plain-Python model of the host-array batch paths of h2o_amd/csrc/hhuff_capi.hip (`pipelined`, `host_packed`;
-`host_batch` and `multi_host` route into them) -- no GPU.
+"""A plain-Python model of the host-array batch paths of h2o_amd/csrc/hhuff_capi_host.hip (`pipelined`, `host_packed`;
+`host_batch` and hhuff_capi_multi.hip's `multi_host` route into them), whose arithmetic is hhuff_hostplan.h -- no GPU.
 
   cuts() / plan()          the chunk cuts of `pipelined` and, per chunk, its addresses, staging slot, the kernel
                            family its own mean picks, its split-list thresholds and whether its edges are deferred
@@ -7,8 +7,9 @@
   emulate_packed_staged()  unstaging as the C++, so that an address defect can be switched on (DEFECTS): the
                            corpora of host_paths_corpora.py must tell each of them from the right code
 
-The constants are the sources' (tests/test_host_paths_host.py reads them back out of the .hip files by regex): a
-retuned constant fails there, and the corpora do not silently move off their edges."""
+The constants are the sources' (tests/test_host_paths_host.py reads them back out of the sources by regex): a
+retuned constant fails there, and the corpora do not silently move off their edges.  tests/test_hostplan_host.py runs
+hhuff_hostplan.h itself against cuts(), plan() and packed_runs()."""
 import collections
 import ctypes
 

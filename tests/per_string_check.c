@@ -9,7 +9,7 @@
  * kind 1, which runs hhuff_decode_batch on a stream of its own for as long as the calling threads work.
  *
  * The calling threads make their first call one after another in thread order, so thread number k of them owns
- * mailbox k mod 64 of the resident service (svc_call, hhuff_capi.hip).  With the plan's lock-step flag they then go
+ * mailbox k mod 64 of the resident service (svc_call, hhuff_capi_string.hip).  With the plan's lock-step flag they then go
  * round by round, a barrier before every call, so that the requests of a round are posted together.  Every thread
  * checks every call itself: the return value, every output byte, the soft_errors word, the sentinel bytes of dst behind
  * the result and behind dst, and through hhuff_service_stamps whether the service's wave served the call -- it must

@@ -81,7 +81,7 @@ def _one(text, pattern):
 
 
 def test_service_constants_match_the_sources():
-    launch, kern, capi = _src("hhuff_launch.h"), _src("hhuff_kernels.hip"), _src("hhuff_capi.hip")
+    launch, kern, capi = _src("hhuff_launch.h"), _src("hhuff_kernels.hip"), _src("hhuff_capi_string.hip")
     assert _one(launch, r"constexpr uint32_t kSvcSlots = (\d+);") == E.SVC_SLOTS == 64
     assert _one(launch, r"constexpr uint32_t kSvcMax = (\d+);") == E.SVC_MAX == 768
     assert _one(launch, r"constexpr uint32_t kOneMax = (\d+);") == E.ONE_MAX

@@ -47,20 +47,35 @@ def _int(text, pattern):
 
 
 def test_constants_match_the_sources():
-    """host_paths_model.py against hhuff_capi.hip and hhuff_kernels.hip.  A retuned constant fails here: move it in
-    the model with the source, and the corpora's edges follow."""
-    capi, k = _src("hhuff_capi.hip"), _src("hhuff_kernels.hip")
-    assert _int(capi, r"constexpr int kDepth = (\d+);") == M.K_DEPTH
-    assert _int(capi, r"constexpr uint64_t kDefaultChunk = (\d+)ull << 20;") << 20 == M.DEFAULT_CHUNK
-    assert "if (!in_len && !out_off && in_size >= 2 * kDefaultChunk) // large contiguous batch" in capi
+    """host_paths_model.py against hhuff_hostplan.h (the arithmetic), hhuff_capi_host.hip (the routes and the chunk
+    loop), hhuff_host.h (the launch the chunks go through) and hhuff_kernels.hip.  A retuned constant fails here: move
+    it in the model with the source, and the corpora's edges follow.  (What the arithmetic next to the constants
+    computes is test_hostplan_host.py's: the header run against the model.)"""
+    plan, host, shared, k = _src("hhuff_hostplan.h"), _src("hhuff_capi_host.hip"), _src("hhuff_host.h"), _src("hhuff_kernels.hip")
+    assert _int(plan, r"constexpr int kDepth = (\d+);") == M.K_DEPTH
+    assert _int(plan, r"constexpr uint64_t kDefaultChunk = (\d+)ull << 20;") << 20 == M.DEFAULT_CHUNK
+    assert "if (!in_len && !out_off && in_size >= 2 * kDefaultChunk) // large contiguous batch" in host
     assert M.ROUTE_MIN == 2 * M.DEFAULT_CHUNK
-    assert "if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;" in capi
-    assert "b = b > a + 32 ? ((b - a) / 32) * 32 + a : a + 32;" in capi and M.CUT_ALIGN == 32
-    assert "const uint64_t base = (s0 / 80) * 80;" in capi and M.BASE_ALIGN == 80
-    assert "is_name_bits + i0 / 32" in capi and "Slot& x = P.slot[k % kDepth];" in capi
-    assert "hhuff::launch_decode(d_in, e0, d_off, nullptr, (uint32_t)m," in capi and "d_len, d_st, x.s, nbytes)" in capi
-    assert _int(capi, r"const size_t chunk = \(size_t\)(\d+) << 20;") << 20 == M.PACKED_CHUNK
-    assert "const uint32_t ntiles = (n + 63) / 64;" in capi and "in_off[(size_t)t * 64]" in capi and M.TILE == 64
+    assert plan.count("if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;") == 1
+    assert plan.count("b = b > a + 32 ? ((b - a) / 32) * 32 + a : a + 32;") == 1 and M.CUT_ALIGN == 32
+    assert plan.count("const uint64_t base = (s0 / 80) * 80;") == 1 and M.BASE_ALIGN == 80
+    assert "const std::vector<uint64_t> cut = chunk_cuts(in_off, n, chunk_bytes);" in host
+    assert "const ChunkLayout L = chunk_layout(decode, in_off[i0], e0, m, is_name_bits != nullptr);" in host
+    assert "is_name_bits + i0 / 32" in host and "Slot& x = P.slot[k % kDepth];" in host
+    # the chunk's launch: its e0 as in_size, its nbytes as sel_bytes -- launch_slots hands both on in those places
+    assert "const uint64_t e0 = in_off[i1];" in host and "nbytes = L.nbytes," in host
+    assert host.count("launch_slots(decode, d_in, e0, d_off, nullptr, (uint32_t)m, d_nm, d_out, nullptr, d_len,") == 1
+    assert host.count("status ? d_st : nullptr, x.s, nbytes);") == 1
+    assert "inline hipError_t launch_slots(bool decode, const uint8_t* in, uint64_t in_size, const uint32_t* in_off, " \
+           "const uint32_t* in_len, uint32_t n, const uint32_t* names, uint8_t* out, const uint32_t* out_off, " \
+           "uint32_t* out_len, uint8_t* status, hipStream_t stream, uint64_t sel_bytes = 0) {" in shared
+    assert "hhuff::launch_decode(in, in_size, in_off, in_len, n, names, out, out_off, out_len, status, stream, sel_bytes)" in shared
+    assert "hhuff::launch_encode(in, in_size, in_off, in_len, n, out, out_off, out_len, status, stream, sel_bytes);" in shared
+    assert _int(plan, r"constexpr size_t kPackedChunk = \(size_t\)(\d+) << 20;") << 20 == M.PACKED_CHUNK
+    assert "const size_t chunk = kPackedChunk;" in host
+    assert plan.count("inline uint32_t packed_ntiles(uint32_t n) { return (n + 63) / 64; }") == 1
+    assert plan.count("in_off[(size_t)t * 64]") == 1 and M.TILE == 64
+    assert "const uint32_t ntiles = packed_ntiles(n);" in host
     assert _int(k, r"constexpr uint32_t kSplitMin = (\d+);") == M.SPLIT_MIN
     assert _int(k, r"constexpr uint32_t kSplitMinFew = (\d+);") == M.SPLIT_MIN_FEW
     m = re.search(r"constexpr uint32_t kSplitBig = (\d+), kSplitBigFew = (\d+);", k)

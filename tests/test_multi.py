@@ -207,3 +207,56 @@ def test_multi_sub_batch_and_small_batches(torch_cuda, mode):
             assert _kept(e2, sub, el2, False) == _kept(e1, sub, el1, False)
     finally:
         os.environ.pop("HHUFF_MULTI_COPY", None)
+
+
+@pytest.mark.gpu
+def test_chunk_and_shard_share_one_layout(torch_cuda, oracle_codec):
+    """A chunk of the host pipeline and a shard copied to a peer device lie on their device buffer in one layout
+    (hhuff_hostplan.h ChunkLayout).  320 strings taken as the sub-range off[37 : 37 + 321] of a larger buffer, so
+    that the first byte is at neither a multiple of 80 (the base is rounded down) nor of 5 (floor(8 s0 / 5) rounds):
+    the pipeline with four chunks and more (HHUFF_HOST_COPY=1) and the peer-copy path of three shards
+    (HHUFF_MULTI_COPY=1) equal the one-device call and the oracle, decode with is-name bits and encode"""
+    import host_paths_model as M
+    from h2o_amd import codec
+
+    torch = torch_cuda
+    data, off, _, n = _batch("c3", 400, 23)
+    lo, m = 37, 320
+    dev = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()  # noqa: E731
+    # the Huffman strings of the same batch, back to back (a string that does not compress stays plain: as Huffman
+    # input it fails or decodes to something else, which every route must agree on too)
+    oe, oel, _ = oracle_codec.encode_batch(data, off, n)
+    parts = [oe[off[i]:off[i] + oel[i]] if oel[i] != FAIL else data[off[i]:off[i + 1]] for i in range(n)]
+    huff = np.concatenate(parts)
+    h_off = np.zeros(n + 1, np.uint32)
+    h_off[1:] = np.cumsum([p.size for p in parts])
+    hn = synth.bits_from_bools(np.random.default_rng(9).random(m) < 0.3)
+    saved = {k: os.environ.get(k) for k in ("HHUFF_HOST_COPY", "HHUFF_MULTI_COPY")}
+    os.environ["HHUFF_HOST_COPY"] = os.environ["HHUFF_MULTI_COPY"] = "1"
+    try:
+        for decode, buf, offs, names in ((True, huff, h_off, hn), (False, data, off, None)):
+            sub = np.ascontiguousarray(offs[lo:lo + m + 1])
+            s0, span = int(sub[0]), int(sub[m]) - int(sub[0])
+            assert s0 % 80 != 0 and s0 % 5 != 0
+            chunk_bytes = span // 5
+            assert len(M.cuts(sub, m, chunk_bytes)) - 1 >= 4
+            kw = dict(is_name_bits=names) if decode else {}
+            dkw = dict(is_name_bits=dev(names)) if decode else {}
+            one = codec.decode_batch if decode else codec.encode_batch
+            piped = codec.decode_batch_host_pipelined if decode else codec.encode_batch_host_pipelined
+            multi = codec.decode_batch_multi if decode else codec.encode_batch_multi
+            ref = (oracle_codec.decode_batch if decode else oracle_codec.encode_batch)(buf, sub, m, **kw)
+            a = one(dev(buf), dev(sub), m, in_size=buf.size, **dkw)
+            torch.cuda.synchronize()
+            b = piped(buf, sub, m, chunk_bytes=chunk_bytes, **kw)
+            c = multi([0, 0, 0], dev(buf), dev(sub), m, **dkw)
+            torch.cuda.synchronize()
+            a, c = [[t.cpu().numpy() for t in r] for r in (a, c)]
+            want_len, want_st = ref[1], ref[2]
+            for out, ln, st in (a, b, c):
+                np.testing.assert_array_equal(ln.view(np.uint32)[:m], want_len)
+                np.testing.assert_array_equal(st[:m], want_st)
+                assert _kept(out, sub, ln.view(np.uint32)[:m], decode) == _kept(ref[0], sub, want_len, decode)
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
