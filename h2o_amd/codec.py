@@ -222,6 +222,9 @@ def lib():
         L.hhuff_h2_control.restype = ctypes.c_int
         L.hhuff_h2_control.argtypes = ([_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint,
                                         ctypes.c_uint32] + [_vp] * 7 + [ctypes.c_uint64, _vp, _vp, _vp])
+        L.hhuff_h2_frame_data.restype = ctypes.c_int
+        L.hhuff_h2_frame_data.argtypes = ([_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint] +
+                                           [_vp] * 4 + [ctypes.c_uint64] + [_vp] * 4)
         L.hhuff_hpack_responses_set_peers.restype = ctypes.c_int
         L.hhuff_hpack_responses_set_peers.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
         L.hhuff_h3_deframe.restype = ctypes.c_int
@@ -250,7 +253,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_qpack_dsession_out_bound", "hhuff_conn_slab_size", "hhuff_conn_image_bound", "hhuff_conn_export",
             "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers", "hhuff_tokens_table_size", "hhuff_tokens_build",
             "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
-            "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers") + SLOTS_SYMBOLS
+            "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers",
+            "hhuff_h2_frame_data") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1050,6 +1054,45 @@ def hpack_responses_set_peers(peers, res, conn_first, nres, stream=None):
     bits) [nconn + 1]"""
     _check(lib().hhuff_hpack_responses_set_peers(_dp(peers), _dp(res), _dp(conn_first), conn_first.numel() - 1, nres,
                                                  _stream(stream)), "hhuff_hpack_responses_set_peers")
+
+
+# include/hhuff.h (2k''): hhuff_h2_send_t / hhuff_h2_sent_t as numpy records, and the section's constants
+H2_SEND_DTYPE = np.dtype([("body_off", "<u4"), ("body_len", "<u4"), ("stream_id", "<u4"), ("window", "<i4"), ("flags", "<u4"),
+                          ("max_frames", "<u4")])
+H2_SENT_DTYPE = np.dtype([("sent", "<u4"), ("nframes", "<u4"), ("out_off", "<u4"), ("flags", "<u4"), ("window", "<i4"),
+                          ("rsv", "<u4")])
+H2S_FINAL, H2S_TRAILERS = 1, 2
+H2T_END_STREAM, H2T_DONE, H2T_STREAM_WINDOW, H2T_ROOM, H2T_CONN_WINDOW, H2T_MAX_FRAMES = 1, 2, 4, 8, 16, 32
+H2D_EINVAL = -314
+
+
+def h2_frame_data(body, sends, send_first, peers, out_off, flags=0, body_size=None, nsend=None, out_size=None, stream=None,
+                  out=None):
+    """HTTP/2 DATA frames on the send side (include/hhuff.h hhuff_h2_frame_data) on device tensors: body uint8, sends a
+    uint8 tensor of H2_SEND_DTYPE records, send_first / out_off int32 (u32 bits) of nconn + 1 entries, peers a uint8
+    tensor of H2_PEER_DTYPE records.  Returns a dict of device tensors: sent (uint8, H2_SENT_DTYPE records, one per send
+    record), out_len, cstatus (per connection), out (the frames) and peers (the records to present next time: a new
+    tensor unless out={"peers": peers} updates in place).  out: a dict with some of these tensors preallocated.  No
+    host synchronisation (out_size given, or out["out"] preallocated)."""
+    import torch
+
+    dev = body.device
+    body_size = body.numel() if body_size is None else body_size
+    nsend = sends.numel() // 24 if nsend is None else nsend
+    nconn = send_first.numel() - 1
+    out = dict(out or {})
+    if "out" not in out and out_size is None:
+        out_size = int(out_off[-1].item()) & 0xFFFFFFFF
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32, u8 = torch.int32, torch.uint8
+    r = dict(sent=new("sent", nsend * 24, u8), out_len=new("out_len", nconn, i32), cstatus=new("cstatus", nconn, i32),
+             out=new("out", out_size or 0, u8), peers=new("peers", nconn * 40, u8))
+    if out_size is None:
+        out_size = r["out"].numel()
+    _check(lib().hhuff_h2_frame_data(_dp(body), body_size, _dp(sends), _dp(send_first), nsend, nconn, flags, _dp(peers),
+                                     _dp(r["peers"]), _dp(r["sent"]), _dp(r["out"]), out_size, _dp(out_off), _dp(r["out_len"]),
+                                     _dp(r["cstatus"]), _stream(stream)), "hhuff_h2_frame_data")
+    return r
 
 
 # include/hhuff.h (2l): hhuff_h3_stream_t / hhuff_h3_frame_t / hhuff_h3_settings_t as numpy records (peers: QPACK_PEER), and

@@ -1361,6 +1361,76 @@ int hhuff_h2_control(const uint8_t *in, uint64_t in_size,            /* in_size 
 int hhuff_hpack_responses_set_peers(const hhuff_h2_peer_t *peers, hhuff_hpack_response_t *res,
                                     const uint32_t *conn_first, uint32_t nconn, uint32_t nres, void *stream);
 
+/* (2k'') HTTP/2 DATA frames on the send side: response bodies that lie in device memory -> the DATA frames h2o would
+ *      queue on conn->_write.buf, cut by the peer's max_frame_size, the connection's and the streams' send windows
+ *      and the room in the buffer, for many connections at once.  h2o_http2_stream_send_pending_data, send_data,
+ *      calc_max_payload_size and commit_data_header (lib/http2/stream.c:107-184, 410-436),
+ *      h2o_http2_conn_get_buffer_window (include/h2o/http2_internal.h:298-319) without the socket's latency
+ *      optimisation, h2o_http2_encode_frame_header (lib/http2/frame.c:68-77).
+ *        body, body_size    the body bytes of all records
+ *        sends, send_first, nsend   connection c's records are sends[send_first[c] .. send_first[c+1]), clamped to
+ *                           nsend (the records `sends` and `sent` hold) as (2k') clamps frm_first; one record is one
+ *                           visit of a stream by the caller's scheduler, the records are served in the order listed
+ *        peers_in, peers_out   (2k')'s records (peers_out may be peers_in): max_frame_size and send_window are read,
+ *                           peers_out[c] is peers_in[c] with send_window reduced by the payload bytes sent
+ *        out, out_off       connection c writes out[out_off[c] .. out_off[c+1]), clamped to out_size as (2k') clamps
+ *                           rep_off: the region stands for conn->_write.buf, its size for capacity - size
+ *      One visit (W_c = send_window, W_s = the record's window, R = the room left in the region, L = the bytes left of
+ *      the record, m = max_frame_size) is one call of h2o_http2_stream_send_pending_data:
+ *        W_s <= 0: stop (_STREAM_WINDOW);  R <= 9: stop (_ROOM);  W_c <= 0: stop (_CONN_WINDOW);
+ *        n = min(m, R - 9, W_c, W_s, L);  with L == 0 and the record not FINAL, or with TRAILERS, nothing is written;
+ *        else the 9-byte header (length n, type 0, flags END_STREAM iff FINAL without TRAILERS and the frame takes the
+ *        record's last byte, the stream id) and the n bytes;  W_c, W_s, L -= n, R -= n + 9;  L == 0: stop (_DONE).
+ *      Visits repeat until one stops, or max_frames of them have been made (_MAX_FRAMES).  An empty FINAL body gets
+ *      its END_STREAM frame of length 0 only while both windows are above 0 and R > 9, as in h2o.  The windows and the
+ *      room carry over from a connection's record to its next.  The walk is not frame by frame: every frame of a
+ *      record is full except the last, so a record's frames follow from a closed form (h2o_amd/csrc/hhuff_h2data.h).
+ *      Per record sent[]: the body bytes consumed, the frames written, where its first frame header lies in `out`,
+ *      END_STREAM and the reason it stopped, its window afterwards.  Per connection out_len[c], peers_out[c] and
+ *      cstatus[c]: 0, or HHUFF_H2D_EINVAL for a record whose body range leaves body[0 .. body_size), whose stream_id
+ *      is 0 or above 2^31 - 1 or that has unknown flag bits, and for a peer whose max_frame_size is outside
+ *      16384 .. 16777215: the connection stops in front of that record, the earlier records stay written, sent[] of
+ *      that record and the later ones is not written.  Bytes of a region behind out_len[c] are not written.
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array, body_size or out_size >= 2^32
+ *      or non-zero flags; nconn == 0 returns HHUFF_OK.  Asynchronous on `stream`, no host synchronisation, workspace
+ *      from the library's pool, no atomics; bitwise deterministic.  Nothing in sends, send_first, out_off or peers_in
+ *      makes the call touch memory outside body, the connection's clamped region or the arrays' declared sizes. */
+typedef struct hhuff_h2_send {       /* 24 bytes: one visit of a stream by the caller's scheduler */
+    uint32_t body_off, body_len;     /* body[body_off .. body_off + body_len): the stream's pending bytes (stream->_data) */
+    uint32_t stream_id;              /* 1 .. 2^31 - 1 */
+    int32_t  window;                 /* stream->output_window on entry (may be <= 0) */
+    uint32_t flags;                  /* HHUFF_H2S_* */
+    uint32_t max_frames;             /* 0: until something runs out;  k: at most k calls of send_pending_data */
+} hhuff_h2_send_t;
+typedef struct hhuff_h2_sent {       /* 24 bytes, one per send record */
+    uint32_t sent, nframes;          /* body bytes consumed, DATA frames written */
+    uint32_t out_off;                /* offset in `out` of the record's first frame header (where it would be, if none) */
+    uint32_t flags;                  /* HHUFF_H2T_END_STREAM | why it stopped: one of the other HHUFF_H2T_* */
+    int32_t  window;                 /* the stream's window afterwards */
+    uint32_t rsv;                    /* 0 */
+} hhuff_h2_sent_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h2_send_t) == 24 && sizeof(hhuff_h2_sent_t) == 24, "record sizes");
+#else
+typedef char hhuff_h2_frame_data_record_sizes[sizeof(hhuff_h2_send_t) == 24 && sizeof(hhuff_h2_sent_t) == 24 ? 1 : -1];
+#endif
+#define HHUFF_H2S_FINAL 1u            /* send flags: send_state FINAL (the record holds the body's last bytes) */
+#define HHUFF_H2S_TRAILERS 2u         /* trailers or server-timing follow: no END_STREAM on DATA (commit_data_header) */
+#define HHUFF_H2T_END_STREAM 1u       /* sent flags: the record's last frame carries END_STREAM */
+#define HHUFF_H2T_DONE 2u             /* stopped: every byte of the record is sent */
+#define HHUFF_H2T_STREAM_WINDOW 4u    /* stopped: the stream's window is <= 0 */
+#define HHUFF_H2T_ROOM 8u             /* stopped: the region has no room for a header and a byte */
+#define HHUFF_H2T_CONN_WINDOW 16u     /* stopped: the connection's send window is <= 0 */
+#define HHUFF_H2T_MAX_FRAMES 32u      /* stopped: max_frames visits made */
+#define HHUFF_H2D_EINVAL (-314)       /* cstatus: a send record or the peer record is out of range */
+int hhuff_h2_frame_data(const uint8_t *body, uint64_t body_size,     /* body_size < 2^32 */
+                        const hhuff_h2_send_t *sends, const uint32_t *send_first /* [nconn + 1] */, uint32_t nsend,
+                        uint32_t nconn, unsigned flags,                     /* none yet: non-zero is HHUFF_EINVAL */
+                        const hhuff_h2_peer_t *peers_in, hhuff_h2_peer_t *peers_out,
+                        hhuff_h2_sent_t *sent,
+                        uint8_t *out, uint64_t out_size /* < 2^32 */, const uint32_t *out_off /* [nconn + 1] */,
+                        uint32_t *out_len, int32_t *cstatus, void *stream);
+
 /* (2l) HTTP/3 frames on the receive side: the bytes of many connections' QUIC streams -> the encoder-stream bytes
  *      and field sections the decoders of (2d) take, and the peers' SETTINGS.  One call is one step of every stream.
  *      It follows h2o_http3_read_frame (lib/http3/common.c:1057-1145), the request-stream handlers of h2o's server
