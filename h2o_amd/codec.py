@@ -43,6 +43,12 @@ class _QpackDsessionsStruct(ctypes.Structure):  # include/hhuff.h hhuff_qpack_ds
                 ("wake_first", _vp), ("nwake", _vp), ("parked", _vp), ("dflags", _vp), ("flags", ctypes.c_uint32)]
 
 
+class _H2StreamsParamsStruct(ctypes.Structure):  # include/hhuff.h hhuff_h2_streams_params_t
+    _fields_ = [("max_streams", ctypes.c_uint32), ("max_streams_for_priority", ctypes.c_uint32),
+                ("active_stream_window_size", ctypes.c_uint32), ("max_entries", ctypes.c_uint32),
+                ("max_request_entity_size", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("rsv", ctypes.c_uint32)]
+
+
 class _ConnFamilyStruct(ctypes.Structure):  # include/hhuff.h hhuff_conn_family_t
     _fields_ = [("family", ctypes.c_uint32), ("table_size", ctypes.c_uint32), ("max_inflight", ctypes.c_uint32),
                 ("max_blocked", ctypes.c_uint32)]
@@ -225,6 +231,17 @@ def lib():
         L.hhuff_h2_frame_data.restype = ctypes.c_int
         L.hhuff_h2_frame_data.argtypes = ([_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint] +
                                            [_vp] * 4 + [ctypes.c_uint64] + [_vp] * 4)
+        u32, u64, slots_p = ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(_ConnSlotsStruct)
+        L.hhuff_h2_streams_scratch_size.restype = u64
+        L.hhuff_h2_streams_scratch_size.argtypes = [u32, u32]
+        L.hhuff_h2_streams.restype = ctypes.c_int
+        L.hhuff_h2_streams.argtypes = ([slots_p, ctypes.POINTER(_H2StreamsParamsStruct), _vp, u64, _vp, _vp, _vp, u32, _vp, _vp, _vp,
+                                        u64] + [_vp] * 6 + [u64] + [_vp] * 6 + [u32, u32] + [_vp] * 6 + [u64, _vp, _vp, _vp, u64,
+                                                                                                      ctypes.c_uint, _vp])
+        L.hhuff_h2_streams_fill_sends.restype = ctypes.c_int
+        L.hhuff_h2_streams_fill_sends.argtypes = [slots_p, u32, _vp, u64, _vp, _vp, u32, u32, _vp, _vp]
+        L.hhuff_h2_streams_commit_sent.restype = ctypes.c_int
+        L.hhuff_h2_streams_commit_sent.argtypes = [slots_p, u32, _vp, u64, _vp, _vp, _vp, u32, u32, _vp]
         L.hhuff_hpack_responses_set_peers.restype = ctypes.c_int
         L.hhuff_hpack_responses_set_peers.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
         L.hhuff_h3_deframe.restype = ctypes.c_int
@@ -254,7 +271,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_conn_import", "hhuff_qpack_flatten_sessions_peers", "hhuff_tokens_table_size", "hhuff_tokens_build",
             "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
             "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers",
-            "hhuff_h2_frame_data") + SLOTS_SYMBOLS
+            "hhuff_h2_frame_data", "hhuff_h2_streams", "hhuff_h2_streams_scratch_size", "hhuff_h2_streams_fill_sends",
+            "hhuff_h2_streams_commit_sent") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1093,6 +1111,103 @@ def h2_frame_data(body, sends, send_first, peers, out_off, flags=0, body_size=No
                                      _dp(r["peers"]), _dp(r["sent"]), _dp(r["out"]), out_size, _dp(out_off), _dp(r["out_len"]),
                                      _dp(r["cstatus"]), _stream(stream)), "hhuff_h2_frame_data")
     return r
+
+
+# include/hhuff.h (2k'''): hhuff_h2_sev_t / hhuff_h2_stream_op_t as numpy records, and the section's constants
+H2_SEV_DTYPE = np.dtype([("stream_id", "<u4"), ("a", "<u4"), ("status", "<i2"), ("err", "<u2"), ("flags", "<u4")])
+H2_STREAM_OP_DTYPE = np.dtype([("stream_id", "<u4"), ("op", "<u4"), ("arg", "<u4"), ("rsv", "<u4")])
+H2ST_CONTINUE = 1
+H2SP_STREAM_BODIES = 1
+H2O_CLOSE, H2O_CREDIT, H2O_OPEN_PUSH = 1, 2, 3
+H2ST_SPACE, H2ST_EINVAL, H2ST_EFULL, H2ST_ENOENT, H2ST_ESLOT = -315, -316, -317, -318, -319
+(H2SE_OPENED, H2SE_BODY, H2SE_REQUEST_COMPLETE, H2SE_TRAILERS, H2SE_RESET_BY_PEER, H2SE_RESET_SENT, H2SE_WINDOW_UPDATE_SENT,
+ H2SE_IGNORED, H2SE_PRIORITY_ONLY_OPENED, H2SE_SEND_WINDOW_OPENED, H2SE_BAD_CONNECT, H2SE_INVALID_HEADER_CHAR,
+ H2SE_PRIORITY) = (1 << i for i in range(13))
+(H2ST_ERR_NONE, H2ST_ERR_HEADERS_STREAM_ID, H2ST_ERR_HEADERS_CLOSED, H2ST_ERR_TUNNEL_TRAILERS, H2ST_ERR_TRAILERS_END_STREAM,
+ H2ST_ERR_SELF_DEPENDENCY, H2ST_ERR_CONTINUATION_STREAM_ID, H2ST_ERR_DATA_FRAME, H2ST_ERR_TOO_MANY_IDLE,
+ H2ST_ERR_RST_STREAM_STREAM_ID, H2ST_ERR_WINDOW_UPDATE_STREAM_ID, H2ST_ERR_TRAILERS_PSEUDO_HEADER, H2ST_ERR_TRAILERS_HOST,
+ H2ST_ERR_HEADER_BLOCK) = range(14)
+
+
+def h2_streams_params(p):
+    """hhuff_h2_streams_params_t of a dict with its fields' names (rsv 0)"""
+    return _H2StreamsParamsStruct(p["max_streams"], p["max_streams_for_priority"], p["active_stream_window_size"], p["max_entries"],
+                                  p["max_request_entity_size"], p["flags"], 0)
+
+
+def h2_streams_scratch_size(nslots, max_entries) -> int:
+    """include/hhuff.h hhuff_h2_streams_scratch_size; 0: a max_entries the calls refuse"""
+    return int(lib().hhuff_h2_streams_scratch_size(nslots, max_entries))
+
+
+def h2_streams_entries(max_streams, max_streams_for_priority, max_push):
+    """include/hhuff.h hhuff_h2_streams_entries"""
+    return min(max_streams + 1 + max_streams_for_priority + max_push, 0xFFFFFFFF)
+
+
+def h2_streams_reply_bound(frame_slots, nops):
+    """include/hhuff.h hhuff_h2_streams_reply_bound"""
+    return 43 * frame_slots + 13 * nops
+
+
+def _slots_ref(slots):
+    return None if slots is None else ctypes.byref(_ConnSlotsStruct(_dp(slots.slot), _dp(slots.flags), slots.nslots))
+
+
+def h2_streams(params, scratch, data, frames, nframes, frm_first, frm_cap, ctl, nctl, ctl_rep, ctl_rep_off, blocks, conn_first,
+               bstatus, req, arena, blk_off, value_off, value_len, peers, rep_off, ops=None, op_first=None, flags=0, slots=None,
+               in_size=None, ctl_rep_size=None, arena_size=None, rep_size=None, stream=None, out=None):
+    """The HTTP/2 stream table (include/hhuff.h hhuff_h2_streams) on device tensors: params a dict (h2_streams_params),
+    scratch a uint8 tensor of h2_streams_scratch_size bytes kept between calls (flags=H2ST_CONTINUE), data .. frm_cap
+    h2_deframe's, ctl / nctl / ctl_rep / ctl_rep_off h2_control's ctl, nctl, rep and rep_off, blocks / conn_first the
+    de-framer's, bstatus / req / arena / blk_off / value_off / value_len hpack_parse_requests', peers h2_control's, ops a
+    uint8 tensor of H2_STREAM_OP_DTYPE records with op_first int32 [nconn + 1], rep_off int32 [nconn + 1], slots a ConnSlots.
+    Returns a dict of device tensors: sev (uint8, H2_SEV_DTYPE records, one per frame slot), op_sev, nstr, sstatus, serr,
+    rep_len (per connection) and rep.  No host synchronisation (rep_size given, or out["rep"] preallocated)."""
+    import torch
+
+    dev = frames.device
+    nconn = frm_first.numel() - 1
+    nops = 0 if ops is None else ops.numel() // 16
+    out = dict(out or {})
+    if "rep" not in out and rep_size is None:
+        rep_size = int(rep_off[-1].item()) & 0xFFFFFFFF
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32, u8 = torch.int32, torch.uint8
+    r = dict(sev=new("sev", frm_cap * 16, u8), op_sev=new("op_sev", nops * 16, u8), nstr=new("nstr", nconn, i32),
+             sstatus=new("sstatus", nconn, i32), serr=new("serr", nconn, i32), rep_len=new("rep_len", nconn, i32),
+             rep=new("rep", rep_size or 0, u8))
+    size = lambda t, given: t.numel() if given is None else given  # noqa: E731
+    _check(lib().hhuff_h2_streams(_slots_ref(slots), h2_streams_params(params), _dp(data), size(data, in_size), _dp(frames),
+                                  _dp(nframes), _dp(frm_first), frm_cap, _dp(ctl), _dp(nctl), _dp(ctl_rep), size(ctl_rep, ctl_rep_size),
+                                  _dp(ctl_rep_off), _dp(blocks), _dp(conn_first), _dp(bstatus), _dp(req), _dp(arena),
+                                  size(arena, arena_size), _dp(blk_off), _dp(value_off), _dp(value_len), _dp(peers), _dp(ops),
+                                  _dp(op_first), nops, nconn, _dp(r["sev"]), _dp(r["op_sev"]), _dp(r["nstr"]), _dp(r["sstatus"]),
+                                  _dp(r["serr"]), _dp(r["rep"]), size(r["rep"], rep_size), _dp(rep_off), _dp(r["rep_len"]),
+                                  _dp(scratch), scratch.numel(), flags, _stream(stream)), "hhuff_h2_streams")
+    return r
+
+
+def h2_streams_fill_sends(max_entries, scratch, sends, send_first, slots=None, nsend=None, stream=None, miss=None):
+    """include/hhuff.h hhuff_h2_streams_fill_sends: the streams' send windows into the H2_SEND_DTYPE records `sends` (uint8
+    tensor, in place); returns miss (uint8 per record: 1 no such stream, 2 listed earlier in the connection's range)"""
+    import torch
+
+    nsend = sends.numel() // 24 if nsend is None else nsend
+    if miss is None:
+        miss = torch.empty(max(1, nsend), dtype=torch.uint8, device=sends.device)
+    _check(lib().hhuff_h2_streams_fill_sends(_slots_ref(slots), max_entries, _dp(scratch), scratch.numel(), _dp(sends),
+                                             _dp(send_first), nsend, send_first.numel() - 1, _dp(miss), _stream(stream)),
+           "hhuff_h2_streams_fill_sends")
+    return miss
+
+
+def h2_streams_commit_sent(max_entries, scratch, sends, sent, send_first, slots=None, nsend=None, stream=None):
+    """include/hhuff.h hhuff_h2_streams_commit_sent: what h2_frame_data sent leaves the streams' send windows"""
+    nsend = sends.numel() // 24 if nsend is None else nsend
+    _check(lib().hhuff_h2_streams_commit_sent(_slots_ref(slots), max_entries, _dp(scratch), scratch.numel(), _dp(sends), _dp(sent),
+                                              _dp(send_first), nsend, send_first.numel() - 1, _stream(stream)),
+           "hhuff_h2_streams_commit_sent")
 
 
 # include/hhuff.h (2l): hhuff_h3_stream_t / hhuff_h3_frame_t / hhuff_h3_settings_t as numpy records (peers: QPACK_PEER), and

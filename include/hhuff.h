@@ -1431,6 +1431,208 @@ int hhuff_h2_frame_data(const uint8_t *body, uint64_t body_size,     /* body_siz
                         uint8_t *out, uint64_t out_size /* < 2^32 */, const uint32_t *out_off /* [nconn + 1] */,
                         uint32_t *out_len, int32_t *cstatus, void *stream);
 
+/* (2k''') HTTP/2 stream table: h2o's conn->streams kept on the device, one slab per connection, and the server-side
+ *      stream rules applied to the outputs of (2k), (2k') and (2c') -- handle_headers_frame, handle_incoming_request,
+ *      handle_trailing_headers, expect_continuation_of_headers, handle_data_frame behind the connection window,
+ *      handle_request_body_chunk, update_stream_input_window, handle_priority_frame, handle_rst_stream_frame,
+ *      handle_window_update_frame, the stream halves of handle_settings_frame and handle_goaway_frame
+ *      (lib/http2/connection.c:49-52, 451-460, 470-481, 518-607, 618-820, 976-1138, 1151-1286), h2o_http2_stream_open /
+ *      _close / _reset (lib/http2/stream.c:36-105), h2o_http2_stream_prepare_for_request
+ *      (include/h2o/http2_internal.h:428-445) and h2o_http2_window_update (include/h2o/http2_common.h:234-251).  With it
+ *      a server step needs no host code between the socket's bytes and a request's verdict.
+ *        slots              (2h), or NULL: connection c uses slab c.  A refused connection (point 3 there) touches no
+ *                           slab: sstatus HHUFF_H2ST_ESLOT, nstr = rep_len = 0, no event written
+ *        params             the server's configuration (host memory, read before the call returns)
+ *        in .. frm_cap      hhuff_h2_deframe's arrays; ctl, nctl, ctl_rep, ctl_rep_off: hhuff_h2_control's records, counts,
+ *                           reply bytes and region offsets (its rep and rep_off); blocks, conn_first: the de-framer's;
+ *                           bstatus, req, arena, value_off, value_len: hhuff_hpack_parse_requests' for those blocks and
+ *                           blk_off (the call reads the :method and :path values only); blocks, bstatus and req hold
+ *                           frm_cap records, blk_off frm_cap + 1, value_off and value_len in_size; peers: the control
+ *                           call's peers_out.  All as they are and on the same stream.
+ *        ops, op_first      connection c's ops are ops[op_first[c] .. op_first[c+1]), clamped to nops: what the
+ *                           application did to its streams since the last step, applied in order in front of its frames
+ *        sev, op_sev        one event per frame slot, at the frame record's index, and one per op; slots that are not
+ *                           walked are not written
+ *        rep, rep_off       connection c's bytes to send go to rep[rep_off[c] .. rep_off[c+1]), clamped to rep_size;
+ *                           hhuff_h2_streams_reply_bound(its frame slots, its ops) always fits
+ *      Per connection: nstr[c], the frames handled; sstatus[c] / serr[c], the first connection-level failure (h2o's return
+ *      value and the HHUFF_H2ST_ERR_* that names its err_desc, or HHUFF_H2ST_SPACE / _EINVAL / _EFULL / _ESLOT); rep_len[c].
+ *      Frames at and beyond frm_first[c] + nctl[c] are not walked, the frame the control call failed on included: its
+ *      failure precedes anything here.  The walk stops at the first connection-level failure; that frame's event (slot
+ *      nstr[c]) is the last one written -- not written for _SPACE, _EINVAL and _EFULL.  The caller drops a connection
+ *      that failed, as h2o does; its slab is left as h2o leaves its own connection.
+ *      rep is the merged stream: first the ops' own bytes, then for every handled frame the bytes the control call
+ *      wrote for it (ctl[i].reply_len of ctl_rep), then this call's own, which is the order h2o queues them on
+ *      conn->_write.buf.  A frame this call fails on still contributes its control reply.  After this call the caller
+ *      sends rep, not ctl_rep.  A region too small for a frame's (an op's) bytes stops the connection in front of it with
+ *      HHUFF_H2ST_SPACE, nothing of it applied.
+ *      The ops (an op's failure is its own: op_sev[k].status, the walk goes on):
+ *        HHUFF_H2O_CLOSE      the response is out (h2o_http2_stream_close): the entry leaves, nothing is written
+ *        HHUFF_H2O_CREDIT     update_stream_input_window(arg), as write_streaming_body / proceed_request do: the event
+ *                             has WINDOW_UPDATE_SENT when a WINDOW_UPDATE was owed; arg <= INT32_MAX
+ *        HHUFF_H2O_OPEN_PUSH  a promised stream (even id): raises push_stream_ids.max_open; the entry has the send window
+ *                             peers[c].initial_window_size and no request body and is not counted in pull.open; refused
+ *                             once a GOAWAY has come
+ *        _EINVAL: an unknown op, stream id 0 or above 2^31 - 1, rsv != 0, a CREDIT above INT32_MAX, an OPEN_PUSH of an odd
+ *        or a present id or after GOAWAY; _ENOENT: CLOSE / CREDIT of a stream that is not there; _EFULL: no room
+ *      The frames, each in h2o's order of tests (E_x: HHUFF_H2ST_ERR_x; "RST(x)": a RST_STREAM with that code is
+ *      written, the event is RESET_SENT with status x and the entry, if any, leaves; the walk goes on):
+ *        HEADERS opening a block   (blocks[].first_frame) even id: -1 E_HEADERS_STREAM_ID.  id <= pull max_open: no
+ *                           entry -5 E_HEADERS_CLOSED; body not OPEN* -1 E_HEADERS_STREAM_ID; a tunnel -1
+ *                           E_TUNNEL_TRAILERS; no END_STREAM -1 E_TRAILERS_END_STREAM; else the block is a trailers block.
+ *                           id > pull max_open: HHUFF_H2B_SELF_DEPENDENCY -1 E_SELF_DEPENDENCY; else a priority-only
+ *                           entry is reused or one is opened, then h2o_http2_stream_prepare_for_request: max_open = id,
+ *                           the stream moves from priority.open to pull.open, output_window = initial_window_size
+ *        CONTINUATION       a stream id other than the block's: -1 E_CONTINUATION_STREAM_ID
+ *        block end, a head  (the event sits on the frame that ended the block) bstatus other than 0 and -254 is the
+ *                           connection's failure (E_HEADER_BLOCK; req[b].err names the text).  Then the pseudo-header
+ *                           maps of connection.c:642-677 (CONNECT with and without :protocol, CONNECT-UDP with path "/"
+ *                           and no :protocol, the normal case): a mismatch is RST(-1).  Then pull.open > max_streams:
+ *                           RST(-7).  Else OPENED, a = the block's index, content_length recorded.  A -254 block:
+ *                           OPENED | INVALID_HEADER_CHAR (h2o's 400, the caller's).  A CONNECT with a content-length or
+ *                           with END_STREAM: OPENED | BAD_CONNECT (h2o's 400).  An accepted CONNECT is a tunnel with body
+ *                           state OPEN, and update_stream_input_window(active_stream_window_size - 65535) runs at once
+ *                           (process_request, connection.c:180-182).  Else END_STREAM on the block: REQUEST_COMPLETE;
+ *                           without it the body state is OPEN_BEFORE_FIRST_FRAME.  expect: (417, 100) stays with the
+ *                           caller; the request record names the field.
+ *        block end, trailers   h2o parses with NULL pseudo-header pointers: req[b].exists_map != 0 is -1
+ *                           E_TRAILERS_PSEUDO_HEADER, a host field (req[b].authority set without the map's bit) -1
+ *                           E_TRAILERS_HOST, then any bstatus != 0 (the soft -254 too) is the connection's failure,
+ *                           E_HEADER_BLOCK.  Else TRAILERS and handle_request_body_chunk(empty, END_STREAM)
+ *        DATA               no entry: id <= pull max_open RST(-5), above -1 E_DATA_FRAME.  Body not OPEN*: RST(-5).
+ *                           Else input_window -= frame length, update_stream_input_window(padding); with data or
+ *                           END_STREAM handle_request_body_chunk: received > max_request_entity_size RST(-7); with a
+ *                           content-length, received above it, or different at END_STREAM, RST(-1); BODY, a = the
+ *                           bytes to deliver (ctl[i].a is where they lie); END_STREAM: REQUEST_COMPLETE; the first
+ *                           frame without END_STREAM: with STREAM_BODIES the request is handed over (the caller
+ *                           credits the window with ops), without it update_stream_input_window(active_stream_window_size
+ *                           - 65535).  update_stream_input_window(d): bytes_unnotified += d; once bytes_unnotified >=
+ *                           the window (compared as unsigned numbers, as h2o does: an overdrawn window owes nothing) a
+ *                           WINDOW_UPDATE carrying it is written, the window rises by it: WINDOW_UPDATE_SENT
+ *        PRIORITY           entry: PRIORITY (the tree is the caller's; ctl[i] has the payload).  No entry: even id or
+ *                           id <= pull max_open IGNORED; priority.open >= max_streams_for_priority -11
+ *                           E_TOO_MANY_IDLE; else an IDLE entry: PRIORITY_ONLY_OPENED
+ *        RST_STREAM         an idle id (by parity, against the matching max_open): -1 E_RST_STREAM_STREAM_ID; else
+ *                           RESET_BY_PEER and the entry leaves, or IGNORED
+ *        WINDOW_UPDATE      on a stream.  The control record's STREAM_ERROR: RESET_SENT, status -1, the entry leaves if
+ *                           there is one (the RST_STREAM is among the control replies).  Idle id: -1
+ *                           E_WINDOW_UPDATE_STREAM_ID.  No entry: IGNORED.  output_window + increment > INT32_MAX:
+ *                           RST(-3).  Else the window rises; SEND_WINDOW_OPENED when it went from <= 0 to > 0
+ *        SETTINGS           with WINDOW_DELTA: ctl[i].b is added to every entry's output_window; an entry whose sum would
+ *                           pass INT32_MAX keeps its window (h2o drops the return value, connection.c:1181); a = the
+ *                           streams whose window opened, SEND_WINDOW_OPENED if any
+ *        GOAWAY             push max_open = 0x7ffffffe
+ *        anything else      the event is zeroed
+ *      State.  scratch = device memory of hhuff_h2_streams_scratch_size(nslots or nconn, params->max_entries) bytes,
+ *      16-byte aligned, kept by the caller between calls.  Without HHUFF_H2ST_CONTINUE, or with HHUFF_CONN_RESET in
+ *      slots->flags[c], a connection starts empty.  With max_entries >= hhuff_h2_streams_entries(...) a pull stream or a
+ *      priority-only stream always finds room (h2o bounds them at max_streams + 1 and max_streams_for_priority); below
+ *      that an insert without room stops the connection with HHUFF_H2ST_EFULL.
+ *      hhuff_h2_streams_fill_sends writes sends[r].window from the stream's output_window for (2k'')'s records
+ *      (send_first and nsend as there); miss[r] = 1 for no such stream, 2 for a stream already listed earlier in the
+ *      connection's range, both with window 0, so that hhuff_h2_frame_data stops them with _STREAM_WINDOW.
+ *      hhuff_h2_streams_commit_sent subtracts sent[r].sent from the window of every stream the fill listed.  Both handle
+ *      a connection's records in order, one lane a connection.
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array (ops may be NULL with nops == 0),
+ *      in_size, arena_size, ctl_rep_size or rep_size >= 2^32, an unknown flag bit, max_entries == 0 or above 2^24,
+ *      active_stream_window_size outside 65535 .. INT32_MAX, a scratch too small or misaligned, and (2h) point 4;
+ *      nconn == 0 returns HHUFF_OK.  Asynchronous on `stream`, no host synchronisation, no atomics; bitwise
+ *      deterministic.  Every input record is untrusted: counts and ranges are clamped as (2k') clamps them; a payload,
+ *      block, field or method range that leaves its array, a frame whose block record does not name it and a control
+ *      reply that leaves the connection's region stop the connection with HHUFF_H2ST_EINVAL; nothing makes the call
+ *      touch memory outside the arrays' declared sizes or the connection's slab. */
+typedef struct hhuff_h2_streams_params { /* 32 bytes; globalconf->http2.* and globalconf->max_request_entity_size */
+    uint32_t max_streams, max_streams_for_priority;
+    uint32_t active_stream_window_size;  /* 65535 .. INT32_MAX */
+    uint32_t max_entries;                /* entries of a connection's table: hhuff_h2_streams_entries() */
+    uint64_t max_request_entity_size;
+    uint32_t flags;                      /* HHUFF_H2SP_* */
+    uint32_t rsv;                        /* 0 */
+} hhuff_h2_streams_params_t;
+typedef struct hhuff_h2_stream_op {  /* 16 bytes */
+    uint32_t stream_id, op /* HHUFF_H2O_* */, arg, rsv /* 0 */;
+} hhuff_h2_stream_op_t;
+typedef struct hhuff_h2_sev {        /* 16 bytes: one per frame record and one per op */
+    uint32_t stream_id;              /* the stream the frame or op is about; 0: none */
+    uint32_t a;
+    int16_t  status;                 /* h2o's error: of the RST_STREAM, or of the connection's failure; an op's status */
+    uint16_t err;                    /* HHUFF_H2ST_ERR_* */
+    uint32_t flags;                  /* HHUFF_H2SE_* */
+} hhuff_h2_sev_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h2_streams_params_t) == 32 && sizeof(hhuff_h2_stream_op_t) == 16 && sizeof(hhuff_h2_sev_t) == 16,
+              "record sizes");
+#else
+typedef char hhuff_h2_streams_record_sizes[sizeof(hhuff_h2_streams_params_t) == 32 && sizeof(hhuff_h2_stream_op_t) == 16 &&
+                                           sizeof(hhuff_h2_sev_t) == 16 ? 1 : -1];
+#endif
+#define HHUFF_H2ST_CONTINUE 1u        /* flags: the tables the previous call left in scratch carry over */
+#define HHUFF_H2SP_STREAM_BODIES 1u   /* params flags: h2o_req_can_stream_request is true for every request */
+#define HHUFF_H2O_CLOSE 1u
+#define HHUFF_H2O_CREDIT 2u
+#define HHUFF_H2O_OPEN_PUSH 3u
+#define HHUFF_H2ST_SPACE (-315)       /* sstatus: the reply region cannot take the next frame's (op's) bytes */
+#define HHUFF_H2ST_EINVAL (-316)      /* sstatus: an input record is out of range; op status: a malformed op */
+#define HHUFF_H2ST_EFULL (-317)       /* sstatus / op status: the table has no room for the stream */
+#define HHUFF_H2ST_ENOENT (-318)      /* op status: no such stream */
+#define HHUFF_H2ST_ESLOT (-319)       /* sstatus: the connection was refused ((2h) point 3) */
+#define HHUFF_H2SE_OPENED 1u                /* event flags: a request's HEADERS passed; a = the block index */
+#define HHUFF_H2SE_BODY 2u                  /* a = the bytes of the DATA record to deliver */
+#define HHUFF_H2SE_REQUEST_COMPLETE 4u      /* END_STREAM has arrived: h2o would execute_or_enqueue_request */
+#define HHUFF_H2SE_TRAILERS 8u
+#define HHUFF_H2SE_RESET_BY_PEER 16u
+#define HHUFF_H2SE_RESET_SENT 32u           /* status = the RST_STREAM's h2o error; the entry is gone */
+#define HHUFF_H2SE_WINDOW_UPDATE_SENT 64u
+#define HHUFF_H2SE_IGNORED 128u
+#define HHUFF_H2SE_PRIORITY_ONLY_OPENED 256u
+#define HHUFF_H2SE_SEND_WINDOW_OPENED 512u  /* the send window went from <= 0 to > 0: h2o_http2_scheduler_activate's cue */
+#define HHUFF_H2SE_BAD_CONNECT 1024u        /* with OPENED: "Invalid CONNECT request", h2o's 400 */
+#define HHUFF_H2SE_INVALID_HEADER_CHAR 2048u /* with OPENED: the block's -254, h2o's 400 */
+#define HHUFF_H2SE_PRIORITY 4096u           /* PRIORITY on a stream that is there */
+#define HHUFF_H2ST_ERR_NONE 0u
+#define HHUFF_H2ST_ERR_HEADERS_STREAM_ID 1u       /* "invalid stream id in HEADERS frame" */
+#define HHUFF_H2ST_ERR_HEADERS_CLOSED 2u          /* "closed stream id in HEADERS frame" */
+#define HHUFF_H2ST_ERR_TUNNEL_TRAILERS 3u         /* "trailer cannot be used in a CONNECT request" */
+#define HHUFF_H2ST_ERR_TRAILERS_END_STREAM 4u     /* "trailing HEADERS frame MUST have END_STREAM flag set" */
+#define HHUFF_H2ST_ERR_SELF_DEPENDENCY 5u         /* "stream cannot depend on itself" */
+#define HHUFF_H2ST_ERR_CONTINUATION_STREAM_ID 6u  /* "unexpected stream id in CONTINUATION frame" */
+#define HHUFF_H2ST_ERR_DATA_FRAME 7u              /* "invalid DATA frame" */
+#define HHUFF_H2ST_ERR_TOO_MANY_IDLE 8u           /* "too many streams in idle/closed state" */
+#define HHUFF_H2ST_ERR_RST_STREAM_STREAM_ID 9u    /* "unexpected stream id in RST_STREAM frame" */
+#define HHUFF_H2ST_ERR_WINDOW_UPDATE_STREAM_ID 10u /* "invalid stream id in WINDOW_UPDATE frame" */
+#define HHUFF_H2ST_ERR_TRAILERS_PSEUDO_HEADER 11u /* "invalid pseudo header" */
+#define HHUFF_H2ST_ERR_TRAILERS_HOST 12u          /* "found an unexpected connection-specific header" */
+#define HHUFF_H2ST_ERR_HEADER_BLOCK 13u           /* h2o_hpack_parse_request's own: req[b].err names the text */
+uint64_t hhuff_h2_streams_scratch_size(uint32_t nslots, uint32_t max_entries);
+static inline uint32_t hhuff_h2_streams_entries(uint32_t max_streams, uint32_t max_streams_for_priority, uint32_t max_push) {
+    uint64_t n = (uint64_t)max_streams + 1u + max_streams_for_priority + max_push;
+    return n > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)n;
+}
+/* a frame owes at most the control call's 17 bytes and 26 of its own, an op 13 */
+static inline uint64_t hhuff_h2_streams_reply_bound(uint64_t frame_slots, uint64_t nops) { return 43u * frame_slots + 13u * nops; }
+int hhuff_h2_streams(const hhuff_conn_slots_t *slots, const hhuff_h2_streams_params_t *params,
+                     const uint8_t *in, uint64_t in_size,
+                     const hhuff_h2_frame_t *frames, const uint32_t *nframes, const uint32_t *frm_first, uint32_t frm_cap,
+                     const hhuff_h2_ctl_t *ctl, const uint32_t *nctl, const uint8_t *ctl_rep, uint64_t ctl_rep_size,
+                     const uint32_t *ctl_rep_off /* [nconn + 1] */,
+                     const hhuff_h2_block_t *blocks, const uint32_t *conn_first /* [nconn + 1] */,
+                     const int32_t *bstatus, const hhuff_request_t *req,
+                     const uint8_t *arena, uint64_t arena_size, const uint32_t *blk_off,
+                     const uint32_t *value_off, const uint32_t *value_len,
+                     const hhuff_h2_peer_t *peers,
+                     const hhuff_h2_stream_op_t *ops, const uint32_t *op_first /* [nconn + 1] */, uint32_t nops,
+                     uint32_t nconn,
+                     hhuff_h2_sev_t *sev, hhuff_h2_sev_t *op_sev,
+                     uint32_t *nstr, int32_t *sstatus, uint32_t *serr,
+                     uint8_t *rep, uint64_t rep_size, const uint32_t *rep_off /* [nconn + 1] */, uint32_t *rep_len,
+                     void *scratch, uint64_t scratch_size, unsigned flags, void *stream);
+int hhuff_h2_streams_fill_sends(const hhuff_conn_slots_t *slots, uint32_t max_entries, void *scratch, uint64_t scratch_size,
+                                hhuff_h2_send_t *sends, const uint32_t *send_first /* [nconn + 1] */, uint32_t nsend,
+                                uint32_t nconn, uint8_t *miss /* [nsend] */, void *stream);
+int hhuff_h2_streams_commit_sent(const hhuff_conn_slots_t *slots, uint32_t max_entries, void *scratch, uint64_t scratch_size,
+                                 const hhuff_h2_send_t *sends, const hhuff_h2_sent_t *sent,
+                                 const uint32_t *send_first /* [nconn + 1] */, uint32_t nsend, uint32_t nconn, void *stream);
+
 /* (2l) HTTP/3 frames on the receive side: the bytes of many connections' QUIC streams -> the encoder-stream bytes
  *      and field sections the decoders of (2d) take, and the peers' SETTINGS.  One call is one step of every stream.
  *      It follows h2o_http3_read_frame (lib/http3/common.c:1057-1145), the request-stream handlers of h2o's server
