@@ -242,6 +242,8 @@ def lib():
         L.hhuff_h2_streams_fill_sends.argtypes = [slots_p, u32, _vp, u64, _vp, _vp, u32, u32, _vp, _vp]
         L.hhuff_h2_streams_commit_sent.restype = ctypes.c_int
         L.hhuff_h2_streams_commit_sent.argtypes = [slots_p, u32, _vp, u64, _vp, _vp, _vp, u32, u32, _vp]
+        L.hhuff_h2_bodies.restype = ctypes.c_int
+        L.hhuff_h2_bodies.argtypes = [_vp, u64, _vp, _vp, _vp, u32, _vp, u32, ctypes.c_uint, _vp, u64] + [_vp] * 6
         L.hhuff_hpack_responses_set_peers.restype = ctypes.c_int
         L.hhuff_hpack_responses_set_peers.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
         L.hhuff_h3_deframe.restype = ctypes.c_int
@@ -272,7 +274,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
             "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers",
             "hhuff_h2_frame_data", "hhuff_h2_streams", "hhuff_h2_streams_scratch_size", "hhuff_h2_streams_fill_sends",
-            "hhuff_h2_streams_commit_sent") + SLOTS_SYMBOLS
+            "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1208,6 +1210,43 @@ def h2_streams_commit_sent(max_entries, scratch, sends, sent, send_first, slots=
     _check(lib().hhuff_h2_streams_commit_sent(_slots_ref(slots), max_entries, _dp(scratch), scratch.numel(), _dp(sends), _dp(sent),
                                               _dp(send_first), nsend, send_first.numel() - 1, _stream(stream)),
            "hhuff_h2_streams_commit_sent")
+
+
+# include/hhuff.h (2k''''): hhuff_h2_body_run_t as numpy records, and the section's constants
+H2_BODY_RUN_DTYPE = np.dtype([("stream_id", "<u4"), ("out_off", "<u4"), ("len", "<u4"), ("nframes", "<u4"), ("first_frame", "<u4"),
+                              ("flags", "<u4"), ("rsv", "<u4", (2,))])
+H2BR_COMPLETE, H2BR_RESET = 1, 2
+H2BD_SPACE, H2BD_EINVAL = -323, -324
+
+
+def h2_bodies_bound(in_bytes):
+    """include/hhuff.h hhuff_h2_bodies_bound"""
+    return in_bytes
+
+
+def h2_bodies(data, ctl, sev, frm_first, frm_cap, nstr, out_off, flags=0, in_size=None, out_size=None, stream=None, out=None):
+    """HTTP/2 request bodies on the receive side (include/hhuff.h hhuff_h2_bodies) on device tensors: data h2_deframe's
+    input, ctl h2_control's records, sev / nstr h2_streams' events and counts, frm_first and frm_cap as those calls had
+    them, out_off int32 (u32 bits) of nconn + 1 entries.  Returns a dict of device tensors: out (the runs' bytes), runs
+    (uint8, H2_BODY_RUN_DTYPE records, one per frame slot), nrun, out_len, bstatus (per connection).  out: a dict with
+    some of these tensors preallocated.  No host synchronisation (out_size given, or out["out"] preallocated)."""
+    import torch
+
+    dev = data.device
+    nconn = frm_first.numel() - 1
+    out = dict(out or {})
+    if "out" not in out and out_size is None:
+        out_size = int(out_off[-1].item()) & 0xFFFFFFFF
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32, u8 = torch.int32, torch.uint8
+    r = dict(out=new("out", out_size or 0, u8), runs=new("runs", frm_cap * 32, u8), nrun=new("nrun", nconn, i32),
+             out_len=new("out_len", nconn, i32), bstatus=new("bstatus", nconn, i32))
+    if out_size is None:
+        out_size = r["out"].numel()
+    _check(lib().hhuff_h2_bodies(_dp(data), data.numel() if in_size is None else in_size, _dp(ctl), _dp(sev), _dp(frm_first), frm_cap,
+                                 _dp(nstr), nconn, flags, _dp(r["out"]), out_size, _dp(out_off), _dp(r["runs"]), _dp(r["nrun"]),
+                                 _dp(r["out_len"]), _dp(r["bstatus"]), _stream(stream)), "hhuff_h2_bodies")
+    return r
 
 
 # include/hhuff.h (2l): hhuff_h3_stream_t / hhuff_h3_frame_t / hhuff_h3_settings_t as numpy records (peers: QPACK_PEER), and

@@ -145,6 +145,25 @@ HHUFF_DATA_HD void store16(uint8_t* d, const uint32_t v[4]) {  // d: 16-byte ali
 #endif
 }
 
+// Bytes [b0, b1) of the line at d, and no other: whole dwords where the job has them, else bytes -- the rest of a
+// job's first and last line is its neighbours'.
+HHUFF_DATA_HD void store_part(uint8_t* d, const uint32_t v[4], int b0, int b1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int q = 0; q < 4; ++q) {
+        if (b0 <= 4 * q && 4 * q + 4 <= b1) {
+            reinterpret_cast<uint32_t*>(d)[q] = v[q];
+        } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+            for (int i = 0; i < 4; ++i)
+                if (4 * q + i >= b0 && 4 * q + i < b1) d[4 * q + i] = (uint8_t)(v[q] >> (8 * i));
+        }
+    }
+}
+
 // byte x (0 .. 8) of a DATA frame's header, as header() writes it
 HHUFF_DATA_HD uint32_t header_byte(uint32_t length, uint32_t flags, uint32_t stream_id, int x) {
     const uint32_t h0 = ((length >> 16) & 0xffu) | (length & 0xff00u) | ((length & 0xffu) << 16);  // length, type 0
@@ -206,24 +225,10 @@ HHUFF_DATA_HD void write_line(uint64_t body, const Job& J, uint64_t d0, uint64_t
         }
         v[q] = word;
     }
-    if (b1 - b0 == 16) {
+    if (b1 - b0 == 16)
         store16(d, v);
-        return;
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int q = 0; q < 4; ++q) {  // whole dwords where the job has them, else bytes: the neighbours' bytes are theirs
-        if (b0 <= 4 * q && 4 * q + 4 <= b1) {
-            reinterpret_cast<uint32_t*>(d)[q] = v[q];
-        } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = 0; i < 4; ++i)
-                if (4 * q + i >= b0 && 4 * q + i < b1) d[4 * q + i] = (uint8_t)(v[q] >> (8 * i));
-        }
-    }
+    else
+        store_part(d, v, b0, b1);
 }
 
 HHUFF_DATA_HD bool peer_ok(const hhuff_h2_peer_t& P) { return P.max_frame_size >= 16384u && P.max_frame_size <= 16777215u; }

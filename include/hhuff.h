@@ -1633,6 +1633,73 @@ int hhuff_h2_streams_commit_sent(const hhuff_conn_slots_t *slots, uint32_t max_e
                                  const hhuff_h2_send_t *sends, const hhuff_h2_sent_t *sent,
                                  const uint32_t *send_first /* [nconn + 1] */, uint32_t nsend, uint32_t nconn, void *stream);
 
+/* (2k'''') HTTP/2 request bodies on the receive side: a step's DATA payloads, which lie in the receive buffer between
+ *      frame headers, pad-length bytes, padding and other streams' frames, gathered into contiguous bytes per stream,
+ *      for many connections at once.  It is what handle_request_body_chunk (lib/http2/connection.c:518-607) appends to
+ *      the stream's req_body.buf: the bytes of a stream's runs over successive steps, in order, are what that buffer
+ *      would have held -- req.entity at END_STREAM, or the chunks of write_req for a streamed request.
+ *        in, in_size        the receive buffer of (2k)
+ *        ctl                hhuff_h2_control's records: of a BODY slot with bytes, a (where they lie in `in`) is read
+ *        sev, nstr          hhuff_h2_streams' events and its counts of frames handled
+ *        frm_first, frm_cap, nconn   as those calls had them.  All as they are and on the same stream; nothing else of
+ *                           the earlier calls is read
+ *        out, out_off       connection c writes out[out_off[c] .. out_off[c+1]), clamped to out_size as (2k') clamps
+ *                           rep_off; hhuff_h2_bodies_bound(the bytes of the connection's input) always fits, since
+ *                           the payloads are disjoint parts of the input
+ *        runs               runs[frm_first[c] + k], k < nrun[c]: run k's record; the other slots are not written
+ *      Connection c's slots frm_first[c] .. frm_first[c] + min(nstr[c], its slots) - 1 are walked in order, the slots
+ *      clamped to frm_cap as (2k') clamps them.  A slot whose event has HHUFF_H2SE_BODY belongs to the run of
+ *      sev[i].stream_id; the stream's first such slot opens the run.  Runs are numbered in the order of their first
+ *      slots and lie back to back from the region's first byte in that order; within a run the payloads
+ *      in[ctl[i].a .. ctl[i].a + sev[i].a) lie back to back in slot order.  With sev[i].a == 0 -- an empty END_STREAM
+ *      frame -- ctl[i] is not looked at; such a slot still opens a run (of length 0 if nothing follows) and counts in
+ *      nframes.  Slots without BODY add no bytes.
+ *      A run's flags: HHUFF_H2BR_COMPLETE if a walked event of its stream, at or behind the run's first slot, has
+ *      HHUFF_H2SE_REQUEST_COMPLETE (a trailers block's event, which has no BODY, included); HHUFF_H2BR_RESET if a walked
+ *      event of its stream behind the run's first slot has RESET_SENT or RESET_BY_PEER: h2o has disposed of the buffer
+ *      then, the bytes are written all the same and the flag tells the caller.
+ *      Per connection: nrun[c], out_len[c] (the runs' bytes together) and bstatus[c]: 0, HHUFF_H2BD_SPACE when the runs'
+ *      bytes exceed the region, or HHUFF_H2BD_EINVAL for a BODY event on stream 0 or a payload that leaves
+ *      in[0 .. in_size).  A connection with a status has nrun = out_len = 0, and no byte of its region and none of its
+ *      run records is written; the other connections are not affected.  Bytes of a region behind out_len[c], and
+ *      everything outside the regions, are not written.
+ *      Out of scope: appending across steps into buffers the library owns would need a device allocator -- the caller
+ *      chains a stream's runs; and HTTP/3 DATA payloads, for which (2l)'s frame records carry what a sibling call needs.
+ *      The plan is one lane per connection in wire order with a table of the step's streams in workspace (two entries
+ *      a slot: linear in the slots, however many streams); the copy deals the 16-byte destination lines of all
+ *      payloads over the grid (h2o_amd/csrc/hhuff_h2bodies.h, hhuff_h2bodies.hip).
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array, in_size or out_size >= 2^32 or
+ *      non-zero flags; nconn == 0 returns HHUFF_OK.  Asynchronous on `stream`, no host synchronisation, workspace
+ *      (80 bytes a frame slot) from the library's pool, no atomics: positions come from scans, equal input gives equal
+ *      bytes.  Every input record is untrusted: counts and offsets are clamped, and nothing makes the call touch memory
+ *      outside the arrays' declared sizes.  With a frm_first that gives two connections the same slots, their records
+ *      and the bytes of their regions are unspecified.  Of `in` the call reads the aligned dwords (by address) that
+ *      hold a payload's bytes, as (2k) does. */
+typedef struct hhuff_h2_body_run {   /* 32 bytes */
+    uint32_t stream_id;
+    uint32_t out_off, len;           /* out[out_off .. out_off + len): the stream's body bytes of this step */
+    uint32_t nframes;                /* its BODY slots */
+    uint32_t first_frame;            /* the slot index of the first of them */
+    uint32_t flags;                  /* HHUFF_H2BR_* */
+    uint32_t rsv[2];                 /* 0 */
+} hhuff_h2_body_run_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h2_body_run_t) == 32, "record sizes");
+#else
+typedef char hhuff_h2_bodies_record_sizes[sizeof(hhuff_h2_body_run_t) == 32 ? 1 : -1];
+#endif
+#define HHUFF_H2BR_COMPLETE 1u        /* run flags: END_STREAM has arrived -- the body is whole */
+#define HHUFF_H2BR_RESET 2u           /* the stream was reset behind the run's first slot */
+#define HHUFF_H2BD_SPACE (-323)       /* bstatus: the runs' bytes exceed the connection's region */
+#define HHUFF_H2BD_EINVAL (-324)      /* bstatus: a BODY event on stream 0, or a payload that leaves in[0 .. in_size) */
+static inline uint64_t hhuff_h2_bodies_bound(uint64_t in_bytes) { return in_bytes; }
+int hhuff_h2_bodies(const uint8_t *in, uint64_t in_size,             /* in_size < 2^32 */
+                    const hhuff_h2_ctl_t *ctl, const hhuff_h2_sev_t *sev,
+                    const uint32_t *frm_first /* [nconn + 1] */, uint32_t frm_cap, const uint32_t *nstr, uint32_t nconn,
+                    unsigned flags,                                   /* none yet: non-zero is HHUFF_EINVAL */
+                    uint8_t *out, uint64_t out_size /* < 2^32 */, const uint32_t *out_off /* [nconn + 1] */,
+                    hhuff_h2_body_run_t *runs, uint32_t *nrun, uint32_t *out_len, int32_t *bstatus, void *stream);
+
 /* (2l) HTTP/3 frames on the receive side: the bytes of many connections' QUIC streams -> the encoder-stream bytes
  *      and field sections the decoders of (2d) take, and the peers' SETTINGS.  One call is one step of every stream.
  *      It follows h2o_http3_read_frame (lib/http3/common.c:1057-1145), the request-stream handlers of h2o's server
