@@ -16,6 +16,8 @@ ARCH = os.environ.get("HHUFF_ARCH", "gfx950")
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
                "-Wno-unused-function"]
+# flags of single units: hhuff_h3bodies.hip is compiled with the packed fp32 instructions switched off
+UNIT_FLAGS = {"hhuff_h3bodies.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():
@@ -34,6 +36,7 @@ def stale():
 
 
 def _compile(hipcc, src, obj, extra, verbose):
+    extra = extra + UNIT_FLAGS.get(os.path.basename(src), [])
     cmd = [hipcc] + HIPCC_FLAGS + ["-c", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + extra + [src, "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)

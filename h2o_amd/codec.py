@@ -249,6 +249,10 @@ def lib():
         L.hhuff_h3_deframe.restype = ctypes.c_int
         L.hhuff_h3_deframe.argtypes = ([_vp, ctypes.c_uint64] + [_vp, ctypes.c_uint32] * 3 + [ctypes.c_uint64, ctypes.c_uint] +
                                        [_vp] * 19 + [ctypes.c_uint64, ctypes.c_uint32, _vp])
+        L.hhuff_h3_bodies.restype = ctypes.c_int
+        L.hhuff_h3_bodies.argtypes = [_vp, u64, _vp, _vp, _vp, u32, u32, _vp, _vp, ctypes.c_uint, _vp, u64, _vp, _vp, _vp]
+        L.hhuff_h3_frame_data.restype = ctypes.c_int
+        L.hhuff_h3_frame_data.argtypes = [_vp, u64, _vp, u32, ctypes.c_uint, _vp, u64, _vp, _vp, _vp]
         _lib = L
     return _lib
 
@@ -274,7 +278,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
             "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers",
             "hhuff_h2_frame_data", "hhuff_h2_streams", "hhuff_h2_streams_scratch_size", "hhuff_h2_streams_fill_sends",
-            "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies") + SLOTS_SYMBOLS
+            "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies", "hhuff_h3_bodies", "hhuff_h3_frame_data") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1302,6 +1306,72 @@ def h3_deframe(data, str_off, conn_str, frm_first, frm_cap, st_in, max_frame_pay
                                   _dp(r["sec_stream_id"]), _dp(r["sec_stream"]), _dp(r["totals"]), _dp(r["peers"]),
                                   _dp(r["settings"]), _dp(r["got_settings"]), _dp(r.get("arena_off")), arena_fixed or 0,
                                   arena_per_byte, _stream(stream)), "hhuff_h3_deframe")
+    return r
+
+
+# include/hhuff.h (2l'), (2l''): hhuff_h3_body_run_t / hhuff_h3_send_t as numpy records, and the sections' constants
+H3_BODY_RUN_DTYPE = np.dtype([("out_off", "<u4"), ("len", "<u4"), ("nframes", "<u4"), ("flags", "<u4"), ("received", "<u8"),
+                              ("status", "<i4"), ("rsv", "<u4")])
+H3_SEND_DTYPE = np.dtype([("body_off", "<u4"), ("body_len", "<u4")])
+H3BR_OVERFLOW = 1
+H3BD_SPACE, H3BD_EINVAL = -325, -326
+
+
+def h3_bodies_bound(in_bytes):
+    """include/hhuff.h hhuff_h3_bodies_bound"""
+    return in_bytes
+
+
+def h3_frame_data_bound(body_bytes, nsend):
+    """include/hhuff.h hhuff_h3_frame_data_bound"""
+    return body_bytes + 9 * nsend
+
+
+def h3_bodies(data, frames, nframes, frm_first, frm_cap, content_length=None, received=None, flags=0, in_size=None,
+              out_size=None, stream=None, out=None):
+    """HTTP/3 bodies on the receive side (include/hhuff.h hhuff_h3_bodies) on device tensors: data, frames, nframes,
+    frm_first and frm_cap as h3_deframe had and returned them, content_length / received int64 (u64 bits) per stream or
+    None.  Returns a dict of device tensors: out (the runs' bytes, packed), runs (uint8, H3_BODY_RUN_DTYPE records, one
+    per stream) and totals [2].  out: a dict with some of these tensors preallocated; out_size defaults to
+    out["out"]'s size, or to h3_bodies_bound(in_size).  No host synchronisation."""
+    import torch
+
+    dev = data.device
+    in_size = data.numel() if in_size is None else in_size
+    nstr = frm_first.numel() - 1
+    out = dict(out or {})
+    if "out" not in out and out_size is None:
+        out_size = h3_bodies_bound(in_size)
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    r = dict(out=new("out", out_size or 0, torch.uint8), runs=new("runs", nstr * 32, torch.uint8), totals=new("totals", 2, torch.int32))
+    if out_size is None:
+        out_size = r["out"].numel()
+    _check(lib().hhuff_h3_bodies(_dp(data), in_size, _dp(frames), _dp(nframes), _dp(frm_first), frm_cap, nstr, _dp(content_length),
+                                 _dp(received), flags, _dp(r["out"]), out_size, _dp(r["runs"]), _dp(r["totals"]), _stream(stream)),
+           "hhuff_h3_bodies")
+    return r
+
+
+def h3_frame_data(body, sends, flags=0, body_size=None, nsend=None, out_size=None, stream=None, out=None):
+    """HTTP/3 DATA frames on the send side (include/hhuff.h hhuff_h3_frame_data) on device tensors: body uint8, sends a
+    uint8 tensor of H3_SEND_DTYPE records.  Returns a dict of device tensors: out (the frames, packed), frm_off
+    [nsend + 1] and sstatus [nsend].  out: a dict with some of these tensors preallocated; out_size defaults to
+    out["out"]'s size, or to h3_frame_data_bound(body_size, nsend).  No host synchronisation."""
+    import torch
+
+    dev = body.device
+    body_size = body.numel() if body_size is None else body_size
+    nsend = sends.numel() // 8 if nsend is None else nsend
+    out = dict(out or {})
+    if "out" not in out and out_size is None:
+        out_size = h3_frame_data_bound(body_size, nsend)
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    r = dict(out=new("out", out_size or 0, torch.uint8), frm_off=new("frm_off", nsend + 1, torch.int32),
+             sstatus=new("sstatus", nsend, torch.int32))
+    if out_size is None:
+        out_size = r["out"].numel()
+    _check(lib().hhuff_h3_frame_data(_dp(body), body_size, _dp(sends), nsend, flags, _dp(r["out"]), out_size, _dp(r["frm_off"]),
+                                     _dp(r["sstatus"]), _stream(stream)), "hhuff_h3_frame_data")
     return r
 
 

@@ -1664,7 +1664,7 @@ int hhuff_h2_streams_commit_sent(const hhuff_conn_slots_t *slots, uint32_t max_e
  *      run records is written; the other connections are not affected.  Bytes of a region behind out_len[c], and
  *      everything outside the regions, are not written.
  *      Out of scope: appending across steps into buffers the library owns would need a device allocator -- the caller
- *      chains a stream's runs; and HTTP/3 DATA payloads, for which (2l)'s frame records carry what a sibling call needs.
+ *      chains a stream's runs.  HTTP/3 DATA payloads are (2l').
  *      The plan is one lane per connection in wire order with a table of the step's streams in workspace (two entries
  *      a slot: linear in the slots, however many streams); the copy deals the 16-byte destination lines of all
  *      payloads over the grid (h2o_amd/csrc/hhuff_h2bodies.h, hhuff_h2bodies.hip).
@@ -1884,6 +1884,86 @@ int hhuff_h3_deframe(const uint8_t *in, uint64_t in_size,            /* in_size 
                      uint32_t *totals /* [3]: nsec, section bytes, encoder bytes */,
                      hhuff_qpack_peer_t *peers, hhuff_h3_settings_t *settings, uint32_t *got_settings,
                      uint64_t *arena_off, uint64_t arena_fixed, uint32_t arena_per_byte, void *stream);
+
+/* (2l') HTTP/3 bodies on the receive side: a step's DATA payloads, as (2l) lists them, gathered into contiguous bytes
+ *      per stream -- what handle_input_expect_data_payload (lib/http3/server.c:1388-1409) appends to stream->req_body,
+ *      with the content-length test of handle_input_expect_data (server.c:1431-1438).
+ *        in, in_size, frames, nframes, frm_first, frm_cap, nstr   as hhuff_h3_deframe had them (frm_first: nstr + 1
+ *                           entries), as they are and on the same stream
+ *        content_length     NULL, or per stream h2o's req.content_length; UINT64_MAX: none (h2o's SIZE_MAX)
+ *        received           NULL (all 0), or per stream req_body_bytes_received of the earlier steps
+ *      Stream s owns the slots frm_first[s] .. + min(nframes[s], its slots clamped to frm_cap as (2l) clamps them).  A
+ *      slot with type == 0 is a DATA slot, its bytes in[payload_off .. payload_off + avail); it is bad when they leave
+ *      in[0 .. in_size) or avail > length, and a bad slot adds no bytes.  The output is packed: stream s's place begins
+ *      at the sum of the DATA bytes of all slots in front of its first -- cuts and statuses do not move it, so
+ *      placement is one scan over the slots -- and holds its payloads back to back in slot order.  An empty DATA frame
+ *      adds no bytes and counts in nframes; other types add nothing.
+ *      The cut: with P(i) the stream's DATA bytes in slots before i, a DATA slot i that has a header (hdr_off !=
+ *      payload_off) fails when content_length[s] - (received[s] + P(i)) < length(i); h2o resets the stream there.  The
+ *      run's len and nframes count what lies in front of the first failing slot, its flags hold HHUFF_H3BR_OVERFLOW,
+ *      and the bytes of its place behind len are unspecified.  The first failing slot is found by bisection, which is
+ *      exact for a stream as (2l) lists it: every DATA frame but the last of a step complete.
+ *      runs[s].status: HHUFF_H3BD_EINVAL for received[s] > content_length[s] (h2o never has it) or a bad slot;
+ *      HHUFF_H3BD_SPACE when the place ends behind out_size -- an empty place that begins behind out_size too, so every
+ *      run behind the first that does not fit reports it, and an empty one that ends at out_size does not.  Such a run
+ *      has len = 0, received unchanged and nframes = its DATA slots, and no byte of its place is required to be
+ *      written.  Nothing at or behind out_size and nothing behind the last place is ever written;
+ *      hhuff_h3_bodies_bound(in_size) always fits what (2l) lists.
+ *      totals[0] = the end of the last place (the DATA bytes of all slots, saturated at 2^32 - 1), totals[1] = the DATA
+ *      slots.  Out of scope: appending across steps (the caller chains runs, as with the HTTP/2 call), the
+ *      end-of-stream comparison of server.c:1176 (runs[s].received is what it needs), and what a reset stream's later
+ *      slots mean.
+ *      Device arrays.  Returns HHUFF_EINVAL, before any device call, for a NULL array other than content_length and
+ *      received, in_size > 2^32 - 3, out_size >= 2^32 or non-zero flags; nstr == 0 returns HHUFF_OK.  Asynchronous on
+ *      `stream`, no host synchronisation, workspace (16 bytes a frame slot) from the library's pool, no atomics:
+ *      positions come from scans, equal input gives equal bytes.  Every input record is untrusted; a frm_first that
+ *      does not rise gives unspecified records and bytes, inside the arrays' declared sizes.  Of `in` the call reads the
+ *      aligned dwords (by address) that hold a payload's bytes, as (2k) does.  The plan is a lane per frame slot, never
+ *      per stream: one stream of 16,384 frames is planned as 4,096 streams of 4 are (h2o_amd/csrc/hhuff_h3bodies.hip). */
+typedef struct hhuff_h3_body_run {   /* 32 bytes, one per stream */
+    uint32_t out_off, len;           /* out[out_off .. out_off + len): the stream's body bytes of this step */
+    uint32_t nframes;                /* its DATA slots (empty and continued ones included) in front of the cut */
+    uint32_t flags;                  /* HHUFF_H3BR_OVERFLOW */
+    uint64_t received;               /* req_body_bytes_received afterwards: received_in + len */
+    int32_t  status;                 /* 0, HHUFF_H3BD_SPACE, HHUFF_H3BD_EINVAL */
+    uint32_t rsv;                    /* 0 */
+} hhuff_h3_body_run_t;
+#define HHUFF_H3BR_OVERFLOW 1u        /* run flags: a DATA frame passed content-length; the run ends in front of it */
+#define HHUFF_H3BD_SPACE (-325)       /* a run's place, or a frame, passes out_size */
+#define HHUFF_H3BD_EINVAL (-326)      /* a bad DATA slot, received > content_length, or a record that leaves body */
+static inline uint64_t hhuff_h3_bodies_bound(uint64_t in_bytes) { return in_bytes; }
+int hhuff_h3_bodies(const uint8_t *in, uint64_t in_size,             /* in_size <= 2^32 - 3 */
+                    const hhuff_h3_frame_t *frames, const uint32_t *nframes,
+                    const uint32_t *frm_first /* [nstr + 1] */, uint32_t frm_cap, uint32_t nstr,
+                    const uint64_t *content_length, const uint64_t *received,
+                    unsigned flags,                                   /* none yet: non-zero is HHUFF_EINVAL */
+                    uint8_t *out, uint64_t out_size /* < 2^32 */,
+                    hhuff_h3_body_run_t *runs, uint32_t *totals /* [2] */, void *stream);
+
+/* (2l'') HTTP/3 DATA frames on the send side: do_send's body part (lib/http3/server.c:1830-1854) with
+ *      flatten_data_frame_header (server.c:1694-1709).  Send record k makes one DATA frame: the type byte 0x00, the
+ *      payload size as the shortest QUIC varint (quicly_encodev: 1, 2, 4 or 8 bytes below 2^6, 2^14, 2^30 and above),
+ *      then body[body_off .. body_off + body_len).  A record of 0 bytes makes nothing (payload_size != 0 guards the
+ *      header).  There are no windows: QUIC owns flow control.  The frames lie packed in record order, frame k at
+ *      out[frm_off[k] .. frm_off[k+1]), so a stream's records listed in a row give its send-buffer bytes in a row.
+ *      frm_off are the packed places whether or not they fit (saturated at 2^32 - 1).  sstatus[k]: HHUFF_H3BD_EINVAL
+ *      for a record whose range leaves body[0 .. body_size), which occupies 0 bytes; HHUFF_H3BD_SPACE for a frame that
+ *      ends behind out_size: neither it nor any frame behind it is written, the frames before it stand.  A record of 0
+ *      bytes behind such a frame reports HHUFF_H3BD_SPACE as well: its place lies behind out_size.  SEND_STATE_FINAL /
+ *      shutdown_by_generator, final_size and the HEADERS frame in front (hhuff_qpack_flatten_responses) stay with the
+ *      caller.  Device arrays; HHUFF_EINVAL, before any device call, for a NULL array, body_size or out_size >= 2^32 or
+ *      non-zero flags; nsend == 0 returns HHUFF_OK and writes nothing.  Otherwise as (2l'): the same scan and the same
+ *      copy kernel, workspace 16 bytes a record. */
+typedef struct hhuff_h3_send { uint32_t body_off, body_len; } hhuff_h3_send_t;   /* 8 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h3_body_run_t) == 32 && sizeof(hhuff_h3_send_t) == 8, "record sizes");
+#else
+typedef char hhuff_h3_bodies_record_sizes[sizeof(hhuff_h3_body_run_t) == 32 && sizeof(hhuff_h3_send_t) == 8 ? 1 : -1];
+#endif
+static inline uint64_t hhuff_h3_frame_data_bound(uint64_t body_bytes, uint64_t nsend) { return body_bytes + 9 * nsend; }
+int hhuff_h3_frame_data(const uint8_t *body, uint64_t body_size /* < 2^32 */, const hhuff_h3_send_t *sends, uint32_t nsend,
+                        unsigned flags, uint8_t *out, uint64_t out_size /* < 2^32 */,
+                        uint32_t *frm_off /* [nsend + 1] */, int32_t *sstatus /* [nsend] */, void *stream);
 
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
