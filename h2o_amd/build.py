@@ -16,8 +16,10 @@ ARCH = os.environ.get("HHUFF_ARCH", "gfx950")
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
                "-Wno-unused-function"]
-# flags of single units: hhuff_h3bodies.hip is compiled with the packed fp32 instructions switched off
-UNIT_FLAGS = {"hhuff_h3bodies.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# flags of single units: hhuff_h3bodies.hip and hhuff_h2simage.hip are compiled with the packed fp32 instructions
+# switched off
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"hhuff_h3bodies.hip": NO_PACKED_FP32, "hhuff_h2simage.hip": NO_PACKED_FP32}
 
 
 def sources():

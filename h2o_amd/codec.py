@@ -242,6 +242,11 @@ def lib():
         L.hhuff_h2_streams_fill_sends.argtypes = [slots_p, u32, _vp, u64, _vp, _vp, u32, u32, _vp, _vp]
         L.hhuff_h2_streams_commit_sent.restype = ctypes.c_int
         L.hhuff_h2_streams_commit_sent.argtypes = [slots_p, u32, _vp, u64, _vp, _vp, _vp, u32, u32, _vp]
+        L.hhuff_h2_streams_image_bound.restype = u64
+        L.hhuff_h2_streams_image_bound.argtypes = [u32]
+        for name in ("hhuff_h2_streams_export", "hhuff_h2_streams_import"):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [u32, _vp, u64, u32, _vp, u32, _vp, _vp, _vp, _vp, _vp]
         L.hhuff_h2_bodies.restype = ctypes.c_int
         L.hhuff_h2_bodies.argtypes = [_vp, u64, _vp, _vp, _vp, u32, _vp, u32, ctypes.c_uint, _vp, u64] + [_vp] * 6
         L.hhuff_hpack_responses_set_peers.restype = ctypes.c_int
@@ -278,7 +283,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_intern_strings", "hhuff_intern_fields", "hhuff_intern_headers", "hhuff_h2_deframe",
             "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers",
             "hhuff_h2_frame_data", "hhuff_h2_streams", "hhuff_h2_streams_scratch_size", "hhuff_h2_streams_fill_sends",
-            "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies", "hhuff_h3_bodies", "hhuff_h3_frame_data") + SLOTS_SYMBOLS
+            "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies", "hhuff_h3_bodies", "hhuff_h3_frame_data",
+            "hhuff_h2_streams_image_bound", "hhuff_h2_streams_export", "hhuff_h2_streams_import") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1214,6 +1220,48 @@ def h2_streams_commit_sent(max_entries, scratch, sends, sent, send_first, slots=
     _check(lib().hhuff_h2_streams_commit_sent(_slots_ref(slots), max_entries, _dp(scratch), scratch.numel(), _dp(sends), _dp(sent),
                                               _dp(send_first), nsend, send_first.numel() - 1, _stream(stream)),
            "hhuff_h2_streams_commit_sent")
+
+
+def h2_streams_image_bound(max_entries) -> int:
+    """include/hhuff.h hhuff_h2_streams_image_bound: the largest image of one connection's table; 0: a max_entries the image
+    calls refuse (0, or above 2048)"""
+    return int(lib().hhuff_h2_streams_image_bound(int(max_entries)))
+
+
+def h2_streams_export(max_entries, scratch, nslots, slot, img=None, img_off=None, stream=None):
+    """hhuff_h2_streams_export of the slots in `slot` (int32 device tensor, u32 bits) of the stream-table `scratch` (nslots
+    slabs of max_entries), as conn_export: img None runs the size query, lays the regions out back to back and writes the
+    images; with img and img_off (int64 device tensor [n + 1]) the caller's regions are used, one too small giving
+    IMG_SPACE and the length needed -> (img, img_off, img_len, status)"""
+    import torch
+
+    n = slot.numel()
+    dev = scratch.device
+    img_len = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    status = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    L, st = lib(), _stream(stream)
+    head = [int(max_entries), _dp(scratch), scratch.numel() * scratch.element_size(), int(nslots), _dp(slot), n]
+    if img is None:
+        _check(L.hhuff_h2_streams_export(*head, None, None, _dp(img_len), _dp(status), st), "hhuff_h2_streams_export")
+        img_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        img_off[1:] = torch.cumsum(img_len[:n].to(torch.int64), 0)
+        img = torch.empty(max(16, int(img_off[-1])), dtype=torch.uint8, device=dev)
+    _check(L.hhuff_h2_streams_export(*head, _dp(img), _dp(img_off), _dp(img_len), _dp(status), st), "hhuff_h2_streams_export")
+    return img, img_off, img_len[:n], status[:n]
+
+
+def h2_streams_import(max_entries, scratch, nslots, slot, img, img_off, img_len, stream=None):
+    """hhuff_h2_streams_import: item k's image (img[img_off[k] .. +img_len[k])) into slot slot[k] of the stream-table
+    `scratch` of max_entries -- any that holds the image's streams -> status (int32 device tensor: 0, IMG_EINVAL,
+    IMG_EFORMAT or IMG_EPARAM; a refused item's slab is untouched)"""
+    import torch
+
+    n = slot.numel()
+    status = torch.empty(max(1, n), dtype=torch.int32, device=scratch.device)
+    _check(lib().hhuff_h2_streams_import(int(max_entries), _dp(scratch), scratch.numel() * scratch.element_size(), int(nslots),
+                                         _dp(slot), n, _dp(img), _dp(img_off), _dp(img_len), _dp(status), _stream(stream)),
+           "hhuff_h2_streams_import")
+    return status[:n]
 
 
 # include/hhuff.h (2k''''): hhuff_h2_body_run_t as numpy records, and the section's constants

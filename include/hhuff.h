@@ -1540,7 +1540,38 @@ int hhuff_h2_frame_data(const uint8_t *body, uint64_t body_size,     /* body_siz
  *      deterministic.  Every input record is untrusted: counts and ranges are clamped as (2k') clamps them; a payload,
  *      block, field or method range that leaves its array, a frame whose block record does not name it and a control
  *      reply that leaves the connection's region stop the connection with HHUFF_H2ST_EINVAL; nothing makes the call
- *      touch memory outside the arrays' declared sizes or the connection's slab. */
+ *      touch memory outside the arrays' declared sizes or the connection's slab.
+ *      Images.  hhuff_h2_streams_export serialises the tables of listed slots into position-independent images and
+ *      hhuff_h2_streams_import rebuilds a table from an image in any slot of any stream-table scratch -- of any
+ *      max_entries that holds its streams, so a scratch can grow or shrink while connections are open.  These are the
+ *      connection images of (2i) for this family: slot[n], img, img_off[n + 1], img_len[n], status[n], the host-side
+ *      refusals (max_entries in the place of the family parameters) and the contract are those of (2i) points 1-3, 5, 6
+ *      and 8; status[k] is 0 or one of HHUFF_IMG_SPACE / _EINVAL / _EFORMAT / _EPARAM; slot ownership in import is (2h)
+ *      point 3.  Export only reads scratch; import writes nothing to a slab before the whole image has been checked.
+ *      Both are asynchronous on `stream`, without host synchronisation, and bitwise deterministic.
+ *        The image: [header 32][state 32][count x 48], 64 + 48 * count bytes (hhuff_h2_streams_image_bound: at
+ *        count = max_entries).
+ *          header  as (2i) point 7 with family = 5 (no HHUFF_FAM_* value: hhuff_conn_import answers such an image with
+ *                  HHUFF_IMG_EPARAM, another family -- an empty one, shorter than any of (2i)'s, with HHUFF_IMG_EFORMAT)
+ *                  and the three parameter words 0
+ *          state   +0 pull max_open  +4 push max_open  +8 pull streams open  +12 priority-only streams open  +16 count
+ *                  +20, +24, +28 reserved, 0
+ *          record  the table's entry: +0 stream_id  +4 u8 state, body, flags, 0  +8 bytes_unnotified  +12 mark
+ *                  +16 i64 output_window  +24 i64 input_window  +32 u64 received  +40 u64 content_length; ascending
+ *                  stream_id; mark = 1 for a stream the last hhuff_h2_streams_fill_sends listed and
+ *                  hhuff_h2_streams_commit_sent has not yet paid for, else 0
+ *        The image is canonical: it holds no slot index, no fill epoch and no max_entries, and two connections whose
+ *        future behaviour is the same have byte-identical images, whatever probe history, deletions and table sizes
+ *        produced them.  An imported connection's marks stand for its last fill, so a connection moved between
+ *        hhuff_h2_streams_fill_sends and hhuff_h2_streams_commit_sent still pays once.  The slab import leaves is a
+ *        function of the image and max_entries alone.
+ *        Import refuses with HHUFF_IMG_EFORMAT: a length that is not img_len[k], not inside the region or not
+ *        64 + 48 * count; a wrong magic, version or family; a non-zero parameter or reserved word; a stream id that is 0,
+ *        above 2^31 - 1 or not above the record's in front (so no id twice); state > 3, body > 3, flags > 15, a
+ *        non-zero pad byte, mark > 1.  A well-formed image of more streams than the destination's max_entries:
+ *        HHUFF_IMG_EPARAM.  Counters and windows that lie about content only are the caller's problem ((2i) point 6).
+ *        Both calls take max_entries from 1 to 2048 (h2o's defaults give 117): above that they return HHUFF_EINVAL and
+ *        hhuff_h2_streams_image_bound returns 0.  Images of larger tables are out of scope. */
 typedef struct hhuff_h2_streams_params { /* 32 bytes; globalconf->http2.* and globalconf->max_request_entity_size */
     uint32_t max_streams, max_streams_for_priority;
     uint32_t active_stream_window_size;  /* 65535 .. INT32_MAX */
@@ -1632,6 +1663,13 @@ int hhuff_h2_streams_fill_sends(const hhuff_conn_slots_t *slots, uint32_t max_en
 int hhuff_h2_streams_commit_sent(const hhuff_conn_slots_t *slots, uint32_t max_entries, void *scratch, uint64_t scratch_size,
                                  const hhuff_h2_send_t *sends, const hhuff_h2_sent_t *sent,
                                  const uint32_t *send_first /* [nconn + 1] */, uint32_t nsend, uint32_t nconn, void *stream);
+uint64_t hhuff_h2_streams_image_bound(uint32_t max_entries);   /* 64 + 48 * max_entries; 0: refused parameters */
+int hhuff_h2_streams_export(uint32_t max_entries, const void *scratch, uint64_t scratch_size, uint32_t nslots,
+                            const uint32_t *slot, uint32_t n, uint8_t *img, const uint64_t *img_off,
+                            uint32_t *img_len, int32_t *status, void *stream);
+int hhuff_h2_streams_import(uint32_t max_entries, void *scratch, uint64_t scratch_size, uint32_t nslots,
+                            const uint32_t *slot, uint32_t n, const uint8_t *img, const uint64_t *img_off,
+                            const uint32_t *img_len, int32_t *status, void *stream);
 
 /* (2k'''') HTTP/2 request bodies on the receive side: a step's DATA payloads, which lie in the receive buffer between
  *      frame headers, pad-length bytes, padding and other streams' frames, gathered into contiguous bytes per stream,
