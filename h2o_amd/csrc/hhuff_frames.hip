@@ -126,17 +126,22 @@ __global__ __launch_bounds__(256) void frm_finish_kernel(FrmArgs A) {
     if (A.arena_off) A.arena_off[b] = A.arena_fixed * (b < nblk ? b : nblk) + (uint64_t)A.arena_per_byte * off;
 }
 
+// the workspace of a call: its size with base = NULL, its pointers with the allocation
+uint64_t frm_carve(FrmArgs& A, uint32_t wgrid, uint8_t* base) {
+    Carve cv{base};
+    A.job = cv.take<uint4>(A.frm_cap);
+    A.count = cv.take<uint2>(A.nconn);
+    A.part = cv.take<uint2>(wgrid);
+    return cv.off;
+}
+
 hipError_t launch_deframe(FrmArgs& A, hipStream_t stream) {
     const uint32_t wgrid = (uint32_t)(((uint64_t)A.nconn + kWalkThreads - 1u) / kWalkThreads);
-    const uint64_t conn_bytes = ((uint64_t)A.nconn * 8u + 15u) & ~15ull;
-    const uint64_t job_bytes = (uint64_t)A.frm_cap * 16u;
     uint8_t* ws = nullptr;
-    hipError_t e = work_alloc((void**)&ws, job_bytes + conn_bytes + (uint64_t)wgrid * 8u + 16u, stream);
+    hipError_t e = work_alloc((void**)&ws, frm_carve(A, wgrid, nullptr), stream);
     if (e != hipSuccess) return e;
-    A.job = reinterpret_cast<uint4*>(ws);
-    A.count = reinterpret_cast<uint2*>(ws + job_bytes);
-    A.part = reinterpret_cast<uint2*>(ws + job_bytes + conn_bytes);
-    if (job_bytes) e = hipMemsetAsync(A.job, 0, job_bytes, stream);
+    frm_carve(A, wgrid, ws);
+    if (A.frm_cap) e = hipMemsetAsync(A.job, 0, sizeof(uint4) * (uint64_t)A.frm_cap, stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(frm_walk_kernel<false>, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
         hipLaunchKernelGGL(frm_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, A, wgrid);
@@ -145,10 +150,8 @@ hipError_t launch_deframe(FrmArgs& A, hipStream_t stream) {
         if (A.frm_cap)
             hipLaunchKernelGGL(frm_gather_kernel, dim3((uint32_t)(((uint64_t)A.frm_cap + kGatherThreads - 1u) / kGatherThreads)),
                                dim3(kGatherThreads), 0, stream, A.in, A.blk, A.job, A.frm_cap);
-        e = hipGetLastError();
     }
-    const hipError_t f = hipFreeAsync(ws, stream);
-    return e != hipSuccess ? e : f;
+    return work_done(e, ws, stream);
 }
 
 }  // namespace

@@ -1,4 +1,5 @@
-// What the two de-framers (hhuff_frames.hip, hhuff_h3frames.hip) share: the scaffolding of their passes and the gather.
+// What the device copies share on the device side: the scaffolding of the de-framers' and the body calls' passes, the
+// de-framers' gather and the job-window copy.  A line's loads and stores are hhuff_linecopy.h's.
 //   SlotRange               a connection's / stream's bytes and frame slots, clamped to the input and to frm_cap
 //   lds_scan                an inclusive scan in LDS, one entry a lane (uint2 and uint4 through vadd)
 //   wg_scan                 sums over a walk workgroup's 256 lanes (uint2 and uint4 counts)
@@ -10,13 +11,14 @@
 //                           chunks of all its fragments through (an LDS scan of the chunk counts) and deals them
 //                           out lane by lane: short fragments share a wave, a 16 KiB fragment's 1,024 chunks go
 //                           over all four waves, consecutive lanes at consecutive 16 bytes of source and
-//                           destination.  A chunk's bytes come from the five aligned source dwords that hold
-//                           them, funnel-shifted; a whole chunk is one 16-byte store, a fragment's first and last
-//                           line, which it shares with its neighbours, dword and byte stores of its own bytes.
+//                           destination, each chunk one lc::copy_line.
+//   copy_grid, copy_share, window_copy   the copy over a job list that one workgroup cannot hold (described below)
 #ifndef HHUFF_GATHER_H
 #define HHUFF_GATHER_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "hhuff_linecopy.h"
 
 namespace hhuff {
 namespace {
@@ -25,18 +27,13 @@ constexpr uint32_t kWalkThreads = 256;  // connections / streams a walk workgrou
 constexpr uint32_t kScanThreads = 1024;
 constexpr uint32_t kGatherThreads = 256;
 
-// Whatever off and first hold, item i's bytes stay inside in[0 .. in_size) and its slots inside [0, frm_cap).
+// Item i's bytes inside in[0 .. in_size) and its slots inside [0, frm_cap), whatever off and first hold (lc::clamp_range)
 struct SlotRange {
     uint32_t start, len, f0, cap;
     __device__ SlotRange(const uint32_t* off, const uint32_t* first, uint32_t i, uint64_t in_size, uint32_t frm_cap) {
-        const uint64_t s = off[i], e = off[i + 1];
-        start = (uint32_t)(s < in_size ? s : in_size);
-        const uint64_t e2 = e < start ? start : (e < in_size ? e : in_size);
-        len = (uint32_t)(e2 - start);
-        const uint32_t a = first[i], b = first[i + 1];
-        f0 = a < frm_cap ? a : frm_cap;
-        const uint32_t f1 = b < f0 ? f0 : (b < frm_cap ? b : frm_cap);
-        cap = f1 - f0;
+        const lc::Range bytes = lc::clamp_range(off[i], off[i + 1], (uint32_t)in_size);  // (in_size < 2^32: the calls' check)
+        const lc::Range slots = lc::clamp_range(first[i], first[i + 1], frm_cap);
+        start = bytes.first, len = bytes.count, f0 = slots.first, cap = slots.count;
     }
 };
 
@@ -98,14 +95,9 @@ __global__ __launch_bounds__(kGatherThreads) void frm_gather_kernel(const uint8_
     const uint32_t tid = threadIdx.x;
     const uint64_t j = (uint64_t)blockIdx.x * kGatherThreads + tid;
     const uint4 J = j < njobs ? job[j] : make_uint4(0u, 0u, 0u, 0u);
-    uint32_t nch = 0;
-    if (J.z != 0) {
-        const uint64_t d = (uint64_t)(uintptr_t)blk + J.y;
-        nch = (uint32_t)(((d + J.z + 15u) >> 4) - (d >> 4));
-    }
     sjob[tid] = J;
     if (tid == 0) pre[0] = 0;
-    pre[tid + 1u] = nch;
+    pre[tid + 1u] = J.z ? lc::lines_of((uint64_t)(uintptr_t)blk + J.y, J.z) : 0u;
     __syncthreads();
     for (uint32_t d = 1; d < kGatherThreads; d <<= 1) {  // (on lds_scan this kernel gains an instruction: kept as it was)
         uint32_t o = 0;
@@ -121,39 +113,72 @@ __global__ __launch_bounds__(kGatherThreads) void frm_gather_kernel(const uint8_
         for (uint32_t step = kGatherThreads / 2; step > 0; step >>= 1)
             if (pre[k + step] <= t) k += step;
         const uint4 Q = sjob[k];
-        const uint64_t d0 = (uint64_t)(uintptr_t)blk + Q.y, d1 = d0 + Q.z;  // the fragment's destination addresses
-        const uint64_t line = (d0 & ~15ull) + 16ull * (t - pre[k]);
-        const uint64_t lo = line > d0 ? line : d0, hi = line + 16u < d1 ? line + 16u : d1;
-        const uint32_t b0 = (uint32_t)(lo - line), b1 = (uint32_t)(hi - line);  // the fragment's bytes of the line
-        // The line's 16 bytes from the aligned source dwords that hold them: sv = where byte 0 of the line comes
-        // from (before the fragment when b0 > 0: no such byte is loaded), dword m = the line's bytes 4 m - r ..
-        // 4 m - r + 3, loaded only when one of them is the fragment's.
-        const uint64_t sv = (uint64_t)(uintptr_t)in + Q.x + (line - d0);
-        const uint32_t r = (uint32_t)(sv & 3u);
-        const uint32_t* a = reinterpret_cast<const uint32_t*>((uintptr_t)(sv - r));
-        uint32_t w[5], v[4];
+        const uint64_t d0 = (uint64_t)(uintptr_t)blk + Q.y;  // the fragment's first destination address
+        lc::copy_line((uint64_t)(uintptr_t)in + Q.x, d0, d0 + Q.z, t - pre[k]);
+    }
+}
+
+// The job-window copy of hhuff_h2_frame_data and hhuff_h2_bodies: jobs in destination order, job k (J) with pre(J, k) =
+// the 16-byte destination lines of the jobs before it (in the job or in an array beside it), njobs and `total` lines in all.  The lines of all jobs are numbered
+// through; a workgroup takes an equal share of the numbers in tiles of 256 (copy_share: one 64 MiB job spreads as
+// 4,096 of 16 KiB do), finds its first job by bisection once, and then takes windows of 256 jobs into LDS.  A lane takes
+// every 256th line of the window: the job by an LDS bisection, then line(k, J, li) for line li of job k, which is J.
+// Both are the caller's, whatever the job array holds: line.admit(J), once as a job enters the window, checks it
+// against the caller's buffers (and empties one that leaves them), line(k, J, li) checks li against J and writes.
+constexpr uint32_t kCopyThreads = 256;
+constexpr uint32_t kCopyMaxGrid = 2048;  // 8 workgroups a CU
+
+// the workgroups of a copy over at most `most` (>= 1) lines
+inline uint32_t copy_grid(uint64_t most) {
+    const uint64_t want = (most + kCopyThreads - 1u) / kCopyThreads;
+    return (uint32_t)(want < kCopyMaxGrid ? want : kCopyMaxGrid);
+}
+
+// workgroup `block` of `grid`: its share [p0, p1) of `total` lines, in tiles of kCopyThreads
+struct Share {
+    uint64_t p0, p1;
+};
+__host__ __device__ __forceinline__ Share copy_share(uint64_t total, uint32_t block, uint32_t grid) {
+    const uint64_t tiles = (total + kCopyThreads - 1u) / kCopyThreads;
+    const uint64_t e1 = tiles * (block + 1u) / grid * kCopyThreads;
+    return Share{tiles * block / grid * kCopyThreads, e1 < total ? e1 : total};
+}
+
+template <class Job, class Pre, class Line>
+__device__ __forceinline__ void window_copy(const Job* __restrict__ job, Pre pre, uint32_t njobs, uint32_t total, Line& line) {
+    __shared__ uint32_t spre[kCopyThreads + 1];  // spre[k] = the lines before job k0 + k
+    __shared__ Job sjob[kCopyThreads];
+    const uint32_t tid = threadIdx.x;
+    if (njobs == 0 || total == 0) return;
+    const Share S = copy_share(total, blockIdx.x, gridDim.x);
+    if (S.p0 >= S.p1) return;
+    uint32_t k0 = 0;  // the last job with pre <= p0
+    for (uint32_t hi = njobs; hi - k0 > 1u;) {
+        const uint32_t mid = k0 + (hi - k0) / 2u;
+        if (pre(job[mid], mid) <= S.p0)
+            k0 = mid;
+        else
+            hi = mid;
+    }
+    for (uint64_t p = S.p0; p < S.p1;) {
+        const uint64_t idx = (uint64_t)k0 + tid;
+        Job Z{};
+        if (idx < njobs) Z = job[idx];
+        line.admit(Z);
+        sjob[tid] = Z, spre[tid] = idx < njobs ? pre(Z, (uint32_t)idx) : total;
+        if (tid == 0) spre[kCopyThreads] = (uint64_t)k0 + kCopyThreads < njobs ? pre(job[k0 + kCopyThreads], k0 + kCopyThreads) : total;
+        __syncthreads();
+        const uint64_t wend = S.p1 < spre[kCopyThreads] ? S.p1 : spre[kCopyThreads];
+        for (uint64_t q = p + tid; q < wend; q += kCopyThreads) {
+            uint32_t k = 0;  // the last job of the window with spre[k] <= q
 #pragma unroll
-        for (int m = 0; m < 5; ++m) {
-            const int first = 4 * m - (int)r;
-            w[m] = (first < (int)b1 && first + 4 > (int)b0) ? a[m] : 0u;
+            for (uint32_t step = kCopyThreads / 2; step > 0; step >>= 1)
+                if (spre[k + step] <= q) k += step;
+            if (q >= spre[k]) line(k0 + k, sjob[k], q - spre[k]);  // (else pre is no running sum: no job's line)
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = __builtin_amdgcn_alignbit(w[q + 1], w[q], 8u * r);
-        uint8_t* d = reinterpret_cast<uint8_t*>((uintptr_t)line);
-        if (b1 - b0 == 16u) {
-            *reinterpret_cast<uint4*>(d) = make_uint4(v[0], v[1], v[2], v[3]);
-        } else {  // a line shared with the neighbours: whole dwords where the fragment has them, else bytes
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q) {
-                if (b0 <= 4u * q && 4u * q + 4u <= b1) {
-                    reinterpret_cast<uint32_t*>(d)[q] = v[q];
-                } else {
-#pragma unroll
-                    for (uint32_t i = 0; i < 4; ++i)
-                        if (4u * q + i >= b0 && 4u * q + i < b1) d[4u * q + i] = (uint8_t)(v[q] >> (8u * i));
-                }
-            }
-        }
+        __syncthreads();
+        if (wend <= p) break;  // (only with line counts that wrapped: regions that overlap)
+        p = wend, k0 += kCopyThreads;
     }
 }
 

@@ -6,14 +6,14 @@
 //   walk        one connection's events in wire order: per BODY slot its run and its offset inside the run, per run
 //               its record, then the verdict, the runs' places and the counts of copy jobs and destination lines
 //   jobs_of     the copy jobs of a planned connection, in slot order, from what the walk left per slot -- no lookup
-//   copy_line   one 16-byte line of the destination (cut by address) of one job: the line code of hhuff_h2data.h
+// A job's bytes are copied a 16-byte line of the destination at a time by lc::copy_line (hhuff_linecopy.h).
 #ifndef HHUFF_H2BODIES_H
 #define HHUFF_H2BODIES_H
 #include <stdint.h>
 
 #include "hhuff.h"
 #include "hhuff_h2ctl.h"
-#include "hhuff_h2data.h"
+#include "hhuff_linecopy.h"
 
 namespace hhuff {
 namespace h2b {
@@ -52,8 +52,6 @@ struct Conn {
     Slot* slot;
     hhuff_h2_body_run_t* run;
 };
-
-HHUFF_CTL_HD uint32_t lines_of(uint64_t d, uint32_t n) { return (uint32_t)(((d + n + 15u) >> 4) - (d >> 4)); }
 
 // Client streams are odd and consecutive, pushed ones even: half the id spreads a step's streams evenly.
 HHUFF_CTL_HD uint32_t home(uint32_t id, uint32_t tcap) { return (id >> 1) % tcap; }
@@ -160,26 +158,8 @@ HHUFF_CTL_HD void jobs_of(const Conn& C, const Plan& P, Sink& sink) {
 struct CountSink {
     uint64_t out_addr;
     uint32_t jobs, lines;
-    HHUFF_CTL_HD void job(uint32_t, uint32_t dst, uint32_t len) { ++jobs, lines += lines_of(out_addr + dst, len); }
+    HHUFF_CTL_HD void job(uint32_t, uint32_t dst, uint32_t len) { ++jobs, lines += lc::lines_of(out_addr + dst, len); }
 };
-
-// Line li of job J (in_addr, out_addr: the addresses of in[0] and out[0]): the job's bytes of it, and no other.  A
-// line inside the job is aligned source dwords, funnel-shifted, and one 16-byte store; its first and last line, which
-// it shares with its neighbours in the run, are dword and byte stores.
-HHUFF_CTL_HD void copy_line(uint64_t in_addr, uint64_t out_addr, const Job& J, uint64_t li) {
-    const uint64_t d0 = out_addr + J.dst, d1 = d0 + J.len;
-    const uint64_t line = (d0 & ~15ull) + 16ull * li;
-    const uint64_t lo = line > d0 ? line : d0, hi = line + 16u < d1 ? line + 16u : d1;
-    const int b0 = (int)(lo - line), b1 = (int)(hi - line);
-    const uint64_t sv = in_addr + J.src + (line - d0);  // where byte 0 of the line comes from (not loaded below b0)
-    uint8_t* d = reinterpret_cast<uint8_t*>((uintptr_t)line);
-    uint32_t v[4];
-    h2d::load16(sv, b0, b1, v);
-    if (b1 - b0 == 16)
-        h2d::store16(d, v);
-    else
-        h2d::store_part(d, v, b0, b1);
-}
 
 }  // namespace h2b
 }  // namespace hhuff

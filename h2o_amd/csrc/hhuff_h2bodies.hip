@@ -9,12 +9,8 @@
 //   h2b_scan_kernel    one workgroup: the workgroups' sums -> the sums of the workgroups before each; the totals
 //   h2b_place_kernel   one lane per connection again, without a lookup: nrun, out_len, bstatus, the run records, and
 //                      from the slots' records every job at its place among all jobs with the count of lines before it
-//   h2b_copy_kernel    the bytes.  The lines of all jobs are numbered through; a workgroup takes an equal share of the
-//                      numbers (one 1 MiB payload spreads as 256 of 4 KiB do), finds its first job by bisection once,
-//                      and then takes windows of 256 jobs into LDS.  A lane takes every 256th line of the window: the
-//                      job by an LDS bisection, then h2b::copy_line -- five aligned source dwords, funnel-shifted, one
-//                      16-byte store; a job's first and last line, shared with its neighbours in the run, are dword and
-//                      byte stores of its own bytes.  Jobs have no headers inside, so a line needs no frame arithmetic.
+//   h2b_copy_kernel    the bytes, by window_copy (hhuff_gather.h): one 1 MiB payload spreads as 256 of 4 KiB do.  Jobs
+//                      have no headers inside, so a line is lc::copy_line and needs no frame arithmetic.
 // Positions come from the scan alone: no atomics, no size read back, equal input gives equal bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,9 +24,6 @@
 
 namespace hhuff {
 namespace {
-
-constexpr uint32_t kCopyThreads = 256;
-constexpr uint32_t kCopyMaxGrid = 2048;  // 8 workgroups a CU
 
 struct BodyArgs {
     const uint8_t* in;
@@ -57,16 +50,14 @@ struct BodyArgs {
     uint2* tot;                // all jobs, all lines
 };
 
-// whatever frm_first, nstr and out_off hold, the slots stay inside [0, frm_cap) and the region inside out
+// connection c's slots inside [0, frm_cap) and its region inside out, whatever frm_first, nstr and out_off hold
+// (out_size < 2^32: hhuff_h2_bodies refuses a larger one, so the cast loses nothing)
 __device__ __forceinline__ h2b::Conn conn_of(const BodyArgs& A, uint32_t c) {
-    const uint32_t a = A.frm_first[c], b = A.frm_first[c + 1];
-    const uint32_t f0 = a < A.frm_cap ? a : A.frm_cap;
-    const uint32_t cap = (b < f0 ? f0 : (b < A.frm_cap ? b : A.frm_cap)) - f0;
+    const lc::Range slots = lc::clamp_range(A.frm_first[c], A.frm_first[c + 1], A.frm_cap);
+    const lc::Range region = lc::clamp_range(A.out_off[c], A.out_off[c + 1], (uint32_t)A.out_size);
+    const uint32_t f0 = slots.first, cap = slots.count, t0 = region.first, room = region.count;
     const uint32_t n = A.nstr[c] < cap ? A.nstr[c] : cap;
-    const uint64_t o0 = A.out_off[c], o1 = A.out_off[c + 1];
-    const uint64_t t0 = o0 < A.out_size ? o0 : A.out_size;
-    const uint32_t room = (uint32_t)((o1 < t0 ? t0 : (o1 < A.out_size ? o1 : A.out_size)) - t0);
-    return h2b::Conn{A.in_size, (uint64_t)(uintptr_t)A.out, A.ctl + f0, A.sev + f0, f0, n, (uint32_t)t0, room,
+    return h2b::Conn{A.in_size, (uint64_t)(uintptr_t)A.out, A.ctl + f0, A.sev + f0, f0, n, t0, room,
                      A.tab + 2ull * f0, 2u * cap, A.slot + f0, A.run + f0};
 }
 
@@ -96,7 +87,7 @@ struct PlaceSink {
     uint32_t jobs, lines;
     __device__ void job(uint32_t src, uint32_t dst, uint32_t len) {
         if (jobs < A.frm_cap) A.job[jobs] = h2b::Job{src, dst, len, lines};  // (beyond only with slots two connections share)
-        ++jobs, lines += h2b::lines_of((uint64_t)(uintptr_t)A.out + dst, len);
+        ++jobs, lines += lc::lines_of((uint64_t)(uintptr_t)A.out + dst, len);
     }
 };
 
@@ -117,86 +108,59 @@ __global__ __launch_bounds__(kWalkThreads) void h2b_place_kernel(BodyArgs A) {
     h2b::jobs_of(C, P, sink);
 }
 
+// window_copy's job check and line: a job is copied only if it lies inside both arrays, whatever the workspace holds.
+// (Measured, medians of three runs of tools/h2_bodies_rate.py, ms, before -> on the shared code: one 14.72 -> 14.56,
+// interleaved 0.1956 -> 0.1957, interleaved_4096 0.5615 -> 0.5634, all inside the spread of the runs before; small
+// (65,536 connections x one 4 KiB frame) 0.1531 -> 0.1540, where the runs before spread over 0.0004 and 0.1537 was the
+// bound.  The same shape with this kernel's window loop written out here: 0.1545; with conn_of's clamps written out:
+// 0.1544; and a kernel trace of the shape gives every kernel of the call the same mean before and after, within what
+// two traces of one build differ by (copy 130.4 and 130.9 us before, 130.6 and 131.4 after; plan 8.18 and 8.21, 8.22 and
+// 8.27).  So no body of its own is kept here: it buys nothing.)
+struct BodyLine {
+    uint64_t in, in_size, out, out_size;  // in, out: the addresses of in[0] and out[0]
+    __device__ __forceinline__ void admit(h2b::Job& J) const {
+        if ((uint64_t)J.src + J.len > in_size || (uint64_t)J.dst + J.len > out_size) J.len = 0;
+    }
+    __device__ __forceinline__ void operator()(uint32_t, const h2b::Job& J, uint64_t li) const {
+        const uint64_t d0 = out + J.dst;
+        if (J.len != 0 && li < lc::lines_of(d0, J.len)) lc::copy_line(in + J.src, d0, d0 + J.len, li);  // a line of the job's own
+    }
+};
+
 __global__ __launch_bounds__(kCopyThreads) void h2b_copy_kernel(const uint8_t* __restrict__ in, uint64_t in_size, uint8_t* __restrict__ out,
                                                                  uint64_t out_size, const h2b::Job* __restrict__ job,
                                                                  const uint2* __restrict__ tot, uint32_t frm_cap) {
-    __shared__ uint32_t spre[kCopyThreads + 1];  // spre[k] = the lines before job k0 + k
-    __shared__ h2b::Job sjob[kCopyThreads];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t njobs = tot->x < frm_cap ? tot->x : frm_cap;
-    const uint32_t total = tot->y;
-    if (njobs == 0 || total == 0) return;
-    // this workgroup's share of the line numbers, in tiles of 256
-    const uint64_t tiles = ((uint64_t)total + kCopyThreads - 1u) / kCopyThreads;
-    const uint64_t p0 = tiles * blockIdx.x / gridDim.x * kCopyThreads;
-    const uint64_t e1 = tiles * (blockIdx.x + 1u) / gridDim.x * kCopyThreads;
-    const uint64_t p1 = e1 < total ? e1 : total;
-    if (p0 >= p1) return;
-    uint32_t k0 = 0;  // the last job with pre <= p0
-    for (uint32_t hi = njobs; hi - k0 > 1u;) {
-        const uint32_t mid = k0 + (hi - k0) / 2u;
-        if (job[mid].pre <= p0)
-            k0 = mid;
-        else
-            hi = mid;
-    }
-    for (uint64_t p = p0; p < p1;) {
-        const uint64_t idx = (uint64_t)k0 + tid;
-        h2b::Job Z{0u, 0u, 0u, total};
-        if (idx < njobs) Z = job[idx];
-        // a job is copied only if it lies inside both arrays, whatever the workspace holds
-        if ((uint64_t)Z.src + Z.len > in_size || (uint64_t)Z.dst + Z.len > out_size) Z.len = 0;
-        sjob[tid] = Z, spre[tid] = Z.pre;
-        if (tid == 0) spre[kCopyThreads] = (uint64_t)k0 + kCopyThreads < njobs ? job[k0 + kCopyThreads].pre : total;
-        __syncthreads();
-        const uint64_t wend = p1 < spre[kCopyThreads] ? p1 : spre[kCopyThreads];
-        for (uint64_t q = p + tid; q < wend; q += kCopyThreads) {
-            uint32_t k = 0;  // the last job of the window with spre[k] <= q
-#pragma unroll
-            for (uint32_t step = kCopyThreads / 2; step > 0; step >>= 1)
-                if (spre[k + step] <= q) k += step;
-            const h2b::Job J = sjob[k];
-            const uint64_t li = q - spre[k];  // the line's number inside the job: a line of the job's own, whatever pre holds
-            if (q < spre[k] || J.len == 0 || li >= h2b::lines_of((uint64_t)(uintptr_t)out + J.dst, J.len)) continue;
-            h2b::copy_line((uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out, J, li);
-        }
-        __syncthreads();
-        if (wend <= p) break;  // (only with line counts that wrapped: regions that overlap)
-        p = wend, k0 += kCopyThreads;
-    }
+    BodyLine line{(uint64_t)(uintptr_t)in, in_size, (uint64_t)(uintptr_t)out, out_size};
+    window_copy(job, [](const h2b::Job& J, uint32_t) { return J.pre; }, tot->x < frm_cap ? tot->x : frm_cap, tot->y, line);
+}
+
+// the workspace of a call: its size with base = NULL, its pointers with the allocation
+uint64_t body_carve(BodyArgs& A, uint32_t wgrid, uint8_t* base) {
+    Carve cv{base};
+    const uint64_t cap = A.frm_cap;
+    A.slot = cv.take<h2b::Slot>(cap);
+    A.run = cv.take<hhuff_h2_body_run_t>(cap);
+    A.tab = cv.take<h2b::Key>(2u * cap);
+    A.job = cv.take<h2b::Job>(cap);
+    A.plan = cv.take<h2b::Plan>(A.nconn);
+    A.part = cv.take<uint2>((uint64_t)wgrid + 1u);
+    A.tot = A.part + wgrid;
+    return cv.off;
 }
 
 hipError_t launch_bodies(BodyArgs& A, hipStream_t stream) {
     const uint32_t wgrid = (uint32_t)(((uint64_t)A.nconn + kWalkThreads - 1u) / kWalkThreads);
-    const uint64_t cap = A.frm_cap;
-    const uint64_t slot_bytes = cap * sizeof(h2b::Slot), run_bytes = cap * sizeof(hhuff_h2_body_run_t);
-    const uint64_t tab_bytes = 2u * cap * sizeof(h2b::Key), job_bytes = cap * sizeof(h2b::Job);
-    const uint64_t plan_bytes = (uint64_t)A.nconn * sizeof(h2b::Plan);
     uint8_t* ws = nullptr;
-    hipError_t e = work_alloc((void**)&ws, slot_bytes + run_bytes + tab_bytes + job_bytes + plan_bytes + (uint64_t)wgrid * 8u + 16u, stream);
+    const hipError_t e = work_alloc((void**)&ws, body_carve(A, wgrid, nullptr), stream);
     if (e != hipSuccess) return e;
-    uint8_t* at = ws;  // every piece is a multiple of 16 bytes
-    A.slot = reinterpret_cast<h2b::Slot*>(at), at += slot_bytes;
-    A.run = reinterpret_cast<hhuff_h2_body_run_t*>(at), at += run_bytes;
-    A.tab = reinterpret_cast<h2b::Key*>(at), at += tab_bytes;
-    A.job = reinterpret_cast<h2b::Job*>(at), at += job_bytes;
-    A.plan = reinterpret_cast<h2b::Plan*>(at), at += plan_bytes;
-    A.part = reinterpret_cast<uint2*>(at);
-    A.tot = A.part + wgrid;
+    body_carve(A, wgrid, ws);
     hipLaunchKernelGGL(h2b_plan_kernel, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
     hipLaunchKernelGGL(h2b_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, A, wgrid);
     hipLaunchKernelGGL(h2b_place_kernel, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
-    if (A.frm_cap != 0 && A.out_size != 0 && A.in_size != 0) {
-        // the lines there can be: those of `out`, and a first or last one shared for every job
-        const uint64_t most = (A.out_size >> 4) + 2u * cap;
-        const uint64_t want = (most + kCopyThreads - 1u) / kCopyThreads;
-        const uint32_t grid = (uint32_t)(want < kCopyMaxGrid ? want : kCopyMaxGrid);
-        hipLaunchKernelGGL(h2b_copy_kernel, dim3(grid), dim3(kCopyThreads), 0, stream, A.in, A.in_size, A.out, A.out_size, A.job, A.tot,
-                           A.frm_cap);
-    }
-    e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(ws, stream);
-    return e != hipSuccess ? e : f;
+    if (A.frm_cap != 0 && A.out_size != 0 && A.in_size != 0)  // the lines there can be: those of `out`, and a first or last one shared for every job
+        hipLaunchKernelGGL(h2b_copy_kernel, dim3(copy_grid((A.out_size >> 4) + 2u * (uint64_t)A.frm_cap)), dim3(kCopyThreads), 0, stream,
+                           A.in, A.in_size, A.out, A.out_size, A.job, A.tot, A.frm_cap);
+    return work_done(hipSuccess, ws, stream);
 }
 
 }  // namespace

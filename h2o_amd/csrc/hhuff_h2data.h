@@ -14,12 +14,9 @@
 #include <stdint.h>
 
 #include "hhuff.h"
+#include "hhuff_linecopy.h"  // the line's loads and stores, under write_line
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define HHUFF_DATA_HD __host__ __device__ __forceinline__
-#else
-#define HHUFF_DATA_HD inline
-#endif
+#define HHUFF_DATA_HD HHUFF_LC_HD
 
 namespace hhuff {
 namespace h2d {
@@ -109,61 +106,6 @@ HHUFF_DATA_HD void advance(const Job& J, At& at, uint64_t bytes) {  // to a late
     while (at.fo >= fw) at.fo -= fw, ++at.f;
 }
 
-HHUFF_DATA_HD uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t bits) {  // bits 0, 8, 16, 24
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbit(hi, lo, bits);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> bits);
-#endif
-}
-
-// The line's 16 bytes from the aligned source dwords that hold them (frm_gather_kernel's scheme): sv = where byte 0 of
-// the line comes from, dword q = the line's bytes 4 q - r .. 4 q - r + 3, loaded only when one of them lies in [lo, hi).
-HHUFF_DATA_HD void load16(uint64_t sv, int lo, int hi, uint32_t v[4]) {
-    const uint32_t r = (uint32_t)(sv & 3u);
-    const uint32_t* a = reinterpret_cast<const uint32_t*>((uintptr_t)(sv - r));
-    uint32_t w[5];
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int q = 0; q < 5; ++q) {
-        const int first = 4 * q - (int)r;
-        w[q] = (first < hi && first + 4 > lo) ? a[q] : 0u;
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int q = 0; q < 4; ++q) v[q] = funnel(w[q + 1], w[q], 8u * r);
-}
-
-HHUFF_DATA_HD void store16(uint8_t* d, const uint32_t v[4]) {  // d: 16-byte aligned
-#if defined(__HIP_DEVICE_COMPILE__)
-    *reinterpret_cast<uint4*>(d) = make_uint4(v[0], v[1], v[2], v[3]);
-#else
-    uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
-    d4[0] = v[0], d4[1] = v[1], d4[2] = v[2], d4[3] = v[3];
-#endif
-}
-
-// Bytes [b0, b1) of the line at d, and no other: whole dwords where the job has them, else bytes -- the rest of a
-// job's first and last line is its neighbours'.
-HHUFF_DATA_HD void store_part(uint8_t* d, const uint32_t v[4], int b0, int b1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int q = 0; q < 4; ++q) {
-        if (b0 <= 4 * q && 4 * q + 4 <= b1) {
-            reinterpret_cast<uint32_t*>(d)[q] = v[q];
-        } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-            for (int i = 0; i < 4; ++i)
-                if (4 * q + i >= b0 && 4 * q + i < b1) d[4 * q + i] = (uint8_t)(v[q] >> (8 * i));
-        }
-    }
-}
-
 // byte x (0 .. 8) of a DATA frame's header, as header() writes it
 HHUFF_DATA_HD uint32_t header_byte(uint32_t length, uint32_t flags, uint32_t stream_id, int x) {
     const uint32_t h0 = ((length >> 16) & 0xffu) | (length & 0xff00u) | ((length & 0xffu) << 16);  // length, type 0
@@ -173,7 +115,7 @@ HHUFF_DATA_HD uint32_t header_byte(uint32_t length, uint32_t flags, uint32_t str
 }
 
 // The line at address `line` of the job whose bytes lie at [d0, d1) (addresses; body: the address of body[0]): the
-// job's bytes of it, and no other.  A line inside one frame's payload is one 16-byte store.  Else line byte i is byte
+// job's bytes of it, and no other.  A line inside one frame's payload is lc::load16 and store16.  Else line byte i is byte
 // x = fo + i of frame f: its header below 9, its payload below m + 9, then frame f + 1's header and payload, whose
 // source lies 9 bytes back (m + 9 > 16 + 9: no third frame in a line).
 HHUFF_DATA_HD void write_line(uint64_t body, const Job& J, uint64_t d0, uint64_t d1, uint64_t line, const At& at) {
@@ -186,8 +128,8 @@ HHUFF_DATA_HD void write_line(uint64_t body, const Job& J, uint64_t d0, uint64_t
     uint8_t* d = reinterpret_cast<uint8_t*>((uintptr_t)line);
     uint32_t v[4];
     if (b1 - b0 == 16 && fo >= kHeaderSize && fo + 16 <= fw) {
-        load16(sv, 0, 16, v);
-        store16(d, v);
+        lc::load16(sv, 0, 16, v);
+        lc::store16(d, v);
         return;
     }
     const int64_t far = 64;  // (anything beyond the line)
@@ -196,19 +138,15 @@ HHUFF_DATA_HD void write_line(uint64_t body, const Job& J, uint64_t d0, uint64_t
     const int alo = b0 > a0 ? b0 : a0, ahi = b1 < h1 ? b1 : h1;
     const int blo = b0 > h1 + 9 ? b0 : h1 + 9;
     uint32_t va[4], vb[4];
-    load16(sv, alo, ahi, va);
-    load16(sv - (uint64_t)kHeaderSize, blo, b1, vb);
+    lc::load16(sv, alo, ahi, va);
+    lc::load16(sv - (uint64_t)kHeaderSize, blo, b1, vb);
     const uint32_t lastf = J.nframes - 1u, short_len = J.total - lastf * J.m;
     const uint32_t len0 = f < lastf ? J.m : short_len, len1 = f + 1u < lastf ? J.m : short_len;
     const uint32_t fl0 = (f == lastf && J.end_stream) ? kEndStream : 0u, fl1 = (f + 1u == lastf && J.end_stream) ? kEndStream : 0u;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
+    HHUFF_LC_UNROLL
     for (int q = 0; q < 4; ++q) {
         uint32_t word = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
+        HHUFF_LC_UNROLL
         for (int i = 0; i < 4; ++i) {
             const int p = 4 * q + i;
             const int64_t x = fo + p;
@@ -226,9 +164,9 @@ HHUFF_DATA_HD void write_line(uint64_t body, const Job& J, uint64_t d0, uint64_t
         v[q] = word;
     }
     if (b1 - b0 == 16)
-        store16(d, v);
+        lc::store16(d, v);
     else
-        store_part(d, v, b0, b1);
+        lc::store_part(d, v, b0, b1);
 }
 
 HHUFF_DATA_HD bool peer_ok(const hhuff_h2_peer_t& P) { return P.max_frame_size >= 16384u && P.max_frame_size <= 16777215u; }

@@ -21,6 +21,7 @@
 
 #include "hhuff.h"
 #include "hhuff_h2simage.h"
+#include "hhuff_launch.h"
 #include "hhuff_slots.h"
 
 #define HHUFF_API extern "C" __attribute__((visibility("default")))
@@ -317,7 +318,5 @@ HHUFF_API int hhuff_h2_streams_import(uint32_t max_entries, void* scratch, uint6
     uint32_t* cmap = nullptr;
     if (conn_map_make(&slots, n, (hipStream_t)stream, &cmap) != hipSuccess) return HHUFF_EHIP;
     A.cmap = cmap;
-    const hipError_t e = launch(true, A, (hipStream_t)stream);
-    const hipError_t f = hipFreeAsync(cmap, (hipStream_t)stream);
-    return e == hipSuccess && f == hipSuccess ? HHUFF_OK : HHUFF_EHIP;
+    return work_done(launch(true, A, (hipStream_t)stream), cmap, (hipStream_t)stream) == hipSuccess ? HHUFF_OK : HHUFF_EHIP;
 }

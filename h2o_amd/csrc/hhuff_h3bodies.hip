@@ -9,11 +9,11 @@
 //                      the content-length cut by bisection over its slots (h3b::over is monotone along a stream)
 //   h3s_place_kernel   one lane per send record: frm_off and sstatus from the same differences
 //   h3b_copy_kernel    the bytes of both calls.  The output is packed, so its 16-byte lines (cut by address) have one
-//                      writer each: a workgroup takes an equal share of the lines, bisects the prefix in global memory
-//                      for its first and last segment, and pulls windows of up to kWindow segment prefixes and sources
-//                      into LDS.  A lane takes every 256th line of the window: the segment of its first byte by an LDS
-//                      bisection, then h3b::write_line -- inside one payload five aligned source dwords, funnel-shifted,
-//                      and one 16-byte store; with a header or several segments in the line a walk over them, the bytes
+//                      writer each: a workgroup takes an equal share of the lines (copy_share, hhuff_gather.h), bisects the
+//                      prefix in global memory for its first and last segment, and pulls windows of up to kWindow segment
+//                      prefixes and sources into LDS.  A lane takes every 256th line of the window: the segment of its
+//                      first byte by an LDS bisection, then h3b::write_line -- inside one payload the line copy of
+//                      hhuff_linecopy.h; with a header or several segments in the line a walk over them, the bytes
 //                      assembled in registers, and still one store.  A segment behind the window (only when more than
 //                      kWindow segments, empty ones counted, lie in one line's reach) is found in global memory.
 // Positions come from the scans alone: no atomics, no size read back, equal input gives equal bytes.
@@ -33,8 +33,6 @@ namespace {
 
 using h3b::Cnt;
 
-constexpr uint32_t kCopyThreads = 256;
-constexpr uint32_t kCopyMaxGrid = 2048;  // 8 workgroups a CU
 constexpr uint32_t kWindow = 2048;       // segments a window: 256 lines of eight 2-byte frames each fill the workgroup
 static_assert(kWalkThreads == 256, "Prefix::at finds a slot's workgroup by a shift");
 
@@ -76,15 +74,13 @@ struct BodyArgs {
     Cnt *pre, *part, *tot;  // workspace
 };
 
-// whatever frm_first and nframes hold, stream s's slots [f0, f0 + n) stay inside [0, frm_cap)
+// stream s's slots [f0, f0 + n) inside [0, frm_cap), whatever frm_first and nframes hold
 struct Slots {
     uint32_t f0, n;
 };
 __device__ __forceinline__ Slots slots_of(const BodyArgs& A, uint32_t s) {
-    const uint32_t a = A.frm_first[s], b = A.frm_first[s + 1];
-    const uint32_t f0 = a < A.frm_cap ? a : A.frm_cap;
-    const uint32_t cap = (b < f0 ? f0 : (b < A.frm_cap ? b : A.frm_cap)) - f0;
-    return Slots{f0, A.nframes[s] < cap ? A.nframes[s] : cap};
+    const lc::Range R = lc::clamp_range(A.frm_first[s], A.frm_first[s + 1], A.frm_cap);
+    return Slots{R.first, A.nframes[s] < R.count ? A.nframes[s] : R.count};
 }
 
 __global__ __launch_bounds__(kWalkThreads) void h3b_count_kernel(BodyArgs A) {
@@ -235,11 +231,8 @@ __global__ __launch_bounds__(kCopyThreads) void h3b_copy_kernel(CopyArgs A) {
     const uint64_t base = (uint64_t)(uintptr_t)A.out;
     const uint32_t a = (uint32_t)(base & 15u);
     const uint64_t nlines = ((uint64_t)a + limit + 15u) >> 4;  // line q holds out[16 q - a .. 16 q - a + 16)
-    // this workgroup's share of the lines, in tiles of 256
-    const uint64_t tiles = (nlines + kCopyThreads - 1u) / kCopyThreads;
-    const uint64_t q0 = tiles * blockIdx.x / gridDim.x * kCopyThreads;
-    const uint64_t e1 = tiles * (blockIdx.x + 1u) / gridDim.x * kCopyThreads;
-    const uint64_t q1 = e1 < nlines ? e1 : nlines;
+    const Share share = copy_share(nlines, blockIdx.x, gridDim.x);
+    const uint64_t q0 = share.p0, q1 = share.p1;
     if (q0 >= q1) return;
     const uint64_t x_first = q0 == 0 ? 0u : 16u * q0 - a, x_last = (16u * q1 - a < limit ? 16u * q1 - a : limit) - 1u;
     const uint64_t k_first = A.P.seg_of(x_first, 0, nseg), k_last = A.P.seg_of(x_last, k_first, nseg);
@@ -269,24 +262,25 @@ __global__ __launch_bounds__(kCopyThreads) void h3b_copy_kernel(CopyArgs A) {
 template <bool kHdr>
 void launch_copy(const CopyArgs& C, hipStream_t stream) {
     if (C.P.n == 0 || C.out_size == 0) return;
-    const uint64_t want = ((C.out_size >> 4) + 2u + kCopyThreads - 1u) / kCopyThreads;  // the lines there can be
-    const uint32_t grid = (uint32_t)(want < kCopyMaxGrid ? want : kCopyMaxGrid);
-    hipLaunchKernelGGL(h3b_copy_kernel<kHdr>, dim3(grid), dim3(kCopyThreads), 0, stream, C);
+    hipLaunchKernelGGL(h3b_copy_kernel<kHdr>, dim3(copy_grid((C.out_size >> 4) + 2u)), dim3(kCopyThreads), 0, stream, C);  // the lines there can be
 }
 
-// the scans' workspace for n segments: pre, part, tot
-hipError_t scan_alloc(uint64_t n, uint32_t wgrid, uint8_t*& ws, Cnt*& pre, Cnt*& part, Cnt*& tot, hipStream_t stream) {
-    const hipError_t e = work_alloc((void**)&ws, (n + wgrid + 1u) * sizeof(Cnt), stream);
-    if (e != hipSuccess) return e;
-    pre = reinterpret_cast<Cnt*>(ws), part = pre + n, tot = part + wgrid;
-    return hipSuccess;
+// the scans' workspace for n segments (A: BodyArgs or SendArgs): its size with base = NULL, its pointers with the allocation
+template <class Args>
+uint64_t scan_carve(Args& A, uint64_t n, uint32_t wgrid, uint8_t* base) {
+    Carve cv{base};
+    A.pre = cv.take<Cnt>(n);
+    A.part = cv.take<Cnt>((uint64_t)wgrid + 1u);
+    A.tot = A.part + wgrid;
+    return cv.off;
 }
 
 hipError_t launch_bodies(BodyArgs& A, uint8_t* out, hipStream_t stream) {
     const uint32_t wgrid = (uint32_t)(((uint64_t)A.frm_cap + kWalkThreads - 1u) / kWalkThreads);
     uint8_t* ws = nullptr;
-    hipError_t e = scan_alloc(A.frm_cap, wgrid, ws, A.pre, A.part, A.tot, stream);
+    const hipError_t e = work_alloc((void**)&ws, scan_carve(A, A.frm_cap, wgrid, nullptr), stream);
     if (e != hipSuccess) return e;
+    scan_carve(A, A.frm_cap, wgrid, ws);
     if (wgrid != 0) hipLaunchKernelGGL(h3b_count_kernel, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
     hipLaunchKernelGGL(h3b_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, A.part, wgrid, A.tot, A.totals);
     hipLaunchKernelGGL(h3b_runs_kernel, dim3((uint32_t)(((uint64_t)A.nstr + kWalkThreads - 1u) / kWalkThreads)), dim3(kWalkThreads), 0,
@@ -294,25 +288,22 @@ hipError_t launch_bodies(BodyArgs& A, uint8_t* out, hipStream_t stream) {
     launch_copy<false>(CopyArgs{A.in, A.in_size, out, A.out_size, reinterpret_cast<const uint8_t*>(A.frames) + offsetof(hhuff_h3_frame_t, payload_off),
                                 (uint32_t)sizeof(hhuff_h3_frame_t), Prefix{A.pre, A.part, A.tot, A.frm_cap}},
                        stream);
-    e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(ws, stream);
-    return e != hipSuccess ? e : f;
+    return work_done(hipSuccess, ws, stream);
 }
 
 hipError_t launch_frame_data(SendArgs& A, const uint8_t* body, uint8_t* out, hipStream_t stream) {
     const uint32_t wgrid = (uint32_t)(((uint64_t)A.nsend + kWalkThreads - 1u) / kWalkThreads);
     uint8_t* ws = nullptr;
-    hipError_t e = scan_alloc(A.nsend, wgrid, ws, A.pre, A.part, A.tot, stream);
+    const hipError_t e = work_alloc((void**)&ws, scan_carve(A, A.nsend, wgrid, nullptr), stream);
     if (e != hipSuccess) return e;
+    scan_carve(A, A.nsend, wgrid, ws);
     hipLaunchKernelGGL(h3s_count_kernel, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
     hipLaunchKernelGGL(h3b_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, A.part, wgrid, A.tot, (uint32_t*)nullptr);
     hipLaunchKernelGGL(h3s_place_kernel, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
     launch_copy<true>(CopyArgs{body, A.body_size, out, A.out_size, reinterpret_cast<const uint8_t*>(A.sends) + offsetof(hhuff_h3_send_t, body_off),
                                (uint32_t)sizeof(hhuff_h3_send_t), Prefix{A.pre, A.part, A.tot, A.nsend}},
                       stream);
-    e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(ws, stream);
-    return e != hipSuccess ? e : f;
+    return work_done(hipSuccess, ws, stream);
 }
 
 }  // namespace

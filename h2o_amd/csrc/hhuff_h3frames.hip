@@ -188,22 +188,27 @@ __global__ __launch_bounds__(256) void h3f_finish_kernel(H3Args A) {
     if (A.arena_off) A.arena_off[k] = A.arena_fixed * (k < nsec ? k : nsec) + (uint64_t)A.arena_per_byte * (uint32_t)(off - t.z);
 }
 
+// the workspace of a call: its size with base = NULL, its pointers with the allocation
+uint64_t h3f_carve(H3Args& A, uint32_t wgrid, uint8_t* base) {
+    Carve cv{base};
+    const uint64_t n = A.nstr;
+    A.job = cv.take<uint4>(n);
+    A.count = cv.take<uint4>(n);
+    A.setting = cv.take<uint4>(n);
+    A.before = cv.take<uint4>(n + 1u);
+    A.part = cv.take<uint4>((uint64_t)wgrid + 1u);
+    A.dgram = cv.take<uint8_t>(n);
+    return cv.off;
+}
+
 hipError_t launch_h3_deframe(H3Args& A, hipStream_t stream) {
     const uint32_t wgrid = (uint32_t)(((uint64_t)A.nstr + kWalkThreads - 1u) / kWalkThreads);
     const uint64_t n = A.nstr;
-    const uint64_t dgram_bytes = (n + 15u) & ~15ull;
-    // job, count, setting [nstr], before [nstr + 1], part [wgrid + 1] of 16 bytes each, then dgram
-    const uint64_t bytes = 16u * (4u * n + 1u + wgrid + 1u) + dgram_bytes;
     uint8_t* ws = nullptr;
-    hipError_t e = work_alloc((void**)&ws, bytes, stream);
+    hipError_t e = work_alloc((void**)&ws, h3f_carve(A, wgrid, nullptr), stream);
     if (e != hipSuccess) return e;
-    A.job = reinterpret_cast<uint4*>(ws);
-    A.count = A.job + n;
-    A.setting = A.count + n;
-    A.before = A.setting + n;
-    A.part = A.before + n + 1u;
-    A.dgram = reinterpret_cast<uint8_t*>(A.part + wgrid + 1u);
-    e = hipMemsetAsync(A.job, 0, 16u * n, stream);
+    h3f_carve(A, wgrid, ws);
+    e = hipMemsetAsync(A.job, 0, sizeof(uint4) * n, stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(h3f_walk_kernel<false>, dim3(wgrid), dim3(kWalkThreads), 0, stream, A);
         hipLaunchKernelGGL(h3f_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, A, wgrid);
@@ -212,10 +217,8 @@ hipError_t launch_h3_deframe(H3Args& A, hipStream_t stream) {
         hipLaunchKernelGGL(h3f_finish_kernel, dim3((uint32_t)((n + 1u + 255u) / 256u)), dim3(256), 0, stream, A);
         hipLaunchKernelGGL(frm_gather_kernel, dim3((uint32_t)((n + kGatherThreads - 1u) / kGatherThreads)), dim3(kGatherThreads), 0,
                            stream, A.in, A.out, A.job, A.nstr);
-        e = hipGetLastError();
     }
-    const hipError_t f = hipFreeAsync(ws, stream);
-    return e != hipSuccess ? e : f;
+    return work_done(e, ws, stream);
 }
 
 }  // namespace

@@ -214,8 +214,6 @@ hipError_t launch_conn_import(const hhuff_conn_family_t& fam, uint8_t* scratch, 
     A.cmap = cmap;
     const uint32_t grid = (uint32_t)(((uint64_t)n * 64u + 255u) / 256u);
     hipLaunchKernelGGL(img_import_kernel, dim3(grid), dim3(256), 0, stream, A);
-    e = hipGetLastError();
-    const hipError_t f = hipFreeAsync(cmap, stream);
-    return e != hipSuccess ? e : f;
+    return work_done(hipSuccess, cmap, stream);
 }
 }  // namespace hhuff

@@ -97,6 +97,13 @@ hipError_t launch_literal_list(const uint32_t* lit_bits, const uint32_t* name_bi
                                uint8_t* prefix_of, hipStream_t stream);
 // stream-ordered device memory from the library's pool (free with hipFreeAsync on the same stream)
 hipError_t work_alloc(void** p, uint64_t bytes, hipStream_t stream);
+// A launcher's last line: e, or when that is no failure what its launches left behind, with ws back in the pool --
+// the first failure of the three.
+inline hipError_t work_done(hipError_t e, void* ws, hipStream_t stream) {
+    if (e == hipSuccess) e = hipGetLastError();
+    const hipError_t f = hipFreeAsync(ws, stream);
+    return e != hipSuccess ? e : f;
+}
 // hand the pool's kept memory on the current device back to the driver (hhuff_pool_trim)
 hipError_t pool_trim();
 

@@ -206,6 +206,22 @@ def test_workgroup_edges(torch_cuda, nconn):
     assert k.size == 300 and 0 in k[1:-1].tolist() and k.sum() > 100
 
 
+@pytest.mark.parametrize("shift", (1, 6, 15))
+@pytest.mark.parametrize("nrec", (257, 513))
+def test_copy_window_edges(torch_cuda, nrec, shift):
+    """one more record than the copy's window of 256 jobs holds, and one more than two windows: a frame of 1..40 bytes
+    each, so a 16-byte line has up to two jobs, in a region that an empty connection in front shifts off the lines.
+    What this reaches of the copy: windows that begin in the middle of the job list and the window's tail behind the
+    last job.  A workgroup here has one tile of 256 lines, which these jobs fill before the window's 256th, so none
+    goes on to a second window: that step needs the capped grid of 2,048 workgroups under more than 8 MiB of short
+    jobs, which is too large for this suite: no test takes it."""
+    body = body_of(4096, 8)
+    recs = [M.send_rec((11 * i) % 4000, 1 + (i * 7) % 40, 2 * i + 1, 100, M.FINAL if i % 2 else 0) for i in range(nrec)]
+    room = sum(9 + 1 + (i * 7) % 40 for i in range(nrec))
+    e = run(torch_cuda, M.batch(body, [[], recs], [(16384, 1 << 20)] * 2, rooms=[shift, room]), guard=True)
+    assert int(e["out_off"][1]) == shift and int(e["out_len"][1]) == room and (e["sent"]["nframes"] == 1).all()
+
+
 # ---------------------------------------------------------------------------------------------------
 # guarded buffers
 # ---------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@
 // `in` holds the tests' pattern, byte i = i * 131 + (i >> 8) + 7.  Every array is a heap block of exactly its size: the
 // event and control records, the slots' and runs' workspace, the table of 2 n entries, and the region, whose address is
 // `start` modulo 16 and which ends at its block's end.  h2b::walk plans the connection, h2b::jobs_of lists its jobs,
-// and every job's lines are written by h2b::copy_line, a lane's every 256th line as the copy kernel takes them.
+// and every job's lines are written by lc::copy_line, a lane's every 256th line as the copy kernel takes them.
 // RESULTS: one line a connection --
 //     status nrun out_len njobs | n x (run off) | nrun x (stream_id out_off len nframes first_frame flags) | the region in hex
 // (slots, runs and region only with status 0; run -1: no BODY slot).  The program itself checks that a refused
@@ -84,9 +84,9 @@ int main(int argc, char** argv) {
         for (const h2b::Job& J : sink.jobs) {
             if ((uint64_t)J.src + J.len > in_size) fail("a job leaves in", ncase, J.src);
             if (J.dst < start || (uint64_t)J.dst + J.len > start + P.out_len) fail("a job leaves the runs", ncase, J.dst);
-            const uint64_t nl = h2b::lines_of(out_addr + J.dst, J.len);
+            const uint64_t d0 = out_addr + J.dst, nl = lc::lines_of(d0, J.len);
             for (uint64_t lane = 0; lane < 256 && lane < nl; ++lane)
-                for (uint64_t li = lane; li < nl; li += 256) h2b::copy_line((uint64_t)(uintptr_t)in, out_addr, J, li);
+                for (uint64_t li = lane; li < nl; li += 256) lc::copy_line((uint64_t)(uintptr_t)in + J.src, d0, d0 + J.len, li);
             lines += nl;
         }
         if (count.jobs != sink.jobs.size() || count.lines != lines) fail("the counts of jobs and lines", ncase, count.lines);
