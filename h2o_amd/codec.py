@@ -258,6 +258,12 @@ def lib():
         L.hhuff_h3_bodies.argtypes = [_vp, u64, _vp, _vp, _vp, u32, u32, _vp, _vp, ctypes.c_uint, _vp, u64, _vp, _vp, _vp]
         L.hhuff_h3_frame_data.restype = ctypes.c_int
         L.hhuff_h3_frame_data.argtypes = [_vp, u64, _vp, u32, ctypes.c_uint, _vp, u64, _vp, _vp, _vp]
+        L.hhuff_cache_digests_load.restype = ctypes.c_int
+        L.hhuff_cache_digests_load.argtypes = [_vp, u64, _vp, _vp, _vp, u32, _vp, _vp, _vp, _vp]
+        L.hhuff_cache_digests_load_fields.restype = ctypes.c_int
+        L.hhuff_cache_digests_load_fields.argtypes = [_vp, u64, _vp, _vp, _vp, _vp, u32, u32, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]
+        L.hhuff_cache_digests_lookup.restype = ctypes.c_int
+        L.hhuff_cache_digests_lookup.argtypes = [_vp, _vp, u32, _vp, u64, _vp, u32, _vp, _vp, _vp]
         _lib = L
     return _lib
 
@@ -284,7 +290,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_h3_deframe", "hhuff_h2_control", "hhuff_hpack_responses_set_peers",
             "hhuff_h2_frame_data", "hhuff_h2_streams", "hhuff_h2_streams_scratch_size", "hhuff_h2_streams_fill_sends",
             "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies", "hhuff_h3_bodies", "hhuff_h3_frame_data",
-            "hhuff_h2_streams_image_bound", "hhuff_h2_streams_export", "hhuff_h2_streams_import") + SLOTS_SYMBOLS
+            "hhuff_h2_streams_image_bound", "hhuff_h2_streams_export", "hhuff_h2_streams_import",
+            "hhuff_cache_digests_load", "hhuff_cache_digests_load_fields", "hhuff_cache_digests_lookup") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1421,6 +1428,70 @@ def h3_frame_data(body, sends, flags=0, body_size=None, nsend=None, out_size=Non
     _check(lib().hhuff_h3_frame_data(_dp(body), body_size, _dp(sends), nsend, flags, _dp(r["out"]), out_size, _dp(r["frm_off"]),
                                      _dp(r["sstatus"]), _stream(stream)), "hhuff_h3_frame_data")
     return r
+
+
+# include/hhuff.h (2m): cache digests
+CD_UNKNOWN, CD_NOT_CACHED, CD_FRESH = 0, 1, 2
+CD_SPACE, CD_EINVAL, CD_EFORMAT = -327, -328, -329
+CDQ_ETAG = 1
+CD_QUERY_DTYPE = np.dtype([("req", "<u4"), ("flags", "<u4"), ("off", "<u4", (5,)), ("len", "<u4", (5,))])  # hhuff_cd_query_t
+
+
+def cache_digests_bound(value_bytes, nvalues):
+    """include/hhuff.h hhuff_cache_digests_bound (numpy arrays or ints)"""
+    return 16 + 16 * np.asarray(nvalues, np.int64) + 52 * np.asarray(value_bytes, np.int64)
+
+
+def _cd_out(dig, dig_off, n, status):
+    import torch
+
+    if dig is None:
+        dig = torch.empty(max(16, int(dig_off[-1].item())), dtype=torch.uint8, device=dig_off.device)
+    if status is None:
+        status = torch.empty(max(1, n), dtype=torch.int32, device=dig_off.device)
+    return dig, status
+
+
+def cache_digests_load(data, val_off, val_len, first, dig_off, dig=None, status=None, in_size=None, stream=None):
+    """hhuff_cache_digests_load on device tensors: request r's `cache-digest` values are the strings first[r] ..
+    first[r + 1] of (val_off, val_len) (int32, u32 bits) in `data`; dig_off int64 [nreq + 1] (multiples of 16).
+    -> (dig, status): the images (uint8) and the int32 status of every request."""
+    nreq = first.numel() - 1
+    dig, status = _cd_out(dig, dig_off, nreq, status)
+    _check(lib().hhuff_cache_digests_load(_dp(data), data.numel() if in_size is None else in_size, _dp(val_off), _dp(val_len),
+                                          _dp(first), nreq, _dp(dig), _dp(dig_off), _dp(status), _stream(stream)),
+           "hhuff_cache_digests_load")
+    return dig, status
+
+
+def cache_digests_load_fields(arena, value_off, value_len, first, nfields, nslots, token, cache_digest_token, dig_off, dig=None,
+                              status=None, arena_size=None, stream=None):
+    """hhuff_cache_digests_load_fields behind a block decoder and TokenSet.intern_fields: block b's values are its
+    slots whose `token` equals cache_digest_token.  -> (dig, status)."""
+    nblk = nfields.numel()
+    dig, status = _cd_out(dig, dig_off, nblk, status)
+    _check(lib().hhuff_cache_digests_load_fields(_dp(arena), arena.numel() if arena_size is None else arena_size, _dp(value_off),
+                                                 _dp(value_len), _dp(first), _dp(nfields), nblk, nslots, _dp(token),
+                                                 int(cache_digest_token), _dp(dig), _dp(dig_off), _dp(status), _stream(stream)),
+           "hhuff_cache_digests_load_fields")
+    return dig, status
+
+
+def cache_digests_lookup(dig, dig_off, data, queries, nq=None, state=None, hash_out=None, want_hash=False, in_size=None,
+                         stream=None):
+    """hhuff_cache_digests_lookup: queries = uint8 tensor of CD_QUERY_DTYPE records (48 B each) over `data`.
+    -> (state int32 [nq], hash int64 [nq] (u64 bits) or None)."""
+    import torch
+
+    nq = queries.numel() // CD_QUERY_DTYPE.itemsize if nq is None else nq
+    if state is None:
+        state = torch.empty(max(1, nq), dtype=torch.int32, device=data.device)
+    if hash_out is None and want_hash:
+        hash_out = torch.empty(max(1, nq), dtype=torch.int64, device=data.device)
+    _check(lib().hhuff_cache_digests_lookup(_dp(dig), _dp(dig_off), dig_off.numel() - 1, _dp(data),
+                                            data.numel() if in_size is None else in_size, _dp(queries), nq, _dp(state),
+                                            _dp(hash_out), _stream(stream)), "hhuff_cache_digests_lookup")
+    return state, hash_out
 
 
 def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_off=0, server_len=0, in_size=None,

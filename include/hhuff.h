@@ -2003,6 +2003,78 @@ int hhuff_h3_frame_data(const uint8_t *body, uint64_t body_size /* < 2^32 */, co
                         unsigned flags, uint8_t *out, uint64_t out_size /* < 2^32 */,
                         uint32_t *frm_off /* [nsend + 1] */, int32_t *sstatus /* [nsend] */, void *stream);
 
+/* (2m) Cache digests: the decision whether to push (lib/http2/cache_digests.c).  h2o_hpack_parse_request hands every
+ *      `cache-digest` field to h2o_cache_digests_load_header (lib/http2/hpack.c:608-610), push_path skips a push that
+ *      h2o_cache_digests_lookup_by_url calls FRESH (lib/http2/connection.c:1898-1903) and send_headers cancels a pushed
+ *      stream the same way with the ETag (lib/http2/stream.c:217-227).  Here a request's digests are an image in the
+ *      caller's memory and both steps are device calls, so parse -> intern -> load -> lookup -> flatten needs no host code.
+ *   1. The image (what h2o_cache_digests_t is to h2o) of request r lies in dig[dig_off[r] .. dig_off[r + 1]), 16-byte
+ *      aligned (dig and every dig_off), and holds no address:
+ *        header, 16 B: "HHCD", u16 version (1), u8 flags (1 = present: *digests != NULL, 2 = fresh.complete), u8 0,
+ *                      u32 nframes, u32 bytes (the image's length)
+ *        frames in load order, each 16 B {u8 capacity_bits, u8 kind (0 url_only, 1 url_and_etag), u16 0, u32 nkeys,
+ *                      8 B 0} and then nkeys ascending uint64_t keys
+ *      It is append only: a digest that h2o drops halfway (a key >= 2^capacity_bits) is never committed, `reset` moves
+ *      the write position back to the header.  The region must hold the image at every commit of the load.
+ *      hhuff_cache_digests_bound(value_bytes, nvalues) always fits: a stored digest of c characters is
+ *      floor(3 c / 4) bytes, at most 6 c bits, of which 10 are nbits and pbits and every key takes one at least, so
+ *      its frame is at most 16 + 8 (6 c - 10) < 48 c bytes; a digest needs 3 characters (two bytes hold the 10 bits)
+ *      and every one but a value's first a separator in front, so there are at most nvalues + value_bytes / 4 frames
+ *      and their 16 B apiece beyond the keys come to 16 nvalues + 4 value_bytes.  It is large on purpose: give a
+ *      realistic region and handle HHUFF_CD_SPACE.
+ *   2. hhuff_cache_digests_load: request r's field values are the strings first[r] .. first[r + 1] (in[val_off[s] ..
+ *      + val_len[s])), in field order, each handled as h2o_cache_digests_load_header handles it on the one image: the
+ *      element / attribute walk of h2o_next_token(';', ',') with its zero-width and "," tokens, blank trimming and
+ *      "=value" form; `reset`, `validators`, `complete` without case; any other attribute skips the digest but not
+ *      its reset; h2o_decode_base64url ('+' and '/' too, tails of 2 and 3; a tail of 1 or a foreign byte drops that
+ *      digest only); 5 + 5 bits of nbits and pbits; values until the bits run dry (a value cut short is no key);
+ *      `complete` is applied by a digest that was stored.  Key sums saturate at 2^63 where h2o's wrap modulo 2^64:
+ *      the two differ only for a unary run of 2^33 bits.  status[r]: 0, HHUFF_CD_SPACE (the region is too small: a
+ *      header-only absent image is written where 16 bytes fit) or HHUFF_CD_EINVAL (a string passes in_size, or
+ *      dig_off[r] is misaligned or above dig_off[r + 1]: header-only likewise).  No byte outside the region is written.
+ *   3. hhuff_cache_digests_load_fields: the same behind the block decoders.  arena .. nslots as hhuff_intern_fields
+ *      takes them, `token` the column it wrote: block b's values are its slots first[b] .. + nfields[b] (below nslots)
+ *      whose token equals cache_digest_token, in slot order.
+ *   4. hhuff_cache_digests_lookup: query q hashes the concatenation of its non-empty segments in[off[k] .. + len[k])
+ *      (h2o's callers: scheme, "://", authority, path and, with HHUFF_CDQ_ETAG, the ETag; "://" lies in `in`, as the
+ *      encoders' server name does), hash = the first 8 bytes of SHA-256, big endian, and looks key = hash >>
+ *      (64 - capacity_bits) up in every frame of the query's kind of image `req`.  capacity_bits == 0: h2o shifts by
+ *      64, which C leaves undefined; the key is the unshifted hash here, what the x86-64 build computes.  state[q]:
+ *      HHUFF_CD_UNKNOWN / _NOT_CACHED / _FRESH exactly as lookup() returns them (an absent image: UNKNOWN -- h2o's
+ *      callers do not look then, and a push proceeds either way); HHUFF_CD_EINVAL for req >= nreq, flags beyond
+ *      HHUFF_CDQ_ETAG or a segment that passes in_size; HHUFF_CD_EFORMAT for an image that is not one the load writes
+ *      (magic, version, flags, `bytes` over the region, a frame whose keys pass `bytes`): the image is untrusted
+ *      bytes and no load leaves its region.  hash_out (may be NULL) receives the hash of every query but the EINVAL ones.
+ *   5. Device arrays, asynchronous on `stream`; HHUFF_EINVAL and nothing enqueued for a NULL required array or a
+ *      misaligned dig; an empty batch returns HHUFF_OK and enqueues nothing; hhuff_last_error_string() stays as it was. */
+#define HHUFF_CD_UNKNOWN 0
+#define HHUFF_CD_NOT_CACHED 1
+#define HHUFF_CD_FRESH 2
+#define HHUFF_CD_SPACE (-327)
+#define HHUFF_CD_EINVAL (-328)
+#define HHUFF_CD_EFORMAT (-329)
+#define HHUFF_CDQ_ETAG 1u /* look in the url_and_etag frames (h2o_cache_digests_lookup_by_url_and_etag) */
+typedef struct hhuff_cd_query { uint32_t req, flags, off[5], len[5]; } hhuff_cd_query_t;   /* 48 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_cd_query_t) == 48, "record size");
+#else
+typedef char hhuff_cd_query_record_size[sizeof(hhuff_cd_query_t) == 48 ? 1 : -1];
+#endif
+static inline uint64_t hhuff_cache_digests_bound(uint64_t value_bytes, uint64_t nvalues) {
+    return 16 + 16 * nvalues + 52 * value_bytes;
+}
+int hhuff_cache_digests_load(const uint8_t *in, uint64_t in_size, const uint32_t *val_off, const uint32_t *val_len,
+                             const uint32_t *first /* [nreq + 1] */, uint32_t nreq, uint8_t *dig,
+                             const uint64_t *dig_off /* [nreq + 1] */, int32_t *status /* [nreq] */, void *stream);
+int hhuff_cache_digests_load_fields(const uint8_t *arena, uint64_t arena_size, const uint32_t *value_off,
+                                    const uint32_t *value_len, const uint32_t *first /* [nblk + 1] */,
+                                    const uint32_t *nfields, uint32_t nblk, uint32_t nslots, const int32_t *token,
+                                    int32_t cache_digest_token, uint8_t *dig, const uint64_t *dig_off /* [nblk + 1] */,
+                                    int32_t *status /* [nblk] */, void *stream);
+int hhuff_cache_digests_lookup(const uint8_t *dig, const uint64_t *dig_off /* [nreq + 1] */, uint32_t nreq,
+                               const uint8_t *in, uint64_t in_size, const hhuff_cd_query_t *queries, uint32_t nq,
+                               int32_t *state /* [nq] */, uint64_t *hash_out /* [nq], may be NULL */, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
