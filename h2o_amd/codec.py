@@ -264,6 +264,8 @@ def lib():
         L.hhuff_cache_digests_load_fields.argtypes = [_vp, u64, _vp, _vp, _vp, _vp, u32, u32, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]
         L.hhuff_cache_digests_lookup.restype = ctypes.c_int
         L.hhuff_cache_digests_lookup.argtypes = [_vp, _vp, u32, _vp, u64, _vp, u32, _vp, _vp, _vp]
+        L.hhuff_casper_step.restype = ctypes.c_int
+        L.hhuff_casper_step.argtypes = [_vp, u32, u32, _vp, _vp, _vp, u32, _vp, u64, _vp, _vp, _vp, u32, ctypes.c_int32, _vp, _vp, _vp, _vp]
         _lib = L
     return _lib
 
@@ -291,7 +293,8 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_h2_frame_data", "hhuff_h2_streams", "hhuff_h2_streams_scratch_size", "hhuff_h2_streams_fill_sends",
             "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies", "hhuff_h3_bodies", "hhuff_h3_frame_data",
             "hhuff_h2_streams_image_bound", "hhuff_h2_streams_export", "hhuff_h2_streams_import",
-            "hhuff_cache_digests_load", "hhuff_cache_digests_load_fields", "hhuff_cache_digests_lookup") + SLOTS_SYMBOLS
+            "hhuff_cache_digests_load", "hhuff_cache_digests_load_fields", "hhuff_cache_digests_lookup",
+            "hhuff_casper_step") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1492,6 +1495,38 @@ def cache_digests_lookup(dig, dig_off, data, queries, nq=None, state=None, hash_
                                             data.numel() if in_size is None else in_size, _dp(queries), nq, _dp(state),
                                             _dp(hash_out), _stream(stream)), "hhuff_cache_digests_lookup")
     return state, hash_out
+
+
+# include/hhuff.h (2n): CASPER
+CSP_INIT, CSP_CONSUME, CSP_CONSUME_FIELDS, CSP_LOOKUP, CSP_MARK, CSP_COOKIE = 1, 2, 3, 4, 5, 6
+CSP_SPACE, CSP_EINVAL, CSP_EFORMAT = -330, -331, -332
+CSP_MAX_KEYS = 2048
+CSP_OP_DTYPE = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4"), ("reserved", "<u4")])  # hhuff_casper_op_t
+CSP_RESULT_DTYPE = np.dtype([("status", "<i4"), ("value", "<u4"), ("nkeys", "<u4"), ("at", "<u4")])  # hhuff_casper_result_t
+
+
+def casper_scratch_bytes(nslots, max_keys):
+    """include/hhuff.h hhuff_casper_scratch_bytes"""
+    return nslots * ((16 + 8 * max_keys + 15) & ~15)
+
+
+def casper_step(scratch, nslots, max_keys, ops, op_first, data, out, out_off, slot=None, fields=None, cookie_token=0, res=None,
+                in_size=None, stream=None):
+    """hhuff_casper_step on device tensors: scratch uint8 (casper_scratch_bytes), ops = uint8 tensor of CSP_OP_DTYPE
+    records, op_first / out_off int32 [nconn + 1] (u32 bits), slot int32 [nconn] or None, fields = (value_off, value_len,
+    token, nfslots) behind TokenSet.intern_fields for CSP_CONSUME_FIELDS.  -> res: uint8 tensor of CSP_RESULT_DTYPE
+    records, one an op."""
+    import torch
+
+    nconn = op_first.numel() - 1
+    if res is None:
+        res = torch.empty(max(16, ops.numel()), dtype=torch.uint8, device=ops.device)
+    value_off, value_len, token, nfslots = fields if fields is not None else (None, None, None, 0)
+    _check(lib().hhuff_casper_step(_dp(scratch), nslots, max_keys, _dp(slot), _dp(ops), _dp(op_first), nconn, _dp(data),
+                                   data.numel() if in_size is None else in_size, _dp(value_off), _dp(value_len), _dp(token),
+                                   nfslots, int(cookie_token), _dp(out), _dp(out_off), _dp(res), _stream(stream)),
+           "hhuff_casper_step")
+    return res
 
 
 def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_off=0, server_len=0, in_size=None,

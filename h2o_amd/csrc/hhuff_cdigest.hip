@@ -1,23 +1,9 @@
 // Cache digests on the device (include/hhuff.h (2m), hhuff_cdigest.h).
 //   cd_load_kernel<FIELDS>   one wave (a workgroup of 64) per request.  The element / attribute walk of hhuff_cdigest.h
 //                      runs wave-uniform: every lane holds the same iterator and only runs of plain bytes are skipped
-//                      64 at a time by a ballot.  A digest is checked (alphabet, tail) by the whole wave, then decoded in
-//                      rounds of 4,096 bits:
-//                        a. the round's 512 bytes and 8 of look-ahead are decoded from base64 into LDS, a quad a lane;
-//                        b. lane L takes bits 64 L .. 64 L + 63 as a window, MSB first, so clz finds the next 1;
-//                        c. every lane fills its window's table entry offset -> offset at which the search enters the
-//                           next window (a backward pass over its 64 offsets, in LDS: a terminator at t hands the search
-//                           to t + pbits + 1 <= 95, so the exit is below 32 and the table composes window by window);
-//                        d. the wave follows the chain through the 64 tables (64 dependent LDS reads, every lane reads
-//                           the same byte) and lane L keeps the offset at which the search enters its window;
-//                        e. every lane walks the terminators of its window: q from the distance to the search position
-//                           before (the round's carry or the nearest earlier lane's, by a max scan, for its first one),
-//                           the remainder from its and its neighbour's window; key counts and sums of q << pbits | r
-//                           plus one are prefix-summed over the wave (saturating, so the drop decision key >= 2^capacity_bits
-//                           is exact at any length), and a second walk puts the keys into an LDS stage that is
-//                           stored 64 lanes x 8 bytes at a time.
-//                      The search position, the running minimum and the key count carry into the next round; an unfinished
-//                      unary run is just a search position that lies rounds back.  The frame header is written when the
+//                      64 at a time by a ballot.  A digest is checked (alphabet, tail) and decoded by the whole wave
+//                      in rounds of 4,096 bits: hhuff_gcswave.h, which the CASPER kernel runs too.  The keys go to the
+//                      image 64 lanes x 8 bytes at a time while they fit.  The frame header is written when the
 //                      digest is complete and fits (append only: a dropped digest leaves the write position alone).
 //   cd_lookup_kernel   one lane per query: the segments' bytes by aligned dword loads and shifts into SHA-256's
 //                      16-word window (registers; no LDS, no scratch), then the checked frame walk with a bisection
@@ -27,6 +13,7 @@
 
 #include "hhuff.h"
 #include "hhuff_cdigest.h"
+#include "hhuff_gcswave.h"
 
 #define HHUFF_API extern "C" __attribute__((visibility("default")))
 
@@ -34,11 +21,7 @@ namespace hhuff {
 namespace {
 using namespace cd;
 
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kRoundBits = 4096, kRoundBytes = kRoundBits / 8u;
-constexpr uint32_t kBufBytes = kRoundBytes + 8u;  // a remainder of up to 31 bits behind bit 4095, and lane 63's neighbour
-constexpr uint32_t kStage = 512;                  // keys an LDS stage holds: a round has at most 4,096, commonly a few hundred
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+using gcsw::kWave;
 
 struct LoadArgs {
     const uint8_t* in;
@@ -74,145 +57,29 @@ struct DevSrc {
     }
 };
 
-template <class T, class Op>
-__device__ __forceinline__ T wave_scan(T v, uint32_t lane, Op op) {  // inclusive
-#pragma unroll
-    for (uint32_t d = 1; d < kWave; d <<= 1) {
-        const T o = __shfl_up(v, d);
-        if (lane >= d) v = op(o, v);
-    }
-    return v;
-}
-
-// The terminators of one window from entry offset e on: f(q, r) for every complete value, q counted from the search
-// position inside the window (the caller adds what lies before the window to the first).  Returns the search position
-// behind the last terminator, relative to the window, or kNone without one.
-template <class F>
-__device__ __forceinline__ uint32_t walk(uint64_t w, uint64_t wn, uint32_t e, uint32_t pbits, uint64_t base, uint64_t nbits, F&& f) {
-    uint32_t p = e;
-    bool any = false;
-    while (p < 64u) {
-        const uint64_t m = w & (~0ull >> p);
-        if (!m) break;
-        const uint32_t t = (uint32_t)__builtin_clzll(m), s = t + 1u;
-        any = true;
-        const uint32_t q = t - p;
-        p = s + pbits;
-        if (base + t + pbits >= nbits) break;  // the remainder is cut short: no key, and nothing behind it
-        const uint64_t x = s == 64u ? wn : (w << s) | (wn >> (64u - s));
-        f(q, pbits ? x >> (64u - pbits) : 0ull);
-    }
-    return any ? p : kNone;
-}
-
 struct WaveSink {
     const uint8_t* in;
     uint8_t* img;
     uint64_t size;
     uint32_t lane;
-    uint32_t* buf;    // kBufBytes
-    uint8_t* tab;     // [64 offsets][64 lanes]
-    uint64_t* stage;  // kStage
+    gcsw::Lds lds;
     uint64_t pos = kHeaderBytes;
     uint32_t nframes = 0, flags = 0;
     int32_t status = 0;
 
     __device__ __forceinline__ void reset() { pos = kHeaderBytes, nframes = 0, flags = 0; }
     __device__ __forceinline__ bool stopped() const { return status != 0; }
-    __device__ __forceinline__ uint64_t be64(uint32_t word) const {
-        return (uint64_t)__builtin_bswap32(buf[word]) << 32 | __builtin_bswap32(buf[word + 1u]);
-    }
 
     __device__ void digest(uint64_t start, uint64_t c, bool validators, bool complete) {
-        if (c % 4u == 1u) return;
-        bool ok = true;
-        for (uint64_t i = lane; i < c; i += kWave) ok = ok && b64_val(in[start + i]) != 0xFFu;
-        if (__ballot(!ok)) return;
-        const uint64_t nbytes = c * 3u / 4u, nbits = 8u * nbytes;
-        if (nbits < 10u) return;
         const bool head = size >= pos + kFrameBytes;
         uint64_t* const keys = reinterpret_cast<uint64_t*>(img + (head ? pos + kFrameBytes : 0u));
         const uint64_t room = head ? (size - pos - kFrameBytes) / 8u : 0u;  // keys are stored while they fit
-        uint32_t pbits = 0, cap = 0;
-        uint64_t limit = 0, p_in = 10, next_min = 0, nkeys = 0;
-        uint8_t* const bytes = reinterpret_cast<uint8_t*>(buf);
-        for (uint64_t R = 0; R < nbits && p_in < nbits; R += kRoundBits) {
-            // a. base64 -> the round's bytes (zeros behind the digest's last byte)
-            const uint64_t byte0 = R / 8u;
-            __syncthreads();
-            for (uint64_t j = byte0 / 3u + lane; 3u * j < byte0 + kBufBytes; j += kWave) {
-                uint32_t v = 0;
-#pragma unroll
-                for (uint32_t i = 0; i < 4u; ++i) v = v << 6 | (4u * j + i < c ? b64_val(in[start + 4u * j + i]) : 0u);
-#pragma unroll
-                for (uint32_t i = 0; i < 3u; ++i) {
-                    const uint64_t b = 3u * j + i;
-                    if (b >= byte0 && b < byte0 + kBufBytes) bytes[b - byte0] = b < nbytes ? (uint8_t)(v >> (16u - 8u * i)) : (uint8_t)0;
-                }
-            }
-            __syncthreads();
-            // b. windows
-            const uint64_t w = be64(2u * lane);
-            const uint64_t up = __shfl_down(w, 1u);
-            const uint64_t wn = lane == kWave - 1u ? be64(2u * kWave) : up;
-            if (R == 0) {
-                const uint64_t w0 = __shfl(w, 0);
-                pbits = (uint32_t)(w0 >> 54) & 31u, cap = ((uint32_t)(w0 >> 59) & 31u) + pbits, limit = 1ull << cap;
-            }
-            // c. the window's table
-            uint32_t x = 0;
-            for (int e = 63; e >= 0; --e) {
-                if ((w >> (63 - e)) & 1u) {
-                    const uint32_t nxt = (uint32_t)e + pbits + 1u;
-                    x = nxt >= 64u ? nxt - 64u : tab[nxt * kWave + lane];
-                }
-                tab[(uint32_t)e * kWave + lane] = (uint8_t)x;
-            }
-            __syncthreads();
-            // d. the chain through the windows
-            uint32_t e = p_in > R ? (uint32_t)(p_in - R) : 0u, mine = 0;  // (p_in - R < 32)
-            for (uint32_t L = 0; L < kWave; ++L) {
-                if (lane == L) mine = e;
-                e = tab[e * kWave + L];
-            }
-            // e. values: first walk, counts and sums
-            const uint64_t base = R + 64u * lane;
-            uint32_t cnt = 0;
-            uint64_t sum = 0;
-            const uint32_t pe = walk(w, wn, mine, pbits, base, nbits, [&](uint32_t q, uint64_t r) {
-                ++cnt, sum = sat_add(sum, sat_add(sat_value(q, r, pbits), 1u));
-            });
-            const uint64_t lastp = wave_scan(pe == kNone ? 0ull : base + pe, lane, [](uint64_t a, uint64_t b) { return a > b ? a : b; });
-            uint64_t before = __shfl_up(lastp, 1u);
-            before = lane == 0 || before < p_in ? p_in : before;          // the search position in front of this window's first
-            const uint64_t qfix = sat_shl(base + mine - before, pbits);  // what its unary run holds outside the window
-            if (cnt) sum = sat_add(sum, qfix);
-            const uint32_t cinc = wave_scan(cnt, lane, [](uint32_t a, uint32_t b) { return a + b; });
-            const uint64_t sinc = wave_scan(sum, lane, [](uint64_t a, uint64_t b) { return sat_add(a, b); });
-            const uint32_t total = (uint32_t)__shfl((int)cinc, (int)(kWave - 1u));
-            const uint64_t next_out = sat_add(next_min, __shfl(sinc, (int)(kWave - 1u)));
-            if (total != 0 && next_out - 1u >= limit) return;  // the round's last key: the digest is dropped
-            uint64_t sbefore = __shfl_up(sinc, 1u);
-            sbefore = lane == 0 ? 0ull : sbefore;
-            // second walk: the keys, through the stage
-            for (uint32_t s0 = 0; s0 < total; s0 += kStage) {
-                uint32_t idx = cinc - cnt - s0;  // (wraps below the stage's start: not stored)
-                uint64_t run = sat_add(next_min, sbefore), fix = qfix;
-                walk(w, wn, mine, pbits, base, nbits, [&](uint32_t q, uint64_t r) {
-                    const uint64_t key = sat_add(run, sat_add(sat_value(q, r, pbits), fix));
-                    if (idx < kStage) stage[idx] = key;
-                    run = key + 1u, fix = 0, ++idx;
-                });
-                __syncthreads();
-                const uint32_t n = total - s0 < kStage ? total - s0 : kStage;
-                for (uint32_t j = lane; j < n; j += kWave)
-                    if (nkeys + s0 + j < room) keys[nkeys + s0 + j] = stage[j];
-                __syncthreads();
-            }
-            nkeys += total, next_min = next_out;
-            const uint64_t plast = __shfl(lastp, (int)(kWave - 1u));
-            p_in = plast > p_in ? plast : p_in;
-        }
+        uint32_t cap = 0;
+        uint64_t nkeys = 0;
+        if (!gcsw::decode<true>(in, start, c, lane, lds, 0u, 0ull, &cap, &nkeys, [&](uint64_t i, uint64_t k) {
+                if (i < room) keys[i] = k;
+            }))
+            return;
         if (nkeys > 0xFFFFFFFFull || pos + kFrameBytes + 8u * nkeys > size) {
             status = HHUFF_CD_SPACE;
             return;
@@ -227,9 +94,9 @@ struct WaveSink {
 
 template <bool FIELDS>
 __global__ __launch_bounds__(kWave) void cd_load_kernel(LoadArgs A) {
-    __shared__ uint32_t buf[kBufBytes / 4u];
+    __shared__ uint32_t buf[gcsw::kBufBytes / 4u];
     __shared__ uint8_t tab[64u * kWave];
-    __shared__ uint64_t stage[kStage];
+    __shared__ uint64_t stage[gcsw::kStage];
     const uint32_t r = blockIdx.x, lane = threadIdx.x;
     const uint64_t d0 = A.dig_off[r], d1 = A.dig_off[r + 1u];
     if ((d0 & 15u) != 0 || d1 < d0) {  // no region to write to
@@ -238,7 +105,7 @@ __global__ __launch_bounds__(kWave) void cd_load_kernel(LoadArgs A) {
     }
     const uint64_t size = d1 - d0 < 0xFFFFFFF0ull ? d1 - d0 : 0xFFFFFFF0ull;  // (`bytes` is a u32)
     const DevSrc S{A.in, lane};
-    WaveSink K{A.in, A.dig + d0, size, lane, buf, tab, stage};
+    WaveSink K{A.in, A.dig + d0, size, lane, {buf, tab, stage}};
     uint32_t s0 = A.first[r], s1 = FIELDS ? A.nfields[r] : A.first[r + 1u];
     if (FIELDS) s1 = (uint64_t)s0 + s1 < A.nslots ? s0 + s1 : A.nslots;
     for (uint64_t sb = s0; sb < s1 && !K.stopped(); sb += kWave) {
@@ -276,17 +143,6 @@ struct LookupArgs {
     uint64_t* hash_out;
 };
 
-struct DevChunks {  // the aligned dword that holds in[pos], from that byte on
-    const uint8_t* in;
-    __device__ __forceinline__ uint32_t chunk(uint64_t pos, uint32_t rem, uint32_t* k) const {
-        const uintptr_t a = (uintptr_t)(in + pos);
-        const uint32_t r = (uint32_t)(a & 3u), n = 4u - r < rem ? 4u - r : rem;
-        const uint32_t d = *reinterpret_cast<const uint32_t*>(a - r);
-        *k = n;
-        return (__builtin_bswap32(d) << (8u * r)) & (0xFFFFFFFFu << (32u - 8u * n));
-    }
-};
-
 struct DevImage {
     const uint32_t* p;
     __device__ __forceinline__ uint32_t word(uint64_t i) const { return p[i]; }
@@ -304,8 +160,8 @@ __global__ __launch_bounds__(kLookupThreads) void cd_lookup_kernel(LookupArgs A)
         A.state[i] = HHUFF_CD_EINVAL;
         return;
     }
-    const DevChunks S{A.in};
-    SegWords<DevChunks> M(S, q + 2, q + 7);
+    const gcsw::DevChunks S{A.in};
+    SegWords<gcsw::DevChunks> M(S, q + 2, q + 7);
     const uint64_t hash = sha256_first8(M, M.nwords / 16u);
     if (A.hash_out) A.hash_out[i] = hash;
     const uint64_t d0 = A.dig_off[req], d1 = A.dig_off[req + 1u];

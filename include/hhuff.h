@@ -2075,6 +2075,95 @@ int hhuff_cache_digests_lookup(const uint8_t *dig, const uint64_t *dig_off /* [n
                                const uint8_t *in, uint64_t in_size, const hhuff_cd_query_t *queries, uint32_t nq,
                                int32_t *state /* [nq] */, uint64_t *hash_out /* [nq], may be NULL */, void *stream);
 
+/* (2n) CASPER: the cookie-borne digest of what a client has cached (lib/http2/casper.c), which h2o runs beside the
+ *      header-borne one of (2m): the request's `cookie` fields are consumed (lib/http2/connection.c:1912-1916), push_path
+ *      skips a path that h2o_http2_casper_lookup(path, 1) knows (connection.c:1905-1910), send_headers marks the path of
+ *      a pushed or blocking asset and puts h2o_http2_casper_get_cookie's bytes on the response as `set-cookie`
+ *      (lib/http2/stream.c:236-262).  Here the connection's key set is a slab in the caller's memory and all of it is
+ *      one device call, so decode -> intern -> casper -> hhuff_hpack_flatten_responses needs no host code.
+ *   1. State (h2o_http2_casper_t, casper.c:33-38).  Connection slot s owns the slab scratch[s * slab .. + slab), slab
+ *      = 16 + 8 max_keys rounded up to 16; hhuff_casper_scratch_bytes(nslots, max_keys) is all of them.  scratch is
+ *      16-byte aligned; a slab holds no address, so a plain copy moves a connection:
+ *        header, 16 B: "HHCS", u16 version (1), u8 capacity_bits, u8 remainder_bits, u32 nkeys, u32 max_keys
+ *        then nkeys ascending uint64_t keys, all below 2^63 - 1
+ *      max_keys <= HHUFF_CSP_MAX_KEYS (h2o's default of 13 capacity bits is sized for about 100 assets).  The kernels
+ *      treat a slab as untrusted bytes: a magic, version, capacity_bits outside 1..30, remainder_bits above 31, nkeys
+ *      above max_keys or a max_keys other than the call's gives HHUFF_CSP_EFORMAT for every op of that connection up
+ *      to its next HHUFF_CSP_INIT, and no access outside the slab whatever the header and the keys hold.
+ *   2. hhuff_casper_step: connection c works on slot slot[c] (c itself with slot == NULL) and runs its ops
+ *      ops[op_first[c] .. op_first[c + 1]) in the order listed; connections do not affect one another.  Two
+ *      connections of one call that name the same slot are the caller's error: the slab then holds what either one
+ *      wrote, and the call still stays inside the scratch.  res[o] = {status, value, nkeys after the op, at}.
+ *        HHUFF_CSP_INIT    a = capacity_bits 1..30, b = remainder_bits 0..31 (h2o: the host's http2-casper bits, and
+ *                          6): h2o_http2_casper_create (casper.c:55-65).  The set is empty afterwards, whatever the
+ *                          slab held.
+ *        HHUFF_CSP_CONSUME the cookie header value in[a .. a + b): h2o_http2_casper_consume_cookie (casper.c:103-169).
+ *                          The value must be longer than 11 bytes and begin with "h2o_casper=" (:109); everything
+ *                          behind that, to the value's end, goes to h2o_decode_base64url (lib/common/string.c:186-241:
+ *                          "-_" and "+/" both, tails of 2 and 3 characters filled with 'A', a tail of 1 or any foreign
+ *                          byte such as ';' or a blank drops the cookie); golombset_decode with remainder_bits and no
+ *                          5 + 5-bit header (deps/golombset/golombset.h:140-160: values until the bits run dry, a
+ *                          value cut short is no key, key = previous + 1 + value, never compared with
+ *                          2^capacity_bits); the retry loop (casper.c:118-128) accepts at most L = max(128,
+ *                          2^capacity_bits) keys and drops a cookie with more whole; the accepted keys are united
+ *                          with the set, an equal key kept once (:131-163).  value = the keys the cookie held; a
+ *                          dropped cookie gives 0 and status 0, as h2o says nothing.
+ *        HHUFF_CSP_CONSUME_FIELDS  the field slots a .. a + b (below nfslots) of value_off / value_len / token, the
+ *                          columns hhuff_intern_fields reads and writes over the arena `in`: every slot whose token
+ *                          equals cookie_token is consumed in slot order (connection.c:1912-1916).  value = the sum
+ *                          over the slots.  The op ends at the first slot that does not give status 0 with that
+ *                          status; the slots before it stay consumed.
+ *        HHUFF_CSP_LOOKUP  the path in[a .. a + b): h2o_http2_casper_lookup(path, 0) (casper.c:79-101): key = the first
+ *                          four bytes of SHA-1(path) read as a little-endian unsigned, & (2^capacity_bits - 1)
+ *                          (casper.c:40-53).  value = 1 if the key is in the set, else 0.
+ *        HHUFF_CSP_MARK    the same with set = 1: a key that is not in the set is inserted in order; value as LOOKUP.
+ *        HHUFF_CSP_COOKIE  h2o_http2_casper_get_cookie (casper.c:177-208), appended to the connection's region
+ *                          out[out_off[c] .. out_off[c + 1]): "h2o_casper=", base64url without padding
+ *                          (string.c:243-284) of golombset_encode(remainder_bits, keys) (golombset.h:123-138: for each
+ *                          key (key - next_min) >> r zero bits, a one and r remainder bits, MSB first, the last byte
+ *                          filled with zeros), "; Path=/; Expires=Tue, 01 Jan 2030 00:00:00 GMT; Secure".  at = the
+ *                          offset in `out` at which the op writes (the region's write position), value = the cookie's
+ *                          length; an empty set gives 0 and no bytes (:182-183).  h2o's cookie_cache is only a cache:
+ *                          the bytes are a function of the set.  They are usable as a header value of the response
+ *                          encoders.
+ *      Statuses: 0; HHUFF_CSP_SPACE: the union or the mark would pass max_keys, or the cookie does not fit what is
+ *      left of the region -- the set and the region's write position stay exactly as they were and nothing outside the
+ *      region is written; HHUFF_CSP_EINVAL: an unknown kind or a non-zero fourth word, a slot[c] at or above nslots,
+ *      bits out of range, a string that passes in_size, slots that pass nfslots (or no field columns); the state stays;
+ *      HHUFF_CSP_EFORMAT (rule 1).  Every status but 0 leaves value 0, except a CONSUME's SPACE, which still counts.
+ *   3. Two deviations from h2o.  Its key vector grows without a bound; here max_keys bounds it (HHUFF_CSP_SPACE).
+ *      Key sums saturate at 2^63 as in (2m) and a cookie with a key whose successor reaches it is dropped; h2o wraps
+ *      modulo 2^64.
+ *   4. Device arrays, asynchronous on `stream`; HHUFF_EINVAL and nothing enqueued for a NULL scratch, ops, op_first,
+ *      in, out, out_off or res, a scratch that is not 16-byte aligned, or max_keys of 0 or above HHUFF_CSP_MAX_KEYS;
+ *      value_off, value_len and token may be NULL when no HHUFF_CSP_CONSUME_FIELDS op is given; an empty batch
+ *      (nconn == 0) returns HHUFF_OK and enqueues nothing; hhuff_last_error_string() stays as it was. */
+#define HHUFF_CSP_INIT 1u
+#define HHUFF_CSP_CONSUME 2u
+#define HHUFF_CSP_CONSUME_FIELDS 3u
+#define HHUFF_CSP_LOOKUP 4u
+#define HHUFF_CSP_MARK 5u
+#define HHUFF_CSP_COOKIE 6u
+#define HHUFF_CSP_SPACE (-330)
+#define HHUFF_CSP_EINVAL (-331)
+#define HHUFF_CSP_EFORMAT (-332)
+#define HHUFF_CSP_MAX_KEYS 2048u
+typedef struct hhuff_casper_op { uint32_t kind, a, b, reserved; } hhuff_casper_op_t;               /* 16 bytes */
+typedef struct hhuff_casper_result { int32_t status; uint32_t value, nkeys, at; } hhuff_casper_result_t; /* 16 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_casper_op_t) == 16 && sizeof(hhuff_casper_result_t) == 16, "record sizes");
+#else
+typedef char hhuff_casper_record_sizes[sizeof(hhuff_casper_op_t) == 16 && sizeof(hhuff_casper_result_t) == 16 ? 1 : -1];
+#endif
+static inline uint64_t hhuff_casper_scratch_bytes(uint64_t nslots, uint64_t max_keys) {
+    return nslots * ((16 + 8 * max_keys + 15) & ~(uint64_t)15);
+}
+int hhuff_casper_step(void *scratch, uint32_t nslots, uint32_t max_keys, const uint32_t *slot /* [nconn] or NULL */,
+                      const hhuff_casper_op_t *ops, const uint32_t *op_first /* [nconn + 1] */, uint32_t nconn,
+                      const uint8_t *in, uint64_t in_size, const uint32_t *value_off, const uint32_t *value_len,
+                      const int32_t *token, uint32_t nfslots, int32_t cookie_token, uint8_t *out,
+                      const uint32_t *out_off /* [nconn + 1] */, hhuff_casper_result_t *res, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
