@@ -266,6 +266,10 @@ def lib():
         L.hhuff_cache_digests_lookup.argtypes = [_vp, _vp, u32, _vp, u64, _vp, u32, _vp, _vp, _vp]
         L.hhuff_casper_step.restype = ctypes.c_int
         L.hhuff_casper_step.argtypes = [_vp, u32, u32, _vp, _vp, _vp, u32, _vp, u64, _vp, _vp, _vp, u32, ctypes.c_int32, _vp, _vp, _vp, _vp]
+        L.hhuff_h2_sched_scratch_size.restype = u64
+        L.hhuff_h2_sched_scratch_size.argtypes = [u32, u32]
+        L.hhuff_h2_schedule.restype = ctypes.c_int
+        L.hhuff_h2_schedule.argtypes = [slots_p, u32, _vp, _vp, u32, _vp, _vp, u32, u32, _vp, u64] + [_vp] * 9 + [u64, ctypes.c_uint, _vp]
         _lib = L
     return _lib
 
@@ -294,7 +298,7 @@ EXPORTED = ("h2o_hpack_decode_huffman", "h2o_hpack_encode_huffman", "hhuff_decod
             "hhuff_h2_streams_commit_sent", "hhuff_h2_bodies", "hhuff_h3_bodies", "hhuff_h3_frame_data",
             "hhuff_h2_streams_image_bound", "hhuff_h2_streams_export", "hhuff_h2_streams_import",
             "hhuff_cache_digests_load", "hhuff_cache_digests_load_fields", "hhuff_cache_digests_lookup",
-            "hhuff_casper_step") + SLOTS_SYMBOLS
+            "hhuff_casper_step", "hhuff_h2_sched_scratch_size", "hhuff_h2_schedule") + SLOTS_SYMBOLS
 
 
 def _check(rc, what):
@@ -1527,6 +1531,61 @@ def casper_step(scratch, nslots, max_keys, ops, op_first, data, out, out_off, sl
                                    nfslots, int(cookie_token), _dp(out), _dp(out_off), _dp(res), _stream(stream)),
            "hhuff_casper_step")
     return res
+
+
+# include/hhuff.h (2o): hhuff_h2_sched_op_t and a slab's node as numpy records, and the section's constants
+H2_SCHED_OP_DTYPE = np.dtype([("stream_id", "<u4"), ("op", "<u4"), ("parent_id", "<u4"), ("weight", "<u2"), ("exclusive", "u1"),
+                              ("rsv", "u1")])
+H2_SCHED_NODE_DTYPE = np.dtype([("id", "<u4"), ("aseq", "<u4"), ("qseq", "<u4"), ("parent", "<u2"), ("weight", "<u2"),
+                                ("deficit", "<u2"), ("active_cnt", "<u2"), ("slot", "u1"), ("qoff", "u1"), ("self_active", "u1"),
+                                ("rsv", "u1")])
+H2Q_OPEN, H2Q_REBIND, H2Q_CLOSE, H2Q_ACTIVATE, H2Q_DEACTIVATE = 1, 2, 3, 4, 5
+H2SC_CONTINUE = 1
+H2SC_EINVAL, H2SC_ENOENT, H2SC_EEXIST, H2SC_EFULL, H2SC_ESLOT, H2SC_EFORMAT = -333, -334, -335, -336, -337, -338
+H2SC_MAX_NODES, H2SC_ROOT = 2048, 0xFFFF
+
+
+def h2_sched_scratch_size(nslots, max_nodes) -> int:
+    """include/hhuff.h hhuff_h2_sched_scratch_size; 0: a max_nodes the call refuses"""
+    return int(lib().hhuff_h2_sched_scratch_size(nslots, max_nodes))
+
+
+def h2_sched_tree(scratch, slot, max_nodes):
+    """the streams of slot `slot` of a scheduler scratch (a host copy): {stream id: (parent id, weight)}"""
+    slab = h2_sched_scratch_size(1, max_nodes)
+    raw = scratch[slot * slab:(slot + 1) * slab].cpu().numpy()
+    nodes = raw[32:32 + 24 * int(raw[12:16].view("<u4")[0])].view(H2_SCHED_NODE_DTYPE)
+    return {int(x["id"]): (0 if x["parent"] == H2SC_ROOT else int(nodes[x["parent"]]["id"]), int(x["weight"])) for x in nodes if x["id"]}
+
+
+def h2_schedule(max_nodes, scratch, sends, send_first, peers, out_off, ops=None, op_first=None, flags=0, slots=None, nsend=None,
+                out_size=None, stream=None, out=None):
+    """The HTTP/2 scheduler (include/hhuff.h hhuff_h2_schedule) on device tensors: scratch a uint8 tensor of
+    h2_sched_scratch_size bytes kept between calls (flags=H2SC_CONTINUE), sends the candidate H2_SEND_DTYPE records with
+    send_first int32 [nconn + 1], peers h2_control's, out_off the regions h2_frame_data will write (int32 [nconn + 1];
+    out_size: the size of its `out`, by default out_off[-1]), ops a uint8 tensor of H2_SCHED_OP_DTYPE records with op_first
+    int32 [nconn + 1], slots a ConnSlots.  Returns a dict of device tensors: ordered (uint8, the records for h2_frame_data
+    with the same send_first), order, pos (int32 per record), op_status (int32 per op), nvisit, cstatus (int32) and active
+    (uint8) per connection.  No host synchronisation with out_size given."""
+    import torch
+
+    dev = sends.device
+    nconn = send_first.numel() - 1
+    nsend = sends.numel() // 24 if nsend is None else nsend
+    nops = 0 if ops is None else ops.numel() // 16
+    if out_size is None:
+        out_size = int(out_off[-1].item()) & 0xFFFFFFFF
+    out = dict(out or {})
+    new = lambda k, n, dt: out.setdefault(k, torch.empty(max(1, n), dtype=dt, device=dev))  # noqa: E731
+    i32, u8 = torch.int32, torch.uint8
+    r = dict(ordered=new("ordered", nsend * 24, u8), order=new("order", nsend, i32), pos=new("pos", nsend, i32),
+             op_status=new("op_status", nops, i32), nvisit=new("nvisit", nconn, i32), cstatus=new("cstatus", nconn, i32),
+             active=new("active", nconn, u8))
+    _check(lib().hhuff_h2_schedule(_slots_ref(slots), max_nodes, _dp(ops), _dp(op_first), nops, _dp(sends), _dp(send_first), nsend,
+                                   nconn, _dp(peers), out_size, _dp(out_off), _dp(r["op_status"]), _dp(r["ordered"]), _dp(r["order"]),
+                                   _dp(r["pos"]), _dp(r["nvisit"]), _dp(r["cstatus"]), _dp(r["active"]), _dp(scratch),
+                                   scratch.numel(), flags, _stream(stream)), "hhuff_h2_schedule")
+    return r
 
 
 def hpack_flatten_responses(data, hdr, res, conn_first, nres, out_off, server_off=0, server_len=0, in_size=None,

@@ -2164,6 +2164,98 @@ int hhuff_casper_step(void *scratch, uint32_t nslots, uint32_t max_keys, const u
                       const int32_t *token, uint32_t nfslots, int32_t cookie_token, uint8_t *out,
                       const uint32_t *out_off /* [nconn + 1] */, hhuff_casper_result_t *res, void *stream);
 
+/* (2o) HTTP/2 scheduler: h2o's priority tree (lib/http2/scheduler.c) kept on the device, one tree per connection, and
+ *      h2o_http2_scheduler_run with emit_writereq_of_openref's rule (lib/http2/connection.c:1553-1597).  The send records
+ *      of (2k'') come out in h2o's visit order, so stream-table events -> ops -> hhuff_h2_streams_fill_sends ->
+ *      hhuff_h2_schedule -> hhuff_h2_frame_data -> hhuff_h2_streams_commit_sent needs no host code.  No byte is framed here.
+ *   1. State.  Slot s owns the slab scratch[s * slab .. + slab), slab = 32 + 24 max_nodes rounded up to 16;
+ *      hhuff_h2_sched_scratch_size(nslots, max_nodes) is all of them (0 for a max_nodes the call refuses).  max_nodes is
+ *      1 .. 2048; hhuff_h2_streams_entries() of the same configuration always has room.  A slab holds indices, never an
+ *      address:
+ *        header, 32 B: "HH2Q", max_nodes, the next sequence number, the table's high mark, the root queue's u64 bits and
+ *                      its ring offset, the streams in the tree
+ *        node, 24 B:   +0 stream id (0: free)  +4 place in the parent's _all_refs (a sequence number)  +8 place in the
+ *                      parent's queue slot (a sequence number)  +12 u16 parent (its index; 0xFFFF: the root)  +14 u16 weight
+ *                      +16 u16 _deficit  +18 u16 _active_cnt  +20 u8 ring slot (64: anchor257, 255: not queued)  +21 u8 the
+ *                      ring offset of its own queue  +22 u8 _self_is_active  +23 0
+ *      Without HHUFF_H2SC_CONTINUE, or with HHUFF_CONN_RESET in slots->flags[c], a connection starts with the empty tree
+ *      of h2o_http2_scheduler_init.  A continued slab with a wrong header, or a node whose fields leave their ranges, gives
+ *      the connection HHUFF_H2SC_EFORMAT: nothing is applied and the slab is not written.
+ *   2. Ops, ops[op_first[c] .. op_first[c+1]) clamped to nops, applied in order ahead of the run; op_status[o] is 0 or a
+ *      refusal, and a refused op changes nothing:
+ *        HHUFF_H2Q_OPEN        h2o_http2_scheduler_open(stream_id under parent_id, weight 1..257, exclusive)
+ *        HHUFF_H2Q_REBIND      h2o_http2_scheduler_rebind, with the move of a new parent that is the stream's descendant
+ *                              (draft-16 5.3.3) and the early return when nothing changes
+ *        HHUFF_H2Q_CLOSE       h2o_http2_scheduler_close: the children go to the parent in _all_refs order with weights
+ *                              (w_child * factor / 32768 + 1) / 2 clamped to 1..256, factor = (w * 65536 + total / 2) / total
+ *        HHUFF_H2Q_ACTIVATE / _DEACTIVATE   h2o_http2_scheduler_activate / _deactivate
+ *      parent_id 0 is the root.  A parent_id that is not in the tree is set_priority's fallback (connection.c:851-858): the
+ *      root, weight 16, not exclusive.  Weight 257 is h2o's "before everything" weight of pushed streams.
+ *      _EINVAL: an unknown op, stream_id 0 or above 2^31 - 1, parent_id above 2^31 - 1 or equal to stream_id, exclusive
+ *      above 1, rsv != 0, an OPEN / REBIND weight outside 1..257, or parent_id, weight or exclusive set on another op;
+ *      _ENOENT: no such stream;  _EEXIST: OPEN of a stream that is there;  _EFULL: OPEN with max_nodes streams in the tree.
+ *   3. Run.  candidates sends[send_first[c] .. send_first[c+1]) clamped to nsend: at most one per stream, window filled by
+ *      hhuff_h2_streams_fill_sends, in any order.  A record of a stream that is not in the tree, or of one listed earlier,
+ *      is never visited; nor is one that hhuff_h2_frame_data refuses for its stream_id (0 or above 2^31 - 1) or an
+ *      unknown flag bit, so no visit is charged for bytes the framer will not write (such a record still stands behind the
+ *      visits and stops the framer there with HHUFF_H2D_EINVAL).  The call has no body: body_off + body_len against
+ *      body_size is the framer's test alone, and a record that fails only that one is visited as any other.  With R = the size of out[out_off[c] .. out_off[c+1]) clamped to out_size (no byte of it is read
+ *      or written), W_c = peers[c].send_window, m = peers[c].max_frame_size and window() = 0 when R < 9, else
+ *      min(R - 9, W_c) (h2o_http2_conn_get_buffer_window without the latency optimisation): the run is made when
+ *      window() > 0 (do_emit_writereq), pops streams as h2o_http2_scheduler_run does -- the offset table x 65536, the
+ *      per-node deficit, 64 ring slots and anchor257, FIFO within a slot, a parent that is not itself active re-queued
+ *      before its children are run -- and each visit sends what one record of (2k'') with max_frames = 0 sends
+ *      (h2o_amd/csrc/hhuff_h2data.h), max_frames ignored.  The stream stays active iff the record is not _DONE and its
+ *      window is above 0 afterwards; the run ends when window() <= 0 after a visit.  An active stream without a
+ *      candidate is deactivated when it is popped, unvisited.
+ *      Outputs.  ordered[] holds, in the connection's own range of send_first, first the nvisit[c] visited records in
+ *      visit order, copied as they are, then the others in the order listed with window 0 (hhuff_h2_frame_data stops
+ *      those with _STREAM_WINDOW): `ordered` goes to hhuff_h2_frame_data with the same send_first, and sent[] there
+ *      equals what the visits sent.  order[r] = the index in `sends` of ordered[r]; pos[j] = where sends[j] went, counted
+ *      from the range's start.  active[c] = h2o_http2_scheduler_is_active(root) afterwards, stale queue bits included.
+ *      cstatus[c]: 0, HHUFF_H2SC_EINVAL (a peer whose max_frame_size is outside 16384 .. 16777215: the ops are applied,
+ *      no visit is made), HHUFF_H2SC_ESLOT ((2h) point 3) or HHUFF_H2SC_EFORMAT; under the last two every op of the
+ *      connection gets that status and nvisit[c] = active[c] = 0.
+ *   4. Device arrays (ordered must not overlap sends).  Returns HHUFF_EINVAL, before any device call, for a NULL array
+ *      (ops, op_first and op_status may be NULL with nops == 0), out_size >= 2^32, an unknown flag bit, max_nodes of 0 or
+ *      above 2048, a scratch too small or not 16-byte aligned, and (2h) point 4; nconn == 0 returns HHUFF_OK.
+ *      Asynchronous on `stream`, no host synchronisation, workspace from the library's pool, no atomics; bitwise
+ *      deterministic.  Nothing in ops, sends, op_first, send_first, out_off, peers or slots makes the call touch memory
+ *      outside the arrays' declared sizes or the connection's slab; ranges are clamped as (2k') clamps them.  peers is
+ *      read only. */
+typedef struct hhuff_h2_sched_op {   /* 16 bytes */
+    uint32_t stream_id, op /* HHUFF_H2Q_* */, parent_id;
+    uint16_t weight;                 /* 1 .. 257 */
+    uint8_t  exclusive, rsv /* 0 */;
+} hhuff_h2_sched_op_t;
+#ifdef __cplusplus
+static_assert(sizeof(hhuff_h2_sched_op_t) == 16, "record sizes");
+#else
+typedef char hhuff_h2_sched_record_sizes[sizeof(hhuff_h2_sched_op_t) == 16 ? 1 : -1];
+#endif
+#define HHUFF_H2Q_OPEN 1u
+#define HHUFF_H2Q_REBIND 2u
+#define HHUFF_H2Q_CLOSE 3u
+#define HHUFF_H2Q_ACTIVATE 4u
+#define HHUFF_H2Q_DEACTIVATE 5u
+#define HHUFF_H2SC_CONTINUE 1u        /* flags: the trees the previous call left in scratch carry over */
+#define HHUFF_H2SC_EINVAL (-333)      /* op status: a malformed op; cstatus: the peer record is out of range */
+#define HHUFF_H2SC_ENOENT (-334)      /* op status: no such stream */
+#define HHUFF_H2SC_EEXIST (-335)      /* op status: the stream is already in the tree */
+#define HHUFF_H2SC_EFULL (-336)       /* op status: the tree holds max_nodes streams */
+#define HHUFF_H2SC_ESLOT (-337)       /* cstatus, op status: the connection was refused ((2h) point 3) */
+#define HHUFF_H2SC_EFORMAT (-338)     /* cstatus, op status: the continued slab is not a tree of this max_nodes */
+uint64_t hhuff_h2_sched_scratch_size(uint32_t nslots, uint32_t max_nodes);
+int hhuff_h2_schedule(const hhuff_conn_slots_t *slots, uint32_t max_nodes,
+                      const hhuff_h2_sched_op_t *ops, const uint32_t *op_first /* [nconn + 1] */, uint32_t nops,
+                      const hhuff_h2_send_t *sends, const uint32_t *send_first /* [nconn + 1] */, uint32_t nsend,
+                      uint32_t nconn, const hhuff_h2_peer_t *peers,
+                      uint64_t out_size /* < 2^32 */, const uint32_t *out_off /* [nconn + 1] */,
+                      int32_t *op_status /* [nops] */, hhuff_h2_send_t *ordered /* [nsend] */,
+                      uint32_t *order /* [nsend] */, uint32_t *pos /* [nsend] */,
+                      uint32_t *nvisit, int32_t *cstatus, uint8_t *active /* [nconn] each */,
+                      void *scratch, uint64_t scratch_size, unsigned flags, void *stream);
+
 /* (3b) Pipelined host path (the socket-buffer -> pinned -> device -> pinned -> pool staging of
  *     SURVEY f3; replaces the caller-side copies around lib/http2/hpack.c:240-241).  Contiguous layout
  *     (in_off[n + 1], implicit output slots) only.  The batch is cut into chunks of about
